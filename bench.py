@@ -14,6 +14,11 @@ north star's 1 -> 8 GPU target is quoted on): every rank builds the GRM partial 
 partials are summed with an RCCL all-reduce over xGMI, every rank then holds K, runs the eigendecomposition (its
 O(n^3) stages dealt over the ranks, see janusx_amd/csrc/eigh.cpp) + null fit and scans its own SNP range.
 `--scaling weak` gives every rank m SNPs of an n x (m N) panel instead.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the record of those steps.  `--full` adds the side
+measurements: the CPU baseline, the extra legs of the default one-GPU run (the other BASELINE configs) and the one-rank RCCL
+overhead.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (`write_outputs`); with the same
+arguments the inputs are the same from run to run (seeded generators), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -217,6 +222,15 @@ def cpu_baseline(packed_cpu, n, y, mode, sample_m, threads, eig_cap=5000, scale_
     }
 
 
+def host_threads():
+    """Host threads of the CPU baseline: OMP_NUM_THREADS when it is set (the CPUs this process is given), else every core."""
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0])
+    except ValueError:
+        omp = 0
+    return omp if omp > 0 else (os.cpu_count() or 1)
+
+
 def grm_peak_tflops(i8_share):
     """Dense MFMA peak the GRM is priced against: the exact-integer SNPs run on the int8 pipes (5 POP/s), the rest on the f16
     pipes (2.5 PFLOP/s, three products per algorithmic product); a mixed panel is priced by the time-weighted (harmonic) mix."""
@@ -403,6 +417,42 @@ def one_gpu_same_workload(n, m, mode):
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy payload in all
+DUMP_SEED = 20260609        # fixed seed of the row sample taken when the outputs exceed DUMP_MAX_BYTES
+
+
+def write_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """`--dump-outputs`: every array of `arrays` (name -> float32 / float64 ndarray) as `path/<name>.npy`.  When they hold more
+    than `max_bytes` together, every array longer than one row is cut to the same fraction of its rows, drawn with a fixed
+    seed per row count (arrays of the same length share one sample), and the chosen row indices are written beside it as
+    `path/<name>_rows.npy` (float64).  -> summary dict for the detail record."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0
+    if total > max_bytes:
+        # a kept row costs its own bytes + 8 bytes of index; the short arrays are written whole; 64 kB left for the headers
+        small = sum(a.nbytes for a in arrays.values() if a.ndim == 0 or len(a) <= 1)
+        sampled = sum(a.nbytes + 8 * len(a) for a in arrays.values() if a.ndim > 0 and len(a) > 1)
+        frac = max(0.0, (max_bytes - small - (64 << 10)) / float(sampled))
+    written, files = 0, []
+    for name, a in arrays.items():
+        if frac < 1.0 and a.ndim > 0 and len(a) > 1:
+            k = max(1, int(len(a) * frac))
+            idx = np.sort(np.random.default_rng([DUMP_SEED, len(a)]).choice(len(a), k, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+            written += 8 * k
+            files.append(name + "_rows.npy")
+            a = a[idx]
+        a = np.ascontiguousarray(a)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+        files.append(name + ".npy")
+    return {"dir": os.path.abspath(path), "files": files, "bytes": int(written), "sampled": frac < 1.0}
+
+
 def emit(res):
     """Detail record to gpurun_out/bench_detail.json and to an EARLIER stdout line, then the headline as the last line."""
     detail = json.dumps(res, default=lambda o: None)
@@ -427,14 +477,22 @@ def main():
     ap.add_argument("--mode", default="lmm", choices=["lmm", "fvlmm"])
     ap.add_argument("--missing", type=float, default=0.0)
     ap.add_argument("--seed", type=int, default=20260609)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the CPU baseline, the extra legs of the default one-GPU run (the "
+                         "other BASELINE configs) and the one-rank RCCL overhead; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all: a fixed-seed row sample beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=2048)
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"])
     ap.add_argument("--leg", default=None, choices=["c1", "c2_fvlmm", "c3_chain", "c5_splmm", "c5_pcg"],
                     help="run ONE extra leg of the default run alone and print its record (profiling)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the two extra legs of the default one-GPU run (1 %% missing calls; BASELINE configs[3] on one GPU)")
+                    help="with --full: skip the extra legs of the default one-GPU run and the one-rank RCCL overhead")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world_env != args.gpus:
         # Started without a launcher (`python bench.py --gpus N`): start one rank per GPU as a CHILD process -- before anything
@@ -551,8 +609,9 @@ def main():
 
         step_no = [0]
         diag_sleep_ms = float(os.environ.get("JXGPU_BENCH_STEP_SLEEP_MS", "0") or 0)   # diagnostic: idle before every ODD step
+        final = {}                  # references to what the last timed step computed (--dump-outputs); nothing is copied
 
-        def one_step(record):
+        def one_step(record, last=False):
             t = {}
             torch.cuda.synchronize()
             step_no[0] += 1
@@ -637,6 +696,8 @@ def main():
                 kern["scan_flops"] = kern.get("scan_flops", 0.0) + (n_evals + len(rows)) * n * (1.5 * dim * (dim + 1) + 5 * dim + 8)
                 kern["scan_evals"] = kern.get("scan_evals", 0.0) + n_evals / max(1, len(rows))
                 kern["launches"] += 1
+            if last:
+                final.update(stats=out, keep=keep, af=af, miss=miss, rows=rows, s=s, null=model.null, geff=geff)
             return len(rows), geff, model.null, out
 
         for _ in range(warmup):
@@ -660,8 +721,8 @@ def main():
         t_start = time.perf_counter()
         kept = 0
         null = None
-        for _ in range(steps):
-            kept, geff, null, out = one_step(True)
+        for i in range(steps):
+            kept, geff, null, out = one_step(True, last=(i == steps - 1))
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
@@ -688,7 +749,7 @@ def main():
             dist.all_reduce(st_t, op=dist.ReduceOp.MAX)
             stage_max = {k: float(v) for k, v in zip(keys, st_t.tolist())}
         return dict(elapsed=float(el_t[0]), kept_total=float(kept_t[0]), kern=kern, stage=stage, null=null, packed=packed, placement=placement,
-                    y=y, x=x, eigh_sharded=eigh_sharded, m=m, stage_max=stage_max)
+                    y=y, x=x, eigh_sharded=eigh_sharded, m=m, stage_max=stage_max, final=final)
 
     def leg_summary(leg, n, steps):
         """Condensed record of an extra leg: whole-step rate, stage times and the two f16-MFMA kernels against the dense peak."""
@@ -886,6 +947,29 @@ def main():
     main_leg = run_leg(n, args.m, args.missing, args.steps, args.warmup)
     elapsed, kept_total, kern, stage, null = (main_leg[k] for k in ("elapsed", "kept_total", "kern", "stage", "null"))
     packed, y, x, eigh_sharded, m = (main_leg[k] for k in ("packed", "y", "x", "eigh_sharded", "m"))
+    dumped = None
+    if args.dump_outputs:
+        # what `pipeline.run_gwas` hands its caller, from the last timed step: the per-SNP table [beta, se, p] of the kept SNPs
+        # in BED order, the kept-SNP mask, allele frequency and missing rate of the kept SNPs, the null fit and the GRM's
+        # effective SNP count; plus the GRM's eigenvalues.  Several ranks: the per-SNP arrays of every rank's shard, gathered.
+        fin = main_leg["final"]
+        rows = fin["rows"]
+        keep_t = torch.from_numpy(fin["keep"].astype(np.float32)).to(dev)
+        afm_t = torch.from_numpy(np.stack([fin["af"][rows], fin["miss"][rows]], 1).astype(np.float32)).to(dev)
+        keep_all = pl.gather_results(keep_t).cpu().numpy()
+        afm = pl.gather_results(afm_t).cpu().numpy()
+        if rank == 0:
+            nf = fin["null"]
+            dumped = write_outputs(args.dump_outputs, {
+                "stats": fin["stats"].cpu().numpy().astype(np.float64),
+                "keep": keep_all,
+                "af": np.ascontiguousarray(afm[:, 0]),
+                "miss": np.ascontiguousarray(afm[:, 1]),
+                "null": np.array([nf.lbd, nf.ml0, nf.reml0, nf.sigma_g2, nf.sigma_e2, nf.pve], dtype=np.float64),
+                "grm_eff_m": np.array([fin["geff"]], dtype=np.float64),
+                "grm_eigenvalues": fin["s"].cpu().numpy().astype(np.float64)})
+        del fin, keep_t, afm_t
+    main_leg.pop("final", None)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -1094,17 +1178,20 @@ def main():
             "null": {"lbd": null.lbd, "pve": null.pve},
             "device": {"cus": int(info[0]), "clock_khz": int(info[1]), "hbm_mib": int(info[2])},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if dumped is not None:
+            res["dump_outputs"] = dumped
+        # everything below is a side measurement of `--full`; a plain run stops at the headline
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 from oracle import jx_oracle_c as OC
                 res["cpu_baseline"] = cpu_baseline(packed.cpu().numpy(), n, y, args.mode, args.cpu_sample,
-                                                   os.cpu_count() or 1)
+                                                   host_threads())
             except Exception as e:  # the baseline is a reported number, never the product path
                 res["cpu_baseline"] = {"error": repr(e)}
         # Extra legs of the default one-GPU run (BASELINE configs[2], -lmm, no missing calls): (1) the same shape with 1 %
         # missing calls (every SNP takes the fp16 hi/lo three-product path of the GRM and of the rotation), (2) one step of
         # BASELINE configs[3] (n = 50 000, m = 500 000: the shape the north star's 8-GPU target is quoted on) on this ONE GPU.
-        if (world == 1 and not distributed and not args.no_extra and args.mode == "lmm" and args.missing == 0.0
+        if (args.full and world == 1 and not distributed and not args.no_extra and args.mode == "lmm" and args.missing == 0.0
                 and (int(n), int(args.m)) == (20000, 200000)):
             del main_leg, packed
             torch.cuda.empty_cache()
@@ -1196,7 +1283,7 @@ def main():
                     try:
                         n_c = 20000
                         sub = leg["packed"][: args.cpu_sample, : n_c // 4].contiguous().cpu().numpy()
-                        cb = cpu_baseline(sub, n_c, leg["y"][:n_c], "lmm", args.cpu_sample, os.cpu_count() or 1, scale_to_n=50000,
+                        cb = cpu_baseline(sub, n_c, leg["y"][:n_c], "lmm", args.cpu_sample, host_threads(), scale_to_n=50000,
                                           m_full=500000)
                         res["extra_c4_1gpu"]["cpu_baseline"] = cb
                         res["extra_c4_1gpu"]["gpu_over_cpu_baseline"] = res["extra_c4_1gpu"]["value"] / cb["value"]
@@ -1248,7 +1335,7 @@ def main():
         # pack / ncclAllReduce / unpack, the band reduction in its sharded launch sequence (per block row, two collectives per
         # panel through the counted callback), the agreement checks, the column-sharded back-transformations with their gather --
         # against the unsharded stages of the main leg above.
-        if (world == 1 and not distributed and not args.no_extra and args.mode == "lmm" and args.missing == 0.0
+        if (args.full and world == 1 and not distributed and not args.no_extra and args.mode == "lmm" and args.missing == 0.0
                 and (int(n), int(args.m)) == (20000, 200000) and not os.environ.get("JXGPU_BENCH_CHILD")):
             try:
                 import socket

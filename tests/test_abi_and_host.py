@@ -22,7 +22,9 @@ def test_library_exports_every_declared_symbol():
     if not os.path.exists(_lib.LIB_PATH):
         import __graft_entry__ as g
         g.build()
-    h = ctypes.CDLL(_lib.LIB_PATH)
+    # through the package's loader: a bare ctypes.CDLL here, before torch, would map /opt/rocm's HIP runtime beside
+    # torch's own, and every GPU test later in the same process would find no device (see `_lib.lib`)
+    h = _lib.lib()
     syms = _declared_symbols()
     assert len(syms) >= 30
     for s in syms:
@@ -446,6 +448,33 @@ def test_bench_headline_line_is_short_strict_json():
     res["stages_ms_per_step"].update({f"stage_{i}": float(i) for i in range(400)})
     _, line2 = bench.headline_record(res)
     assert len(line2.encode()) < 6144 and "value" in json.loads(line2)
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """`bench.py --dump-outputs DIR` (`bench.write_outputs`): every array as DIR/<name>.npy, float32 / float64 only; beyond
+    64 MB in all, arrays of the same length share one fixed-seed row sample, written beside them, and the files stay in budget."""
+    import bench
+    rng = np.random.default_rng(3)
+    small = {"stats": rng.normal(size=(1000, 3)), "keep": np.ones(1200, np.float32), "null": np.arange(6.0)}
+    rec = bench.write_outputs(str(tmp_path / "a"), small)
+    assert not rec["sampled"] and sorted(rec["files"]) == ["keep.npy", "null.npy", "stats.npy"]
+    for name, a in small.items():
+        back = np.load(tmp_path / "a" / f"{name}.npy")
+        assert back.dtype == a.dtype and np.array_equal(back, a)
+    big = {"stats": rng.normal(size=(2_000_000, 3)), "af": rng.random(2_000_000, dtype=np.float32),
+           "keep": np.ones(3_000_000, np.float32), "grm_eff_m": np.array([7.0])}        # 80 MB
+    for d in ("b", "c"):
+        rec = bench.write_outputs(str(tmp_path / d), big, max_bytes=16 << 20)
+        assert rec["sampled"] and rec["bytes"] <= 16 << 20
+        assert sum(os.path.getsize(tmp_path / d / f) for f in rec["files"]) <= 16 << 20
+    rows = np.load(tmp_path / "b" / "stats_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "af_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "stats.npy"), big["stats"][rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "grm_eff_m.npy"), big["grm_eff_m"])
+    for f in rec["files"]:                                                            # same sample from run to run
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    with pytest.raises(TypeError, match="float32 / float64"):
+        bench.write_outputs(str(tmp_path / "d"), {"keep": np.ones(3, bool)})
 
 
 def test_warm_chain_offsets_host_rules():

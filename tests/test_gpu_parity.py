@@ -2228,6 +2228,60 @@ def test_bench_two_ranks_share_one_gpu():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_last_step_computed(tmp_path):
+    """A plain `bench.py` run (no `--full`) times `--steps` steps and carries no side measurement; `--dump-outputs DIR` writes
+    the last timed step's results, which are what `pipeline.run_gwas` returns for the same seeded inputs.  Two ranks sharing
+    the device (gloo): the per-SNP arrays of both shards, gathered in BED order."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import bench
+    from janusx_amd import pipeline
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, m, seed = 1200, 5000, 20260609
+    dump = tmp_path / "one"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--samples", str(n), "--snps", str(m), "--steps", "2",
+                          "--warmup", "1", "--seed", str(seed), "--dump-outputs", str(dump)], cwd=root, capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "cpu_baseline" not in d and "legs" not in d and "dist_overhead_ms" not in d
+    mk = d["config"]["m_kept"]
+    o = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert set(o) == {"stats", "keep", "af", "miss", "null", "grm_eff_m", "grm_eigenvalues"}
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values())
+    assert o["stats"].shape == (mk, 3) and o["keep"].shape == (m,) and int(o["keep"].sum()) == mk
+    assert o["af"].shape == o["miss"].shape == (mk,) and o["grm_eigenvalues"].shape == (n,)
+    assert abs(o["null"][0] - d["null"]["lbd"]) <= 1e-5 * d["null"]["lbd"]
+    # the same inputs through the product's entry point
+    dev = torch.device("cuda", 0)
+    packed, dos = bench.synth_panel_gpu(n, m, seed, dev)
+    y = bench.make_phenotype(dos, n, seed, dev)
+    res = pipeline.run_gwas(packed, n, y, mode="lmm")
+    assert np.array_equal(res.keep.astype(np.float32), o["keep"]) and int(o["grm_eff_m"][0]) == res.grm_eff_m
+    assert np.array_equal(res.af.astype(np.float32), o["af"]) and np.array_equal(res.miss.astype(np.float32), o["miss"])
+    # two processes: the eigensolver's run-to-run rounding (~1e-12 on the eigenvalues) moves the Brent optima slightly
+    assert abs(res.null.lbd - o["null"][0]) <= 1e-8 * res.null.lbd
+    be, se, pe = _assoc_err(o["stats"], res.stats)
+    assert be < 1e-5 and se < 1e-5 and pe < 1e-5, (be, se, pe)
+    # two ranks on the one device, weak scaling: every rank's shard of m SNPs
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["JXGPU_BENCH_BACKEND"] = "gloo"
+    dump2 = tmp_path / "two"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--samples", "600", "--snps", "3000",
+                          "--steps", "1", "--warmup", "0", "--scaling", "weak", "--dump-outputs", str(dump2)], env=env, cwd=root,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    mk = d["config"]["m_kept"]
+    assert np.load(dump2 / "keep.npy").shape == (6000,) and int(np.load(dump2 / "keep.npy").sum()) == mk
+    assert np.load(dump2 / "stats.npy").shape == (mk, 3) and np.load(dump2 / "af.npy").shape == (mk,)
+
+
+@pytest.mark.gpu
 def test_cli_two_ranks_share_one_gpu(tmp_path):
     """`jx grm` / `jx gwas -lmm -fvlmm` started with one process per rank (torch.distributed.run, two ranks on the one device,
     gloo collectives): the product's own multi-GPU composition (pipeline.build_grm: SNP-sharded accumulation + one reduction;
