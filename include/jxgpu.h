@@ -463,6 +463,19 @@ int jxg_p32_transpose(const uint8_t *d_p32, int64_t m_total, int n, const int32_
                       void *stream);
 int jxg_packed_dot_t32(const uint8_t *d_t32, int n, int nrows, const float *d_lut, const double *d_beta, void *d_work,
                        double *d_out, void *stream);
+/* Skinny products of the randomized SVD (`jx pca -rsvd`; src/stats/rsvd.rs:1548-1661) with the centred additive design
+ * Z[r][i] = d_ab[r][0] + d_ab[r][1] g (g = 0 / 1 / 2 for the codes 00 / 10 / 11, missing calls 01 -> 0; d_ab (nrows, 2) f64):
+ *   jxg_packed_mm_cols : d_w (nrows, kp) = Z Q,   d_q (n, kp) f64 row-major, P32 image + row list as jxg_packed_tdot;
+ *   jxg_packed_tmm_cols: d_y (n, kp)     = Z' W,  d_w (nrows, kp) f64, sample-major T32 image of the same rows
+ *                        (`jxg_p32_transpose`).
+ * Dose and missing bit planes against a four-digit int8 image of each column on v_mfma_i32_16x16x64_i8 (exact sums, f64
+ * merge, csrc/k_rsvd.hip); Z' W adds its SNP slices in a fixed order (run-to-run identical bits).  1 <= kp; up to 32 columns
+ * are one pass over the payload, more loop over passes of 32.  The i32 plane sums are exact over 2^23 elements: Z Q refuses
+ * n > 8 388 608, Z' W cuts its SNP slices at that length.  Outputs are overwritten. */
+int jxg_packed_mm_cols(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const double *d_ab,
+                       const double *d_q, int kp, double *d_w, void *stream);
+int jxg_packed_tmm_cols(const uint8_t *d_t32, int n, int nrows, const double *d_ab, const double *d_w, int kp, double *d_y,
+                        void *stream);
 
 /* SparseLMM exact scan on rotated rows (`exact_scan_blocks_core`, src/stats/splmm.rs:2567-2880, with V = K + lambda I
  * handled spectrally): per row g~ = U'g the sums g~'Wg~, g~'(W X~), g~.(Py)~ of E2, then the score-form Wald test of

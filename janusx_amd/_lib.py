@@ -98,6 +98,8 @@ SIGNATURES = {
     "jxg_t32_bytes": [c_i, c_i],
     "jxg_p32_transpose": [c_p, c_l, c_i, c_p, c_i, c_p, c_p],
     "jxg_packed_dot_t32": [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "jxg_packed_mm_cols": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p],
+    "jxg_packed_tmm_cols": [c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p],
     "jxg_packed_dot": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "jxg_cross_dot": [c_p, c_i, c_l, c_p, c_i, c_p, c_i, c_p, c_d, c_p, c_p],
     "jxg_splmm_exact_scan_dev": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_p],

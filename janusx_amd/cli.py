@@ -6,12 +6,13 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-lmm | -lmm2 | -fvlmm) [-k 1|2|GRM.npy] [-c COV.tsv]
                             [-maf 0.02] [-geno 0.05] [-het 1.0] [-o OUT] [-force-model]
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
+  python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
 
 Outputs: `{out}.{trait}.lmm.tsv` / `.lmm2.tsv` / `.fvlmm.tsv` / `.splmm2.tsv` (`gwas -splmm-exact [cutoff]`, exact SparseLMM scan) / `.splmm.tsv` (`gwas -splmm [cutoff]`, GRAMMAR-gamma SparseLMM scan); `{out}.cGRM.npy` (method 1) or `.sGRM.npy` (method 2) + `.npy.id`; `{out}.spgrm` + `.spgrm.id` with `grm -sparse [cutoff]`;
-`{out}.{trait}.gs.GBLUP.tsv` (sample, observed, predicted, fold) for `gs`.
+`{out}.{trait}.gs.GBLUP.tsv` (sample, observed, predicted, fold) for `gs`; `{out}.eigenvec` + `{out}.eigenval` for `pca`.
 Only PLINK BED input, the additive model, the -lmm / -fvlmm scans and the GBLUP branch of `-BLUP`
 (python/janusx/gs/blup.py:72-163 routes n <= BLUP_SMALL_N there; `gblup_reml_npy_grm` call of
 python/janusx/gs/workflow.py:9122) are built; VCF/HMP readers, PCs (-q), plots, the history DB, the
@@ -828,6 +829,103 @@ def cmd_gs_rrblup(args):
     return 0
 
 
+def _resolve_pca_grm(spec):
+    """-k PATH or PREFIX (python/janusx/script/pca.py:1720-1760): PREFIX.cGRM.npy / .sGRM.npy / .grm.npy (then .txt); sample ids
+    from {file}.id -> (path, ids)."""
+    cands = [spec] + [f"{spec}.{t}.{e}" for e in ("npy", "txt") for t in ("cGRM", "sGRM", "grm")]
+    path = next((c for c in cands if os.path.isfile(c)), None)
+    if path is None:
+        raise SystemExit(f"GRM not found: {spec} (tried {', '.join(cands)})")
+    if not os.path.exists(path + ".id"):
+        raise SystemExit(f"{path}.id not found (sample ids of the GRM)")
+    ids = [ln.split()[0] for ln in open(path + ".id") if ln.strip()]
+    return path, ids
+
+
+def _write_pca(out, ids, eigvec, eigval, dim, total_variance=None):
+    """{out}.eigenvec (id + the first `dim` columns, %.6f, tab, no header; pca.py:1700-1716) and {out}.eigenval (eigenvalue,
+    explained ratio, %.8f, tab; `_write_eigenval_table`, pca.py:795-820)."""
+    ev = np.asarray(eigval, dtype=np.float64).reshape(-1)
+    total = float(np.sum(ev)) if total_variance is None else float(total_variance)
+    ratio = ev / total if (np.isfinite(total) and total > 0.0) else np.zeros_like(ev)
+    vec = np.asarray(eigvec, dtype=np.float64)[:, :dim]
+    with open(f"{out}.eigenvec", "w") as fh:
+        for sid, row in zip(ids, vec):
+            fh.write("\t".join([str(sid)] + ["%.6f" % v for v in row]) + "\n")
+    np.savetxt(f"{out}.eigenval", np.column_stack([ev, ratio]), fmt=["%.8f", "%.8f"], delimiter="\t")
+
+
+def cmd_pca(args):
+    """`jx pca` (python/janusx/script/pca.py:1134-1265): -bfile -> method-1 GRM with QC and its eigendecomposition, or with -rsvd
+    the randomized SVD of the genotypes (`admx_rsvd_stream_sample`); -k -> eigendecomposition of a GRM file."""
+    for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"pca: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    for flag, what in (("qcov", "-c/--qcov"), ("plot", "-plot"), ("plot3d", "-plot3D"), ("group", "-group"),
+                       ("palette", "-palette")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"pca: {what} (plots and the view-only mode) is out of scope on this build")
+    if bool(args.bfile) == bool(args.grm):
+        raise SystemExit("pca needs exactly one of -bfile PREFIX or -k GRM")
+    rsvd = args.rsvd is not None
+    power, tol = 3, 0.1
+    if rsvd:
+        if args.grm:
+            raise SystemExit("pca: -rsvd works on genotype input (-bfile), not on a GRM (-k)")
+        if len(args.rsvd) > 2:
+            raise SystemExit("-rsvd accepts at most two optional values: [power] [tol].")
+        try:
+            if len(args.rsvd) >= 1:
+                power = int(args.rsvd[0])
+            if len(args.rsvd) >= 2:
+                tol = float(args.rsvd[1])
+        except ValueError:
+            raise SystemExit("Invalid -rsvd values: use '-rsvd 3' or '-rsvd 3 0.1' (power integer >= 0, tol > 0)") from None
+        if power < 0:
+            raise SystemExit("RSVD power must be >= 0.")
+        if not tol > 0:
+            raise SystemExit("RSVD tol must be > 0.")
+    if args.dim < 1:
+        raise SystemExit(f"pca: -dim must be >= 1 (got {args.dim})")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("PCA runs on one GPU: start it without the launcher")
+    import torch
+    from . import janusx as jxrs
+    from . import pipeline as pl
+    from .bed import read_fam_ids, snps_only_mask, stage_bed_payload
+    out = _resolve_out(args, args.bfile or args.grm)
+    t0 = time.perf_counter()
+    total_variance = None
+    if args.grm:
+        path, ids = _resolve_pca_grm(args.grm)
+        k = np.loadtxt(path, dtype=np.float64) if path.lower().endswith(".txt") else np.load(path)
+        if k.ndim != 2 or k.shape != (len(ids), len(ids)):
+            raise SystemExit(f"GRM shape {k.shape} does not match the {len(ids)} ids of {path}.id")
+        s, ut = pl.eigh_from_grm(torch.from_numpy(np.ascontiguousarray(k)).to(torch.device("cuda", torch.cuda.current_device())),
+                                 ridge=0.0)
+        eigval, eigvec = s.cpu().numpy()[::-1], ut.cpu().numpy()[::-1].T
+        what = f"GRM {path}"
+    else:
+        ids = read_fam_ids(args.bfile)
+        packed_t, n, bim = stage_bed_payload(args.bfile, None)
+        if rsvd:
+            ev, vec, total_variance, rounds = jxrs._admx_rsvd(args.bfile, args.dim, 42, power, tol, bool(args.snps_only),
+                                                              args.maf, args.geno, payload=(packed_t, n, bim))
+            eigval, eigvec = ev.astype(np.float64), vec
+            what = f"randomized SVD ({rounds} power rounds)"
+        else:
+            if args.snps_only:
+                packed_t = packed_t[torch.from_numpy(np.nonzero(snps_only_mask(bim))[0]).to(packed_t.device)]
+            k_t, eff, _ = pl.build_grm(packed_t, n, 1, args.maf, args.geno)
+            s, ut = pl.eigh_from_grm(k_t, ridge=0.0)
+            eigval, eigvec = s.cpu().numpy()[::-1], ut.cpu().numpy()[::-1].T
+            what = f"GRM method 1 (eff_m={eff})"
+    dim = min(int(args.dim), eigvec.shape[1])
+    _write_pca(out, ids, eigvec, eigval, dim, total_variance)
+    print(f"PCA: {what}, n={len(ids)} dim={dim} -> {out}.eigenvec, {out}.eigenval ({time.perf_counter() - t0:.2f}s)")
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="jx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -920,6 +1018,31 @@ def main(argv=None):
     q.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
     q.add_argument("-t", "--thread", type=int, default=0, help="accepted for compatibility; unused")
     q.set_defaults(func=cmd_gs)
+    c = sub.add_parser("pca")
+    c.add_argument("-bfile", "--bfile", default=None)
+    c.add_argument("-k", "--grm", dest="grm", default=None,
+                   help="GRM file or prefix (.cGRM.npy / .sGRM.npy / .grm.npy / .txt with a sibling .id)")
+    c.add_argument("-vcf", "--vcf", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-hmp", "--hmp", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-file", "--file", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-dim", "--dim", type=int, default=3)
+    c.add_argument("-maf", "--maf", type=float, default=0.02)
+    c.add_argument("-geno", "--geno", type=float, default=0.05)
+    c.add_argument("-rsvd", "--rsvd", nargs="*", default=None, metavar="RSVD_ARG",
+                   help="randomized SVD of the genotypes: '-rsvd', '-rsvd 3' or '-rsvd 3 0.1' (power, tol; seed 42)")
+    c.add_argument("-snps-only", "--snps-only", dest="snps_only", action="store_true", default=False,
+                   help="drop sites whose alleles are not single A/C/G/T")
+    c.add_argument("-c", "--qcov", dest="qcov", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-plot", "--plot", dest="plot", action="store_true", default=False, help=argparse.SUPPRESS)
+    c.add_argument("-plot3D", "--plot3D", dest="plot3d", action="store_true", default=False, help=argparse.SUPPRESS)
+    c.add_argument("-group", "--group", dest="group", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-palette", "--palette", dest="palette", default=None, help=argparse.SUPPRESS)
+    c.add_argument("-o", "--out", default=None)
+    c.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
+    c.add_argument("-mem", "--memory", dest="memory", type=float, default=None, help="accepted for compatibility; unused")
+    c.add_argument("-v", "--verbose", action="store_true", default=False, help="accepted for compatibility")
+    c.add_argument("-t", "--thread", type=int, default=0, help="accepted for compatibility; unused")
+    c.set_defaults(func=cmd_pca)
     args = ap.parse_args(argv)
     return args.func(args)
 

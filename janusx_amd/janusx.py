@@ -4261,3 +4261,306 @@ fastlmm_reml_chunk_f32 = _out_of_scope("fastlmm_reml_chunk_f32", "the FastLMM lo
 fastlmm_reml_null_f32 = _out_of_scope("fastlmm_reml_null_f32", "the FastLMM low-rank model")
 fastlmm_assoc_chunk_f32 = _out_of_scope("fastlmm_assoc_chunk_f32", "the FastLMM low-rank model")
 
+
+
+# ---- randomized SVD of the packed genotypes (`jx pca -rsvd`) ------------------------------------------------------------------
+
+def _splitmix64(z):
+    """SplitMix64 finaliser on a uint64 numpy array (wrapping arithmetic)."""
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def rsvd_omega(seed, rows, kp):
+    """The random start of both randomized SVDs: Omega (rows, kp) f64, entry (r, c) a standard normal drawn from the
+    counter-based hash of (seed, r, c) alone -- u_j = (SplitMix64(s + 2 (65536 r + c) + j) >> 11 + 1) 2^-53 for j = 0, 1 with
+    s = SplitMix64(seed), then Box-Muller sqrt(-2 ln u_0) cos(2 pi u_1).  Row r is the r-th SNP row of the product (kept-row index).
+    The reference draws Omega from StdRng + StandardNormal (ziggurat); the PCs agree with it to within the approximation error of
+    the method, not bit for bit."""
+    rows, kp = int(rows), int(kp)
+    if kp > 65536:
+        raise RuntimeError("rsvd_omega: kp must be <= 65536")
+    s = _splitmix64(np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))[0]
+    ctr = (np.arange(rows, dtype=np.uint64)[:, None] * np.uint64(65536) + np.arange(kp, dtype=np.uint64)[None, :])
+    with np.errstate(over="ignore"):
+        base = s + np.uint64(2) * ctr
+        u0 = ((_splitmix64(base) >> np.uint64(11)).astype(np.float64) + 1.0) * 2.0 ** -53
+        u1 = ((_splitmix64(base + np.uint64(1)) >> np.uint64(11)).astype(np.float64) + 1.0) * 2.0 ** -53
+    return np.sqrt(-2.0 * np.log(u0)) * np.cos(2.0 * np.pi * u1)
+
+
+def _rsvd_row_design(maf32, flip):
+    """(nrows, 2) f64 (a, b) of the centred additive design: z = (flip ? 2 - g : g) - 2 maf (f32 mean, as
+    `prepare_packed_block_centered_mean_scale_f32`, src/decode/decode.rs:509-532), missing calls 0."""
+    mean = (np.float32(2.0) * np.asarray(maf32, dtype=np.float32)).astype(np.float64)
+    flip = np.asarray(flip, dtype=bool)
+    ab = np.empty((len(mean), 2), dtype=np.float64)
+    ab[:, 0] = np.where(flip, 2.0 - mean, -mean)
+    ab[:, 1] = np.where(flip, -1.0, 1.0)
+    return ab
+
+
+class _RsvdOperator:
+    """Z Q and Z' W of the centred design over the rows `rows` of a Panel (`jxg_packed_mm_cols` / `jxg_packed_tmm_cols`; the
+    sample-major T32 image of the rows is built once)."""
+
+    def __init__(self, panel, rows, ab):
+        import torch
+        from . import pipeline as pl
+        self.panel, self.dev = panel, panel.device
+        self.nrows = int(ab.shape[0])
+        self.rows_t = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(self.dev)
+        self.ab = torch.from_numpy(np.ascontiguousarray(ab, dtype=np.float64)).to(self.dev)
+        self.t32 = torch.empty(int(lib().jxg_t32_bytes(panel.n, self.nrows)), dtype=torch.uint8, device=self.dev)
+        check(lib().jxg_p32_transpose(panel.p32.data_ptr(), panel.m, panel.n, pl._ptr(self.rows_t), self.nrows,
+                                      self.t32.data_ptr(), pl._stream()))
+
+    def zq(self, q):
+        import torch
+        from . import pipeline as pl
+        q = q.contiguous()
+        kp = int(q.shape[1])
+        w = torch.empty((self.nrows, kp), dtype=torch.float64, device=self.dev)
+        check(lib().jxg_packed_mm_cols(self.panel.p32.data_ptr(), self.panel.m, self.panel.n, pl._ptr(self.rows_t), self.nrows,
+                                       self.ab.data_ptr(), q.data_ptr(), kp, w.data_ptr(), pl._stream()))
+        return w
+
+    def ztw(self, w):
+        import torch
+        from . import pipeline as pl
+        w = w.contiguous()
+        kp = int(w.shape[1])
+        y = torch.empty((self.panel.n, kp), dtype=torch.float64, device=self.dev)
+        check(lib().jxg_packed_tmm_cols(self.t32.data_ptr(), self.panel.n, self.nrows, self.ab.data_ptr(), w.data_ptr(), kp,
+                                        y.data_ptr(), pl._stream()))
+        return y
+
+
+def _rsvd_qr(x):
+    """Q of the modified Gram-Schmidt QR (`qr_normalize_mgs`, src/stats/rsvd.rs:1377-1417): Householder QR with the signs
+    that make diag(R) positive; a column whose residual norm is <= 1e-12 fails like the reference."""
+    import torch
+    q, r = torch.linalg.qr(x, mode="reduced")
+    d = torch.diagonal(r)
+    bad = ~(torch.isfinite(d) & (d.abs() > 1e-12))
+    if bool(bad.any()):
+        j = int(torch.nonzero(bad)[0, 0])
+        raise RuntimeError(f"QR normalization failed: near-dependent column at j={j}")
+    return q * torch.sign(d)[None, :]
+
+
+def _rsvd_lu(x, lu_eps=1e-10, cond_min_ratio=1e-8):
+    """`lu_normalize_with_qr_fallback` (src/stats/rsvd.rs:1419-1546) -> (Q, used_lu)."""
+    import torch
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    if rows < cols:
+        return _rsvd_qr(x), False
+    # factor of the n x kp block alone: pivots as row swaps (no dense n x n permutation), Q = P' L by a row index
+    lu, piv = torch.linalg.lu_factor(x)
+    d = torch.diagonal(lu[:cols]).abs()
+    ok = bool(torch.isfinite(d).all()) and bool((d > lu_eps).all())
+    if ok:
+        dmin, dmax = float(d.min()), float(d.max())
+        ok = dmax > lu_eps and dmin > lu_eps and (dmin / dmax) >= cond_min_ratio
+    if not ok:
+        return _rsvd_qr(x), False
+    perm = np.arange(rows)
+    for jj, pj in enumerate(piv.cpu().numpy().astype(np.int64) - 1):     # LAPACK ipiv: row jj swapped with row pj, in order
+        perm[jj], perm[pj] = perm[pj], perm[jj]
+    l = torch.tril(lu, diagonal=-1)
+    l[:cols].fill_diagonal_(1.0)
+    q = torch.empty_like(l)
+    q[torch.from_numpy(perm).to(x.device)] = l                      # row perm[i] of X is row i of P X = L U
+    nrm = torch.linalg.vector_norm(q, dim=0)
+    if not bool((torch.isfinite(nrm) & (nrm > lu_eps)).all()):
+        return _rsvd_qr(x), False
+    return q / nrm[None, :], True
+
+
+def _rsvd_engine(op, kp, k_eff, varsum, seed, power, tol, mode):
+    """Shifted subspace iteration of `rsvd_packed_subset` (mode "lu", src/stats/rsvd.rs:1589-1661) or of
+    `rsvd_stream_sample_packed_impl` (mode "svd", src/stats/adamixture.rs:3590-3700) -> (eigvals f64 (k_eff), eigvecs f64
+    (n, k_eff) device, power rounds done)."""
+    import torch
+    omega = torch.from_numpy(rsvd_omega(seed, op.nrows, kp)).to(op.dev)
+    y = op.ztw(omega)
+    del omega
+    if mode == "lu":
+        q = _rsvd_qr(y)
+    else:
+        q = torch.linalg.svd(y, full_matrices=False)[0]
+    sk = np.zeros(kp, dtype=np.float64)
+    alpha = 0.0
+    q_is_qr = True
+    rounds = 0
+    for it in range(int(power)):
+        y = op.ztw(op.zq(q)) - alpha * q
+        if mode == "lu":
+            if it + 1 >= power:
+                q, q_is_qr = _rsvd_qr(y), True
+            else:
+                q, used_lu = _rsvd_lu(y)
+                q_is_qr = not used_lu
+            s_y = np.sort(torch.linalg.vector_norm(y, dim=0).cpu().numpy())[::-1]
+        else:
+            u, s, _ = torch.linalg.svd(y, full_matrices=False)
+            q = u
+            s_y = s.cpu().numpy()
+        rounds = it + 1
+        if it > 0:
+            sk_now = s_y[:k_eff] + alpha
+            rel = np.abs(sk_now - sk[:k_eff]) / np.maximum(sk_now, 1e-12)
+            sk[:k_eff] = sk_now
+            if float(rel.max()) < tol:
+                if mode == "lu" and not q_is_qr:
+                    q, q_is_qr = _rsvd_qr(q), True
+                break
+        else:
+            sk[:kp] = s_y[:kp] + alpha
+        tail = float(s_y[kp - 1])
+        if alpha < tail:
+            alpha = 0.5 * (alpha + tail)
+    if mode == "lu" and not q_is_qr:
+        q = _rsvd_qr(q)
+    w = op.zq(q)
+    gram = (w.T @ w).cpu().numpy()
+    ev, v = np.linalg.eigh(0.5 * (gram + gram.T))
+    order = np.argsort(-ev, kind="stable")
+    ev, v = np.maximum(ev[order], 1e-12), v[:, order]
+    eigvals = ev[:k_eff] / float(varsum)
+    eigvecs = q @ torch.from_numpy(np.ascontiguousarray(v[:, :k_eff])).to(op.dev)
+    return eigvals, eigvecs, rounds
+
+
+def _rsvd_panel(packed, n_samples, sample_indices):
+    """Panel of a host (numpy) or device (torch CUDA) payload over the selected samples."""
+    import torch
+    from . import pipeline as pl
+    pk, _ptr_unused, m = _payload(packed, n_samples)
+    if m == 0:
+        raise RuntimeError("packed matrix has zero SNP rows")
+    idx = None
+    if sample_indices is not None:
+        idx = _c(sample_indices, np.int64).ravel()
+        if idx.size == 0:
+            raise RuntimeError("sample_indices must not be empty")
+        if idx.min() < 0 or idx.max() >= int(n_samples):
+            raise RuntimeError("sample_indices out of range")
+    if _is_device_tensor(pk):
+        payload = pk
+    else:
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)          # a read-only host array: only read on its way to the device
+            payload = torch.from_numpy(pk).to(torch.device("cuda", torch.cuda.current_device()))
+    return pl.Panel(payload, int(n_samples), idx)
+
+
+def rsvd_packed_subset(packed, n_samples, k, sample_indices=None, seed=42, power=5, tol=1e-1):
+    """src/stats/rsvd.rs:1548-1782: randomized SVD of the centred additive design of a packed payload (m, ceil(n / 4)) over the
+    selected samples -> (eigvals f32 (k_eff), eigvecs f32 (n, k_eff), row_maf f32 (m), row_flip bool (m)).  Row statistics over
+    all m rows without QC (`packed_subset_row_stats`, :208-258); kp = min(max(k_eff + 10, 20), m, n); the two products per
+    round run on the device (`jxg_packed_mm_cols` / `jxg_packed_tmm_cols`), the small dense steps in torch.  The start block is
+    `rsvd_omega` (not the reference's StdRng stream).  `packed` may be a torch CUDA uint8 tensor (used in place)."""
+    return _rsvd_packed_subset(packed, n_samples, k, sample_indices, seed, power, tol)[:4]
+
+
+def _rsvd_packed_subset(packed, n_samples, k, sample_indices, seed, power, tol):
+    import math
+    k, n_samples, power = int(k), int(n_samples), int(power)
+    if k <= 0:
+        raise RuntimeError("k must be > 0")
+    if n_samples <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    tol = float(np.float32(tol))
+    if not (math.isfinite(tol) and tol > 0.0):
+        raise RuntimeError("tol must be positive and finite")
+    panel = _rsvd_panel(packed, n_samples, sample_indices)
+    n, m = panel.n, panel.m
+    c = panel.counts().astype(np.int64)
+    nm = n - c[:, 0]
+    alt = c[:, 1] + 2 * c[:, 2]
+    has = nm > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.where(has, alt / (2.0 * np.maximum(nm, 1)), 0.0)
+    flip = has & (p > 0.5)
+    pmin = np.where(flip, 1.0 - p, p)
+    maf32 = pmin.astype(np.float32)
+    varsum = float(np.sum(np.where(has, 2.0 * pmin * (1.0 - pmin), 0.0)))
+    if not (math.isfinite(varsum) and varsum > 0.0):
+        raise RuntimeError("invalid scaling denominator in packed subset RSVD")
+    kp = min(max(min(k, n) + 10, 20), max(m, 1), max(n, 1))
+    k_eff = min(k, n, kp)
+    op = _RsvdOperator(panel, None, _rsvd_row_design(maf32, flip))
+    ev, vec, rounds = _rsvd_engine(op, kp, k_eff, varsum, seed, power, tol, "lu")
+    return (ev.astype(np.float32), vec.to(dtype=__import__("torch").float32).cpu().numpy(), maf32, flip.astype(bool), rounds)
+
+
+def admx_rsvd_stream_sample(genotype_path, k, seed=42, power=5, tol=1e-1, snps_only=True, maf=0.02, missing_rate=0.05,
+                            delimiter=None, mmap_window_mb=0, memory_mb=0):
+    """src/stats/adamixture.rs:2563-2700 with the packed path `rsvd_stream_sample_packed_impl` (:3527-3720): randomized SVD of the
+    centred additive design of a PLINK prefix after QC (`maf` on the minor allele, `missing_rate`, `snps_only`) ->
+    (eigvals f32 (k_eff), eigvecs f32 (n, k_eff), total_variance = trace(K) of the method-1 GRM over the kept SNPs).
+    kp = max(k_eff + 6, 12) capped by min(m, n) (`admx_rsvd_kp`, :621-640); a thin SVD of Y in every round.  Only a PLINK
+    prefix is accepted.  `delimiter`, `mmap_window_mb` and `memory_mb` are accepted and unused."""
+    return _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate)[:3]
+
+
+def _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate, payload=None):
+    """`payload`: (packed (m, bps) numpy or torch CUDA uint8, n_samples, bim) already read (the CLI's staged payload)."""
+    import math
+    import torch
+    from . import stats as st
+    from .bed import read_bed_payload, snps_only_mask
+    k, power = int(k), int(power)
+    if k <= 0:
+        raise RuntimeError("k must be > 0")
+    if not (0.0 <= float(np.float32(maf)) <= 0.5):
+        raise RuntimeError("maf must be within [0, 0.5]")
+    if not (0.0 <= float(np.float32(missing_rate)) <= 1.0):
+        raise RuntimeError("missing_rate must be within [0, 1]")
+    tol = float(np.float32(tol))
+    if not (math.isfinite(tol) and tol > 0.0):
+        raise RuntimeError("tol must be positive and finite")
+    if payload is None:
+        path = str(genotype_path)
+        low = path.lower()
+        if low.endswith((".vcf", ".vcf.gz", ".hmp", ".hmp.gz", ".txt", ".tsv", ".csv", ".npy")):
+            raise RuntimeError(f"admx_rsvd_stream_sample: only a PLINK prefix is accepted on this build (got {path})")
+        if low.endswith((".bed", ".bim", ".fam")):
+            path = path[:-4]
+        packed, n_fam, bim = read_bed_payload(path)
+    else:
+        packed, n_fam, bim = payload
+    panel = _rsvd_panel(packed, n_fam, None)
+    n = panel.n
+    c = panel.counts()
+    keep, _miss, af, _std = st.packed_prep_row_stats(c, n, float(maf), float(missing_rate), 0.0)
+    if snps_only:
+        keep &= snps_only_mask(bim)
+    rows = np.nonzero(keep)[0]
+    if rows.size == 0:
+        raise RuntimeError("no SNPs passed filtering in streaming RSVD")
+    flip = af[rows] > np.float32(0.5)
+    freq = np.where(flip, np.float32(1.0) - af[rows], af[rows]).astype(np.float32)
+    f64 = freq.astype(np.float64)
+    varsum = float(np.sum(2.0 * f64 * (1.0 - f64)))
+    if not (math.isfinite(varsum) and varsum > 0.0):
+        raise RuntimeError("invalid scaling denominator in streaming RSVD (varsum <= 0)")
+    # trace(K) = sum over kept rows and called genotypes of z^2, from the genotype counts (f64)
+    cr = c[rows].astype(np.float64)
+    n0 = (n - cr[:, 0]) - cr[:, 1] - cr[:, 2]
+    mean = (np.float32(2.0) * freq).astype(np.float64)
+    g0, g1, g2 = np.where(flip, 2.0, 0.0) - mean, 1.0 - mean, np.where(flip, 0.0, 2.0) - mean
+    total_variance = float(np.sum(n0 * g0 * g0 + cr[:, 1] * g1 * g1 + cr[:, 2] * g2 * g2)) / varsum
+    if not (math.isfinite(total_variance) and total_variance > 0.0):
+        raise RuntimeError("invalid total variance in streaming RSVD (trace(K) <= 0)")
+    m = int(rows.size)
+    kp = min(max(min(k, n) + 6, 12), max(min(m, n), 1))
+    k_eff = min(k, n, kp)
+    op = _RsvdOperator(panel, rows.astype(np.int32), _rsvd_row_design(freq, flip))
+    ev, vec, rounds = _rsvd_engine(op, kp, k_eff, varsum, seed, power, tol, "svd")
+    return ev.astype(np.float32), vec.to(torch.float32).cpu().numpy(), float(total_variance), rounds
