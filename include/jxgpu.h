@@ -476,6 +476,25 @@ int jxg_packed_mm_cols(const uint8_t *d_p32, int64_t m_total, int n, const int32
                        const double *d_q, int kp, double *d_w, void *stream);
 int jxg_packed_tmm_cols(const uint8_t *d_t32, int n, int nrows, const double *d_ab, const double *d_w, int kp, double *d_y,
                         void *stream);
+/* ADMIXTURE / FastPop training passes (`jx adamixture`; src/stats/adamixture.rs:2957-3005, 5434-5898) over the rows d_rows
+ * (nrows; NULL = rows 0..nrows-1) of a P32 image, genotypes = minor-allele counts after the row flip d_flip (nrows bytes, NULL =
+ * no flip), missing calls contribute nothing.  P (nrows, k) and Q (n, k) are f32 row-major, 1 <= k <= 64 and k <= n.
+ *   jxg_admx_work_bytes: bytes of the work buffer of the three calls below (partial sums of the EM pass, bounded by a fixed cap);
+ *   jxg_admx_called    : d_qb (n) = 2 x the called count of each sample over the rows (a constant of the panel);
+ *   jxg_admx_em_step   : one EM pass (a, b, t from the same P, Q; fixed-order merges, run-to-run identical bits) and its
+ *                        finalise.  d_mp == NULL: the plain EM step, P_em (clip) -> d_p_em, Q_em (clip, normalised) -> d_q_em,
+ *                        P and Q unchanged.  Otherwise one Adam step in place on P, Q and the moments (lr, beta1, beta2, eps, the
+ *                        bias-correction scales m_scale, v_scale), clip, Q rows normalised;
+ *   jxg_admx_loglik    : d_out[0] = sum g ln rec + (2 - g) ln(1 - rec) (f64; per-workgroup partials added in a fixed order). */
+int64_t jxg_admx_work_bytes(int nrows, int n, int k);
+int jxg_admx_called(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, void *d_work, int64_t work_bytes,
+                    float *d_qb, void *stream);
+int jxg_admx_em_step(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip, int k,
+                     float *d_p, float *d_q, const float *d_qb, void *d_work, int64_t work_bytes, float *d_p_em, float *d_q_em,
+                     float *d_mp, float *d_vp, float *d_mq, float *d_vq, float lr, float beta1, float beta2, float eps,
+                     float m_scale, float v_scale, void *stream);
+int jxg_admx_loglik(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip, int k,
+                    const float *d_p, const float *d_q, void *d_work, int64_t work_bytes, double *d_out, void *stream);
 
 /* SparseLMM exact scan on rotated rows (`exact_scan_blocks_core`, src/stats/splmm.rs:2567-2880, with V = K + lambda I
  * handled spectrally): per row g~ = U'g the sums g~'Wg~, g~'(W X~), g~.(Py)~ of E2, then the score-form Wald test of

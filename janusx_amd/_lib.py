@@ -100,6 +100,11 @@ SIGNATURES = {
     "jxg_packed_dot_t32": [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     "jxg_packed_mm_cols": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p],
     "jxg_packed_tmm_cols": [c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p],
+    "jxg_admx_work_bytes": [c_i, c_i, c_i],
+    "jxg_admx_called": [c_p, c_l, c_i, c_p, c_i, c_p, c_l, c_p, c_p],
+    "jxg_admx_em_step": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p,
+                         c_f, c_f, c_f, c_f, c_f, c_f, c_p],
+    "jxg_admx_loglik": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_l, c_p, c_p],
     "jxg_packed_dot": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "jxg_cross_dot": [c_p, c_i, c_l, c_p, c_i, c_p, c_i, c_p, c_d, c_p, c_p],
     "jxg_splmm_exact_scan_dev": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_p],
@@ -164,7 +169,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,
-             "jxg_spgrm_work_bytes": C.c_int64, "jxg_tri_tiles_doubles": C.c_int64, "jx_assoc_tsv_write": C.c_int64,
+             "jxg_spgrm_work_bytes": C.c_int64, "jxg_admx_work_bytes": C.c_int64, "jxg_tri_tiles_doubles": C.c_int64, "jx_assoc_tsv_write": C.c_int64,
              "jx_assoc_tsv_append": C.c_int64, "jx_pcg_dist_count": C.c_int64, "jxg_scratch_trim": C.c_int64,
              "jxg_lmm_series_doubles": C.c_int64, "jxg_sps_work_doubles": C.c_int64}
 

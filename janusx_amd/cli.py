@@ -7,6 +7,8 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
                             [-maf 0.02] [-geno 0.05] [-het 1.0] [-o OUT] [-force-model]
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
+  python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
+                                 [-solver adam-em|adam|auto] [-max-iter 500] [-check 5] [-tol 1e-5] [-snps-only]  (fastpop: same)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
@@ -926,6 +928,175 @@ def cmd_pca(args):
     return 0
 
 
+ADMX_DEFAULTS = dict(power=5, max_als=1000, reg_als=1e-5, lr=0.005, beta1=0.80, beta2=0.88, epsilon=1e-8, lr_decay=0.5,
+                     min_lr=1e-6)     # python/janusx/script/adamixture.py (the CLI's fixed optimiser settings)
+
+
+def _k_range(tok, lo_s, hi_s, step_s):
+    lo, hi = int(lo_s), int(hi_s)
+    step = abs(int(step_s)) if step_s is not None else 1
+    if step == 0:
+        raise ValueError(f"K range step must be non-zero: {tok!r}")
+    if hi < lo:
+        step = -step
+    return list(range(lo, hi + (1 if step > 0 else -1), step))
+
+
+def parse_k_spec(spec):
+    """The -k grammar of `jx adamixture` (`_parse_k_spec`, python/janusx/script/adamixture.py:1027-1093): a value (8), an
+    inclusive range (1..10 or 1:10), a stepped range (1..10..3, 1:10:3, 1..10:3), a comma list, or a mix of these; duplicates
+    dropped in first-seen order, every K >= 1.  Raises ValueError."""
+    text = str(spec if spec is not None else "").strip()
+    if not text:
+        raise ValueError("Empty -k/--k specification.")
+    if ";" in text:
+        raise ValueError("Semicolon-separated K list is not supported for shell compatibility. Use comma-separated form, "
+                         "e.g. -k 1,5,8.")
+    toks = [t.strip() for t in text.split(",") if t.strip()]
+    if not toks:
+        raise ValueError(f"Invalid -k/--k specification: {spec!r}")
+    vals = []
+    for tok in toks:
+        if ".." in tok or ":" in tok:
+            if ".." in tok:
+                parts = [x.strip() for x in tok.replace("..", ":").split(":") if x.strip()]
+            else:
+                parts = tok.split(":")
+            if len(parts) not in (2, 3):
+                raise ValueError(f"Invalid K range token: {tok!r}")
+            vals += _k_range(tok, parts[0], parts[1], parts[2] if len(parts) == 3 else None)
+        else:
+            vals.append(int(tok))
+    if not vals:
+        raise ValueError(f"Invalid -k/--k specification: {spec!r}")
+    out = []
+    for v in vals:
+        if v < 1:
+            raise ValueError(f"K must be >= 1, got {v}.")
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def _admx_check_args(args):
+    """Input and range checks of `jx adamixture` / `jx fastpop` -> the K list (SystemExit with a message on a refusal)."""
+    cmd = args.cmd
+    for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"{cmd}: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    if not args.bfile:
+        raise SystemExit(f"{cmd} needs -bfile PREFIX")
+    if args.cv is not None and int(args.cv) >= 2:
+        raise SystemExit(f"{cmd}: -cv {args.cv} (cross-validation error) is not built; use -cv 0 or leave it out")
+    if args.cv is not None and int(args.cv) < 0:
+        raise SystemExit("-cv must be >= 0.")
+    if not (0.0 <= float(args.maf) <= 0.5):
+        raise SystemExit("-maf must be within [0, 0.5].")
+    if not (0.0 <= float(args.geno) <= 1.0):
+        raise SystemExit("-geno must be within [0, 1.0].")
+    if not float(args.tol) > 0:
+        raise SystemExit("-tol/--tol must be > 0.")
+    if int(args.max_iter) <= 0:
+        raise SystemExit("-max-iter/--max-iter must be a positive integer.")
+    if int(args.check) <= 0:
+        raise SystemExit("-check/--check must be a positive integer.")
+    if args.thread is not None and int(args.thread) <= 0:
+        raise SystemExit("-t/--thread must be a positive integer.")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"{cmd} runs on one GPU: start it without the launcher")
+    try:
+        ks = parse_k_spec(args.k)
+    except ValueError as e:
+        raise SystemExit(f"{cmd}: {e}") from None
+    bad = [k for k in ks if k > 64]
+    if bad:
+        raise SystemExit(f"{cmd}: K={bad[0]} is out of range: this build supports 1 <= K <= 64")
+    return ks
+
+
+def cmd_adamixture(args):
+    """`jx adamixture` / `jx fastpop` (python/janusx/script/adamixture.py; fastpop.py is the same command): ancestry estimation
+    by ALS + Adam-EM on the kept rows of a PLINK prefix (`AdmxBedTrainingSession.fit_k`), every K of the -k spec on one staged
+    session.  Per K: {prefix}.{K}.Q.txt, .P.npy, .P.site, .fastpop.log; then {prefix}.fastpop.summary.log."""
+    ks = _admx_check_args(args)
+    from . import janusx as jxrs
+    from .bed import read_fam_ids, stage_bed_payload
+    prefix_in = args.bfile[:-4] if args.bfile.lower().endswith((".bed", ".bim", ".fam")) else args.bfile
+    outdir = args.out or "."
+    os.makedirs(outdir, exist_ok=True)
+    prefix = args.prefix or os.path.basename(prefix_in)
+    ids = read_fam_ids(prefix_in)
+    t0 = time.perf_counter()
+    payload = stage_bed_payload(prefix_in, None)
+    sess = jxrs.AdmxBedTrainingSession(prefix_in, bool(args.snps_only), float(args.maf), float(args.geno), 0, payload=payload)
+    del payload
+    t_stage = time.perf_counter() - t0
+    summary = []
+    for idx, k in enumerate(ks, 1):
+        t1 = time.perf_counter()
+        p, q, ll, it, init_ll, als_it = sess.fit_k(k, int(args.seed), args.solver, ADMX_DEFAULTS["power"], float(args.tol),
+                                                   ADMX_DEFAULTS["max_als"], ADMX_DEFAULTS["reg_als"], ADMX_DEFAULTS["lr"],
+                                                   ADMX_DEFAULTS["beta1"], ADMX_DEFAULTS["beta2"], ADMX_DEFAULTS["epsilon"],
+                                                   int(args.max_iter), int(args.check), ADMX_DEFAULTS["lr_decay"],
+                                                   ADMX_DEFAULTS["min_lr"])
+        dt = time.perf_counter() - t1
+        base = os.path.join(outdir, f"{prefix}.{k}")
+        with open(f"{base}.Q.txt", "w") as fh:
+            for sid, row in zip(ids, q.astype(np.float64)):
+                fh.write(sid + "\t" + "\t".join(f"{float(v):.8f}" for v in row) + "\n")
+        np.save(f"{base}.P.npy", np.ascontiguousarray(p, dtype=np.float32))
+        sess.write_site_file(f"{base}.P.site")
+        with open(f"{base}.fastpop.log", "w") as fh:
+            fh.write(f"command: {args.cmd}\n")
+            fh.write(f"genotype: {prefix_in}\n")
+            fh.write(f"K scan progress: {idx}/{len(ks)} (K={k}, spec={args.k})\n")
+            fh.write(f"samples: {sess.n_samples}\nkept SNPs: {sess.n_snps} (maf >= {args.maf}, missing rate <= {args.geno}, "
+                     f"snps-only {'on' if args.snps_only else 'off'})\n")
+            fh.write(f"solver: {args.solver}  seed: {args.seed}  tol: {args.tol}  max-iter: {args.max_iter}  check: {args.check}\n")
+            fh.write(f"ALS rounds: {als_it}  init log-likelihood: {init_ll:.6f}\n")
+            fh.write(f"Adam-EM iterations: {it}  final log-likelihood: {ll:.6f}\n")
+            fh.write(f"time: {dt:.3f} s (staging {t_stage:.3f} s, shared by the K scan)\n")
+            fh.write("structure plot: not drawn (plots are not built)\n")
+            fh.write(f"outputs: {base}.Q.txt {base}.P.npy {base}.P.site\n")
+        summary.append((k, ll, init_ll, it, als_it, dt))
+        print(f"{args.cmd}: K={k} ll={ll:.3f} iterations={it} ALS={als_it} ({dt:.2f}s) -> {base}.Q.txt")
+    with open(os.path.join(outdir, f"{prefix}.fastpop.summary.log"), "w") as fh:
+        fh.write(f"genotype: {prefix_in}\nsamples: {sess.n_samples}\nkept SNPs: {sess.n_snps}\nK spec: {args.k}\n")
+        fh.write("K\tll_final\tinit_ll\tadam_iter\tals_iter\tseconds\n")
+        for k, ll, init_ll, it, als_it, dt in summary:
+            fh.write(f"{k}\t{ll:.6f}\t{init_ll:.6f}\t{it}\t{als_it}\t{dt:.3f}\n")
+        fh.write(f"total seconds: {time.perf_counter() - t0:.3f}\n")
+    return 0
+
+
+def _add_admixture_parser(sub, name):
+    a = sub.add_parser(name)
+    a.add_argument("-bfile", "--bfile", default=None)
+    a.add_argument("-vcf", "--vcf", default=None, help=argparse.SUPPRESS)
+    a.add_argument("-hmp", "--hmp", default=None, help=argparse.SUPPRESS)
+    a.add_argument("-file", "--file", default=None, help=argparse.SUPPRESS)
+    a.add_argument("-k", "--k", type=str, required=True,
+                   help="K spec: single (8), range (1..10 or 1:10), stepped range (1..10..3, 1:10:3, or 1..10:3), or list (1,5,8)")
+    a.add_argument("-o", "--out", default=None, help="output directory (default: current directory)")
+    a.add_argument("-prefix", "--prefix", default=None, help="output file prefix (default: the genotype basename)")
+    a.add_argument("-maf", "--maf", type=float, default=0.02)
+    a.add_argument("-geno", "--geno", type=float, default=0.05)
+    a.add_argument("-snps-only", "--snps-only", dest="snps_only", action="store_true", default=False,
+                   help="drop sites whose alleles are not single A/C/G/T")
+    a.add_argument("-seed", "--seed", type=int, default=42)
+    a.add_argument("-solver", "--solver", type=str, default="adam-em", choices=["auto", "adam", "adam-em"])
+    a.add_argument("-max-iter", "--max-iter", dest="max_iter", type=int, default=500)
+    a.add_argument("-check", "--check", type=int, default=5)
+    a.add_argument("-tol", "--tol", type=float, default=1e-5)
+    a.add_argument("-cv", "--cv", type=int, default=None, help="cross-validation folds: not built (0 accepted)")
+    a.add_argument("--no-plot", dest="no_plot", action="store_true", default=False, help="accepted; plots are never drawn")
+    a.add_argument("-tag", "--tag", default=None, help="accepted and unused (plots are not built)")
+    a.add_argument("-t", "--thread", "-threads", "--threads", dest="thread", type=int, default=None,
+                   help="accepted for compatibility; unused")
+    a.add_argument("-mem", "--memory", dest="memory", type=float, default=None, help="accepted for compatibility; unused")
+    a.set_defaults(func=cmd_adamixture)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="jx", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -1043,6 +1214,8 @@ def main(argv=None):
     c.add_argument("-v", "--verbose", action="store_true", default=False, help="accepted for compatibility")
     c.add_argument("-t", "--thread", type=int, default=0, help="accepted for compatibility; unused")
     c.set_defaults(func=cmd_pca)
+    _add_admixture_parser(sub, "adamixture")
+    _add_admixture_parser(sub, "fastpop")
     args = ap.parse_args(argv)
     return args.func(args)
 

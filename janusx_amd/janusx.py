@@ -4509,12 +4509,43 @@ def admx_rsvd_stream_sample(genotype_path, k, seed=42, power=5, tol=1e-1, snps_o
     return _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate)[:3]
 
 
+def _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload, who, what, before_panel=None):
+    """The kept rows of the ADMIXTURE / FastPop paths (QC on the minor allele, `missing_rate`, `snps_only`) ->
+    (Panel, counts, rows int64, row_flip bool, row_freq f32 minor-allele frequency, Bim, PLINK prefix or None).
+    `before_panel(packed, n)`, when given, is called before the P32 image is built (a memory check)."""
+    from . import stats as st
+    from .bed import read_bed_payload, snps_only_mask
+    path = None
+    if payload is None:
+        path = str(genotype_path)
+        low = path.lower()
+        if low.endswith((".vcf", ".vcf.gz", ".hmp", ".hmp.gz", ".txt", ".tsv", ".csv", ".npy")):
+            raise RuntimeError(f"{who}: only a PLINK prefix is accepted on this build (got {path})")
+        if low.endswith((".bed", ".bim", ".fam")):
+            path = path[:-4]
+        packed, n_fam, bim = read_bed_payload(path)
+    else:
+        packed, n_fam, bim = payload
+    if before_panel is not None:
+        before_panel(packed, n_fam)
+    panel = _rsvd_panel(packed, n_fam, None)
+    n = panel.n
+    c = panel.counts()
+    keep, _miss, af, _std = st.packed_prep_row_stats(c, n, float(maf), float(missing_rate), 0.0)
+    if snps_only:
+        keep &= snps_only_mask(bim)
+    rows = np.nonzero(keep)[0]
+    if rows.size == 0:
+        raise RuntimeError(f"no SNPs passed filtering in {what}")
+    flip = af[rows] > np.float32(0.5)
+    freq = np.where(flip, np.float32(1.0) - af[rows], af[rows]).astype(np.float32)
+    return panel, c, rows, flip, freq, bim, path
+
+
 def _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate, payload=None):
     """`payload`: (packed (m, bps) numpy or torch CUDA uint8, n_samples, bim) already read (the CLI's staged payload)."""
     import math
     import torch
-    from . import stats as st
-    from .bed import read_bed_payload, snps_only_mask
     k, power = int(k), int(power)
     if k <= 0:
         raise RuntimeError("k must be > 0")
@@ -4525,27 +4556,9 @@ def _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate,
     tol = float(np.float32(tol))
     if not (math.isfinite(tol) and tol > 0.0):
         raise RuntimeError("tol must be positive and finite")
-    if payload is None:
-        path = str(genotype_path)
-        low = path.lower()
-        if low.endswith((".vcf", ".vcf.gz", ".hmp", ".hmp.gz", ".txt", ".tsv", ".csv", ".npy")):
-            raise RuntimeError(f"admx_rsvd_stream_sample: only a PLINK prefix is accepted on this build (got {path})")
-        if low.endswith((".bed", ".bim", ".fam")):
-            path = path[:-4]
-        packed, n_fam, bim = read_bed_payload(path)
-    else:
-        packed, n_fam, bim = payload
-    panel = _rsvd_panel(packed, n_fam, None)
+    panel, c, rows, flip, freq, _bim, _prefix = _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload,
+                                                                "admx_rsvd_stream_sample", "streaming RSVD")
     n = panel.n
-    c = panel.counts()
-    keep, _miss, af, _std = st.packed_prep_row_stats(c, n, float(maf), float(missing_rate), 0.0)
-    if snps_only:
-        keep &= snps_only_mask(bim)
-    rows = np.nonzero(keep)[0]
-    if rows.size == 0:
-        raise RuntimeError("no SNPs passed filtering in streaming RSVD")
-    flip = af[rows] > np.float32(0.5)
-    freq = np.where(flip, np.float32(1.0) - af[rows], af[rows]).astype(np.float32)
     f64 = freq.astype(np.float64)
     varsum = float(np.sum(2.0 * f64 * (1.0 - f64)))
     if not (math.isfinite(varsum) and varsum > 0.0):
@@ -4564,3 +4577,505 @@ def _admx_rsvd(genotype_path, k, seed, power, tol, snps_only, maf, missing_rate,
     op = _RsvdOperator(panel, rows.astype(np.int32), _rsvd_row_design(freq, flip))
     ev, vec, rounds = _rsvd_engine(op, kp, k_eff, varsum, seed, power, tol, "svd")
     return ev.astype(np.float32), vec.to(torch.float32).cpu().numpy(), float(total_variance), rounds
+
+
+# ---- ADMIXTURE / FastPop (`jx adamixture`): ALS start and Adam-EM on the packed genotypes -------------------------------------
+
+ADMX_MAX_K = 64
+_ADMX_EPS = 1e-5                       # clip32 (src/stats/adamixture.rs:50-60)
+
+
+def _admx_clip(x):
+    return x.clamp(_ADMX_EPS, 1.0 - _ADMX_EPS)
+
+
+def _admx_map_q(q):
+    """`map_q_rows_inplace_f32` (src/stats/adamixture.rs:4120-4137) on a torch tensor: clip, then rows / row sum; a non-finite
+    or non-positive sum gives 1/K."""
+    import torch
+    q = _admx_clip(q)
+    s = q.sum(dim=1, keepdim=True)
+    bad = ~(torch.isfinite(s) & (s > 0))
+    return torch.where(bad, torch.full_like(q, 1.0 / max(int(q.shape[1]), 1)), q / torch.where(bad, torch.ones_like(s), s))
+
+
+def _stdrng_words(seed, count):
+    """The first `count` u32 words of `_StdRngU32(seed)`, all ChaCha12 blocks at once (numpy, wrapping u32 arithmetic)."""
+    key = _StdRngU32(seed).key
+    nb = (int(count) + 15) // 16
+    ctr = np.arange(nb, dtype=np.uint64)
+    st = [np.full(nb, v, dtype=np.uint32) for v in (0x61707865, 0x3320646e, 0x79622d32, 0x6b206574)]
+    st += [np.full(nb, v, dtype=np.uint32) for v in key]
+    st += [(ctr & np.uint64(0xffffffff)).astype(np.uint32), (ctr >> np.uint64(32)).astype(np.uint32),
+           np.zeros(nb, dtype=np.uint32), np.zeros(nb, dtype=np.uint32)]
+    x = [a.copy() for a in st]
+
+    def rotl(v, c):
+        return (v << np.uint32(c)) | (v >> np.uint32(32 - c))
+
+    def qr(a, b, c, d):
+        x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16)
+        x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12)
+        x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8)
+        x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7)
+    with np.errstate(over="ignore"):
+        for _ in range(6):
+            qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15)
+            qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
+        out = np.stack([x[i] + st[i] for i in range(16)], axis=1).reshape(-1)
+    return out[: int(count)]
+
+
+def adam_seed_init(m, n, k, seed):
+    """`adam_seed_init_rust` (src/stats/adamixture.rs:4274-4286): StdRng `random::<f32>()` ((u32 >> 8) 2^-24), P (m, k) first,
+    then Q (n, k), clipped; Q rows mapped by `map_q` -> (P, Q) f32 numpy."""
+    import torch
+    total = (int(m) + int(n)) * int(k)
+    u = _stdrng_words(seed, total)
+    v = ((u >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float32)
+    v = np.clip(v, np.float32(_ADMX_EPS), np.float32(1.0 - _ADMX_EPS)).astype(np.float32)
+    p = v[: int(m) * int(k)].reshape(int(m), int(k)).copy()
+    q = _admx_map_q(torch.from_numpy(v[int(m) * int(k):].reshape(int(n), int(k)).copy())).numpy()
+    return p, q
+
+
+def _admx_pinv(mat):
+    """`symmetric_pinv_f32` (src/stats/adamixture.rs:3985-4014): eigendecomposition in f64, eigenvalues with |l| <= max(1e-12
+    max|l|, 1e-12) dropped, result in the dtype of `mat`."""
+    import torch
+    m64 = mat.to(torch.float64)
+    ev, vec = torch.linalg.eigh(0.5 * (m64 + m64.T))
+    cutoff = max(float(ev.abs().max()) * 1e-12, 1e-12) if ev.numel() else 1e-12
+    keep = torch.isfinite(ev) & (ev.abs() > cutoff)
+    inv_ev = torch.where(keep, 1.0 / torch.where(keep, ev, torch.ones_like(ev)), torch.zeros_like(ev))
+    return ((vec * inv_ev[None, :]) @ vec.T).to(mat.dtype)
+
+
+def _admx_right_pinv(x, reg):
+    """`right_multiply_pinv_f32` (:4104-4111): X (X'X + reg I)^+."""
+    import torch
+    k = int(x.shape[1])
+    gram = x.T @ x + float(reg) * torch.eye(k, dtype=x.dtype, device=x.device)
+    return x @ _admx_pinv(gram)
+
+
+def _admx_q_from_p(z, v, row_freq, i_mat):
+    """`compute_q_from_p_projection_f32` (:4232-4251)."""
+    q = v @ (z.T @ i_mat)
+    fsum = (i_mat * row_freq[:, None]).sum(dim=0)
+    return _admx_map_q(0.5 * q + fsum[None, :])
+
+
+def _admx_p_from_q(z, v, row_freq, i_mat):
+    """`compute_p_from_q_projection_f32` (:4253-4272)."""
+    p = z @ (v.T @ i_mat)
+    isum = i_mat.sum(dim=0)
+    return _admx_clip(0.5 * p + row_freq[:, None] * isum[None, :])
+
+
+def _admx_rmse(a, b):
+    d = (a - b).to(__import__("torch").float64)
+    return float((d * d).mean()) ** 0.5 if d.numel() else 0.0
+
+
+def admx_als_init(z, v, row_freq, p0, max_iter=1000, tol=1e-5, reg=1e-5, loglik=None):
+    """`als_init_packed_session_impl` (src/stats/adamixture.rs:4288-4389) on torch tensors of any device and dtype: z = Z v
+    (m, k), v (n, k), row_freq (m), the seed P0 (m, k).  Q and P are projected in turn; the loop stops on RMSE(Q, Q_prev) < tol
+    and, once max |corr| of P's columns has exceeded 0.95, after 20 rounds without a new best RMSE, rolling back to the best
+    state.  -> (P, Q, init_ll = loglik(P, Q) or NaN, rounds)."""
+    import torch
+    dt = z.dtype
+    row_freq = row_freq.to(dt)
+    p = p0.to(dt)
+    k = int(p.shape[1])
+    q = _admx_q_from_p(z, v, row_freq, _admx_right_pinv(p, reg))
+    q_prev = q.clone()
+    rmse_best = float("inf")
+    stall = 0
+    high_corr = False
+    p_best = q_best = None
+    last = 0
+    eye = torch.eye(k, dtype=dt, device=p.device)
+    for it in range(int(max_iter)):
+        last = it + 1
+        p = _admx_p_from_q(z, v, row_freq, _admx_right_pinv(q, reg))
+        p = _admx_clip(p)
+        g_p = p.T @ p
+        q = _admx_q_from_p(z, v, row_freq, p @ _admx_pinv(g_p + float(reg) * eye))
+        err = _admx_rmse(q, q_prev)
+        if not high_corr and k > 1:
+            sd = torch.sqrt(torch.clamp(torch.diagonal(g_p), min=1e-12))
+            corr = (g_p / torch.clamp(sd[:, None] * sd[None, :], min=1e-10)).abs()
+            corr.fill_diagonal_(0.0)
+            if float(corr.max()) > 0.95:
+                high_corr = True
+        if high_corr:
+            if err < rmse_best:
+                rmse_best, p_best, q_best, stall = err, p.clone(), q.clone(), 0
+            else:
+                stall += 1
+            if stall >= 20:
+                if p_best is not None:
+                    p, q = p_best, q_best
+                break
+        if err < tol:
+            break
+        q_prev = q.clone()
+    init_ll = float(loglik(p, q)) if loglik is not None else float("nan")
+    return p, q, init_ll, last
+
+
+class _AdmxEngine:
+    """The device side of one panel: P32 image, kept rows and flips, the per-sample called counts (2 x, computed once), the
+    work buffer of the EM pass (per K) and the three calls `jxg_admx_called` / `jxg_admx_em_step` / `jxg_admx_loglik`."""
+
+    def __init__(self, panel, rows, flip):
+        import torch
+        from . import pipeline as pl
+        self.panel, self.dev = panel, panel.device
+        self.m = int(len(flip))
+        self.n = panel.n
+        self.rows_t = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(self.dev)
+        self.flip_t = torch.from_numpy(np.ascontiguousarray(flip, dtype=np.uint8)).to(self.dev)
+        self.work, self.work_k = None, None
+        self._ensure_work(1)
+        self.qb = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+        check(lib().jxg_admx_called(panel.p32.data_ptr(), panel.m, self.n, pl._ptr(self.rows_t), self.m, self.work.data_ptr(),
+                                    int(self.work.numel()), self.qb.data_ptr(), pl._stream()))
+
+    def _ensure_work(self, k):
+        import torch
+        k = int(k)
+        if not 1 <= k <= ADMX_MAX_K:
+            raise RuntimeError(f"K must be within [1, {ADMX_MAX_K}] on this build (got K={k})")
+        if k > self.n:
+            raise RuntimeError(f"K={k} exceeds the number of samples ({self.n})")
+        if self.work_k == k:
+            return
+        nb = int(lib().jxg_admx_work_bytes(self.m, self.n, k))
+        self.work = None
+        _admx_need_hbm(nb + 16 * (self.m + self.n) * k, f"the EM partial sums of K={k}")
+        self.work = torch.empty(max(nb, 4 * self.n), dtype=torch.uint8, device=self.dev)
+        self.work_k = k
+
+    def _pq(self, p, q):
+        k = int(p.shape[1])
+        if tuple(p.shape) != (self.m, k) or tuple(q.shape) != (self.n, k):
+            raise RuntimeError(f"shape mismatch: expected P ({self.m}, K) and Q ({self.n}, K), got P {tuple(p.shape)}, "
+                               f"Q {tuple(q.shape)}")
+        self._ensure_work(k)
+        return k
+
+    def em_step(self, p, q):
+        """Plain EM step -> (P_em, Q_em); P and Q unchanged."""
+        import torch
+        from . import pipeline as pl
+        k = self._pq(p, q)
+        p_em, q_em = torch.empty_like(p), torch.empty_like(q)
+        check(lib().jxg_admx_em_step(self.panel.p32.data_ptr(), self.panel.m, self.n, pl._ptr(self.rows_t), self.m,
+                                     self.flip_t.data_ptr(), k, p.data_ptr(), q.data_ptr(), self.qb.data_ptr(),
+                                     self.work.data_ptr(), int(self.work.numel()), p_em.data_ptr(), q_em.data_ptr(),
+                                     None, None, None, None, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, pl._stream()))
+        return p_em, q_em
+
+    def adam_step(self, p, q, mom, lr, beta1, beta2, eps, m_scale, v_scale):
+        """One Adam-EM iteration in place on P, Q and the moments mom = (m_P, v_P, m_Q, v_Q)."""
+        from . import pipeline as pl
+        k = self._pq(p, q)
+        mp, vp, mq, vq = mom
+        check(lib().jxg_admx_em_step(self.panel.p32.data_ptr(), self.panel.m, self.n, pl._ptr(self.rows_t), self.m,
+                                     self.flip_t.data_ptr(), k, p.data_ptr(), q.data_ptr(), self.qb.data_ptr(),
+                                     self.work.data_ptr(), int(self.work.numel()), None, None, mp.data_ptr(), vp.data_ptr(),
+                                     mq.data_ptr(), vq.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
+                                     float(m_scale), float(v_scale), pl._stream()))
+
+    def loglik(self, p, q):
+        import torch
+        from . import pipeline as pl
+        k = self._pq(p, q)
+        out = torch.empty(1, dtype=torch.float64, device=self.dev)
+        check(lib().jxg_admx_loglik(self.panel.p32.data_ptr(), self.panel.m, self.n, pl._ptr(self.rows_t), self.m,
+                                    self.flip_t.data_ptr(), k, p.data_ptr(), q.data_ptr(), self.work.data_ptr(),
+                                    int(self.work.numel()), out.data_ptr(), pl._stream()))
+        return float(out.item())
+
+
+def _admx_need_hbm(nbytes, what):
+    """Fail with a message, rather than partway through, when the device lacks `nbytes` of free memory."""
+    import torch
+    free, _total = torch.cuda.mem_get_info()
+    if int(nbytes) > int(free):
+        raise RuntimeError(f"not enough free device memory for {what}: need {int(nbytes) / 2**30:.2f} GiB, "
+                           f"{int(free) / 2**30:.2f} GiB free")
+
+
+def _admx_adam_loop(eng, p, q, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay, min_lr, trace=None):
+    """`adam_optimize_packed_inplace_impl` (src/stats/adamixture.rs:5608-5898): Adam on the EM direction with bias correction,
+    the log-likelihood after every `check_every`-th iteration, stop when |ll - ll_best| < 0.1, lr x lr_decay (floor min_lr) on a
+    non-improvement and stop after two in a row; the best state is kept.  The scalars follow the reference's f32 arithmetic.
+    -> (P_best, Q_best, ll_best, last_iter); `trace`, a list, receives (iteration, ll) of every check."""
+    import math
+    import torch
+    f32 = np.float32
+    lr_cur, b1, b2 = f32(lr), f32(beta1), f32(beta2)
+    b1p, b2p = f32(1.0), f32(1.0)
+    mom = tuple(torch.zeros_like(x) for x in (p, p, q, q))
+    p_best = q_best = None
+    ll_best = float("-inf")
+    no_improve = 0
+    last = 0
+    check_every = max(int(check_every), 1)
+    for it in range(int(max_iter)):
+        last = it + 1
+        b1p, b2p = f32(b1p * b1), f32(b2p * b2)
+        ms = f32(1.0) if abs(f32(1.0) - b1p) < f32(1e-8) else f32(f32(1.0) / f32(f32(1.0) - b1p))
+        vs = f32(1.0) if abs(f32(1.0) - b2p) < f32(1e-8) else f32(f32(1.0) / f32(f32(1.0) - b2p))
+        eng.adam_step(p, q, mom, lr_cur, b1, b2, f32(epsilon), ms, vs)
+        if last % check_every != 0:
+            continue
+        ll = eng.loglik(p, q)
+        if trace is not None:
+            trace.append((last, ll))
+        if abs(ll - ll_best) < 0.1:
+            break
+        if ll > ll_best:
+            ll_best, p_best, q_best, no_improve = ll, p.clone(), q.clone(), 0
+        else:
+            no_improve += 1
+            lr_cur = max(f32(lr_cur * f32(lr_decay)), f32(min_lr))
+            if no_improve >= 2:
+                break
+    if not math.isfinite(ll_best):
+        ll_best, p_best, q_best = eng.loglik(p, q), p, q
+    return p_best, q_best, float(ll_best), last
+
+
+def _admx_check_qc(maf, missing_rate):
+    if not (0.0 <= float(np.float32(maf)) <= 0.5):
+        raise RuntimeError("maf must be within [0, 0.5]")
+    if not (0.0 <= float(np.float32(missing_rate)) <= 1.0):
+        raise RuntimeError("missing_rate must be within [0, 1]")
+
+
+def _admx_p32_check(packed, n):
+    m = int(packed.shape[0])
+    _admx_need_hbm(((int(n) + 127) // 128) * 128 // 4 * m + (0 if _is_device_tensor(packed) else int(packed.nbytes)),
+                   f"the genotype image ({m} SNPs x {int(n)} samples)")
+
+
+class AdmxBedTrainingSession:
+    """`AdmxBedTrainingSession` (src/stats/adamixture.rs:1526, 5950-6140): the kept rows of a PLINK prefix (QC on the minor
+    allele, `missing_rate`, `snps_only`) staged once as a P32 image in HBM with their flips and the per-sample called counts;
+    every `fit_k` of a K scan reuses them.  `memory_mb` is accepted and unused."""
+
+    def __init__(self, genotype_path, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0, payload=None):
+        import torch
+        _admx_check_qc(maf, missing_rate)
+        self.snps_only, self.maf, self.missing_rate = bool(snps_only), float(maf), float(missing_rate)
+        panel, _c, rows, flip, freq, bim, prefix = _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload,
+                                                                   "AdmxBedTrainingSession", "BED training session",
+                                                                   before_panel=_admx_p32_check)
+        self.prefix = prefix if prefix is not None else str(genotype_path)
+        self._panel, self._rows, self._flip, self._freq, self._bim = panel, rows, flip, freq, bim
+        self._eng = _AdmxEngine(panel, rows, flip)
+        self._freq_t = torch.from_numpy(freq).to(panel.device)
+        self._op = None
+
+    @property
+    def n_samples(self):
+        return int(self._panel.n)
+
+    @property
+    def n_snps(self):
+        return int(self._rows.size)
+
+    def row_freq(self):
+        return self._freq.copy()
+
+    def row_flip(self):
+        return self._flip.copy()
+
+    def kept_rows(self):
+        return self._rows.copy()
+
+    def write_site_file(self, path):
+        """`write_p_site_from_backend_impl` (src/stats/adamixture.rs:1698-1760): chrom, pos, ref, alt of the kept BIM rows, tab
+        separated, alleles swapped on flipped rows."""
+        b = self._bim
+        with open(path, "w") as fh:
+            for r, f in zip(self._rows.tolist(), self._flip.tolist()):
+                ref, alt = (b.a1[r], b.a0[r]) if f else (b.a0[r], b.a1[r])
+                fh.write(f"{b.chrom[r]}\t{b.pos[r]}\t{ref}\t{alt}\n")
+
+    def __repr__(self):
+        return (f"AdmxBedTrainingSession(prefix='{self.prefix}', n_snps={self.n_snps}, n_samples={self.n_samples}, "
+                f"snps_only={self.snps_only}, maf={self.maf}, missing_rate={self.missing_rate})")
+
+    def _operator(self):
+        if self._op is None:
+            from . import pipeline as pl
+            _admx_need_hbm(int(lib().jxg_t32_bytes(self._panel.n, self.n_snps)), "the sample-major image of the randomized SVD")
+            self._op = _RsvdOperator(self._panel, self._rows.astype(np.int32), _rsvd_row_design(self._freq, self._flip))
+            del pl
+        return self._op
+
+    def zq(self, v):
+        """z = Z v of the centred design over the kept rows (`multiply_a_omega_packed_checked_impl`) -> (m, k) f32 tensor."""
+        import torch
+        return self._operator().zq(v.to(torch.float64)).to(torch.float32)
+
+    def fit_k(self, k, seed, solver, power, tol, max_als, reg_als, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay,
+              min_lr):
+        """`fit_admx_bed_training_session_impl` (src/stats/adamixture.rs:4391-4484) -> (P f32 (m, k), Q f32 (n, k), ll_final,
+        adam iterations, init_ll, ALS rounds)."""
+        p, q, ll, it, init_ll, als_it = self._fit(k, seed, solver, power, tol, max_als, reg_als, lr, beta1, beta2, epsilon,
+                                                  max_iter, check_every, lr_decay, min_lr)
+        return p.cpu().numpy(), q.cpu().numpy(), ll, it, init_ll, als_it
+
+    def _fit(self, k, seed, solver, power, tol, max_als, reg_als, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay,
+             min_lr, trace=None):
+        import math
+        import torch
+        k = int(k)
+        m, n = self.n_snps, self.n_samples
+        if m == 0 or n == 0 or k == 0:
+            raise RuntimeError("invalid empty input for BED training session")
+        if k > ADMX_MAX_K:
+            raise RuntimeError(f"K must be within [1, {ADMX_MAX_K}] on this build (got K={k})")
+        dev = self._panel.device
+        mode = "adam" if str(solver).strip().lower() == "adam" else "adam-em"
+        if mode == "adam":
+            if k > n:
+                raise RuntimeError(f"K={k} exceeds the number of samples ({n})")
+            p0, q0 = adam_seed_init(m, n, k, seed)
+            p, q = torch.from_numpy(p0).to(dev), torch.from_numpy(q0).to(dev)
+            init_ll, als_it = float("nan"), 0
+        else:
+            op = self._operator()
+            f64 = self._freq.astype(np.float64)
+            varsum = float(np.sum(2.0 * f64 * (1.0 - f64)))
+            if not (math.isfinite(varsum) and varsum > 0.0):
+                raise RuntimeError("invalid scaling denominator in streaming RSVD (varsum <= 0)")
+            kp = min(max(min(k, n) + 6, 12), max(min(m, n), 1))
+            k_eff = min(k, n, kp)
+            if k_eff != k:
+                raise RuntimeError(f"K={k} exceeds sample-side RSVD rank {k_eff}; reduce K or use dense fallback")
+            _ev, vec, _rounds = _rsvd_engine(op, kp, k_eff, varsum, seed, int(power), float(np.float32(tol)), "svd")
+            v = vec.to(torch.float32)
+            z = op.zq(v.to(torch.float64)).to(torch.float32)
+            p0 = adam_seed_init(m, 0, k, seed)[0]              # P comes first in the stream: Q's draws are not needed
+            p, q, init_ll, als_it = admx_als_init(z, v, self._freq_t, torch.from_numpy(p0).to(dev), int(max_als),
+                                                  float(np.float32(tol)), float(np.float32(reg_als)),
+                                                  loglik=lambda pp, qq: self._eng.loglik(pp.contiguous(), qq.contiguous()))
+            p, q = p.contiguous(), q.contiguous()
+        p, q, ll, it = _admx_adam_loop(self._eng, p, q, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay, min_lr,
+                                       trace)
+        return p, q, ll, it, init_ll, als_it
+
+
+def admx_bed_training_meta(genotype_path, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0):
+    """-> (row_freq f32 of the kept rows, n_samples) (src/stats/adamixture.rs:6761-6800)."""
+    _admx_check_qc(maf, missing_rate)
+    panel, _c, _rows, _flip, freq, _bim, _p = _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, None,
+                                                              "admx_bed_training_meta", "BED training session")
+    return freq, int(panel.n)
+
+
+def admx_multiply_a_omega_bed(genotype_path, omega, row_freq, snps_only=True, maf=0.02, missing_rate=0.05, delimiter=None,
+                              mmap_window_mb=0, memory_mb=0):
+    """Z omega of the centred design over the kept rows (src/stats/adamixture.rs:6709-6760; `_RsvdOperator.zq`) -> (m, k) f32.
+    `delimiter`, `mmap_window_mb` and `memory_mb` are accepted and unused."""
+    import torch
+    s = AdmxBedTrainingSession(genotype_path, snps_only, maf, missing_rate, memory_mb)
+    om = _c(omega, np.float32)
+    if om.ndim != 2 or om.shape[0] != s.n_samples or om.shape[1] == 0:
+        raise RuntimeError("omega must be a non-empty 2D matrix with shape (n_samples, k)")
+    rf = _c(row_freq, np.float32).ravel()
+    if rf.size != s.n_snps:
+        raise RuntimeError(f"row_freq length mismatch: got {rf.size}, expected {s.n_snps}")
+    return s.zq(torch.from_numpy(om).to(s._panel.device)).cpu().numpy()
+
+
+def _admx_pq_host(eng, p, q):
+    import torch
+    p = _c(p, np.float32)
+    q = _c(q, np.float32)
+    if p.ndim != 2 or q.ndim != 2 or p.shape[0] != eng.m or q.shape[0] != eng.n or p.shape[1] != q.shape[1]:
+        raise RuntimeError(f"shape mismatch: G=({eng.m},{eng.n}), P={tuple(p.shape)}, Q={tuple(q.shape)}")
+    return torch.from_numpy(p).to(eng.dev), torch.from_numpy(q).to(eng.dev)
+
+
+def admx_loglikelihood_bed_f32(genotype_path, p, q, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0):
+    s = AdmxBedTrainingSession(genotype_path, snps_only, maf, missing_rate, memory_mb)
+    pt, qt = _admx_pq_host(s._eng, p, q)
+    return s._eng.loglik(pt, qt)
+
+
+def admx_adam_optimize_bed_f32(genotype_path, p0, q0, lr=0.005, beta1=0.80, beta2=0.88, epsilon=1e-8, max_iter=1500,
+                               check_every=5, lr_decay=0.5, min_lr=1e-6, snps_only=True, maf=0.02, missing_rate=0.05,
+                               memory_mb=0):
+    """-> (P, Q, ll_best, iterations) (src/stats/adamixture.rs:8563-8640)."""
+    s = AdmxBedTrainingSession(genotype_path, snps_only, maf, missing_rate, memory_mb)
+    pt, qt = _admx_pq_host(s._eng, p0, q0)
+    p, q, ll, it = _admx_adam_loop(s._eng, pt, qt, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay, min_lr)
+    return p.cpu().numpy(), q.cpu().numpy(), ll, it
+
+
+def _admx_dense_engine(g):
+    """Engine of a dense (m, n) u8 genotype matrix (0 / 1 / 2 = minor-allele count, 3 = missing, no flip), packed to 2 bits."""
+    import torch
+    from .bed import pack_dosage
+    g = np.asarray(g)
+    if g.ndim != 2 or g.dtype != np.uint8:
+        raise RuntimeError("g must be a 2D uint8 matrix (m, n) with 0/1/2 and 3 = missing")
+    m, n = g.shape
+    if m == 0 or n == 0:
+        raise RuntimeError("invalid empty genotype matrix")
+    dose = np.where(g > 2, -1, g.astype(np.int8)).astype(np.int8)
+    packed = torch.from_numpy(pack_dosage(dose)).to(torch.device("cuda", torch.cuda.current_device()))
+    from . import pipeline as pl
+    return _AdmxEngine(pl.Panel(packed, n), None, np.zeros(m, dtype=bool))
+
+
+def admx_loglikelihood_f32(g, p, q):
+    eng = _admx_dense_engine(g)
+    pt, qt = _admx_pq_host(eng, p, q)
+    return eng.loglik(pt, qt)
+
+
+def admx_em_step_inplace_f32(g, p, q, p_em, q_em, tile_cols=None):
+    """One EM step of a dense u8 matrix into the caller's p_em (m, k) / q_em (n, k) f32 arrays (`tile_cols` accepted, unused)."""
+    eng = _admx_dense_engine(g)
+    pt, qt = _admx_pq_host(eng, p, q)
+    if p_em.shape != tuple(pt.shape) or q_em.shape != tuple(qt.shape):
+        raise RuntimeError("invalid packed EM output buffer size")
+    pe, qe = eng.em_step(pt, qt)
+    p_em[...] = pe.cpu().numpy()
+    q_em[...] = qe.cpu().numpy()
+
+
+def admx_adam_optimize_f32(g, p0, q0, lr=0.005, beta1=0.80, beta2=0.88, epsilon=1e-8, max_iter=1500, check_every=5,
+                           lr_decay=0.5, min_lr=1e-6, tile_cols=None):
+    eng = _admx_dense_engine(g)
+    pt, qt = _admx_pq_host(eng, p0, q0)
+    p, q, ll, it = _admx_adam_loop(eng, pt, qt, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay, min_lr)
+    return p.cpu().numpy(), q.cpu().numpy(), ll, it
+
+
+def admx_map_q_f32(q):
+    import torch
+    return _admx_map_q(torch.from_numpy(_c(q, np.float32).copy())).numpy()
+
+
+def admx_map_p_f32(p):
+    return np.clip(_c(p, np.float32), np.float32(_ADMX_EPS), np.float32(1.0 - _ADMX_EPS)).astype(np.float32)
+
+
+def admx_rmse_f32(q1, q2):
+    a, b = _c(q1, np.float32), _c(q2, np.float32)
+    if a.shape != b.shape:
+        raise RuntimeError("shape mismatch in admx_rmse_f32")
+    if a.size == 0:
+        return 0.0
+    d = (a - b).astype(np.float64)
+    return float(np.float32(np.float32(np.sum(d * d) / a.size) ** np.float32(0.5)))
