@@ -31,12 +31,6 @@ extern "C" {
 const char *jx_last_error(void);
 int jx_version(void);
 
-/* Progress hook of the host layer's row-block loops (jx_assoc_packed): `fn(done, total, user)` is called every `every` rows
- * (every <= 0: once per internal block of 8192 rows) and at the end; a nonzero return stops the call, which then fails with
- * "interrupted by the progress callback".  NULL clears the hook.  Replaces the `progress_callback` / `progress_every`
- * arguments of the reference's PyO3 entry points (src/stats/lmm.rs:3059-3083, 3214-3330; src/stats/grm.rs:3485-3495). */
-typedef int (*jx_progress_fn)(int64_t done, int64_t total, void *user);
-int jx_set_progress(jx_progress_fn fn, void *user, int64_t every);
 int jxg_device_count(void);
 int jxg_set_device(int dev);
 /* device properties: out[0]=CU count, out[1]=clock kHz, out[2]=total HBM MiB, out[3]=LDS bytes/CU */
@@ -572,47 +566,12 @@ int jx_fvlmm_assoc_chunk(const double *s, const double *xcov, const double *y_ro
                          double log10_lbd, const float *snp_chunk, int64_t m_chunk, const float *u_t,
                          int has_nullml, double nullml, double *out);
 
-/* `lmm_reml_assoc_packed_f32` (src/stats/lmm.rs:3040-3362) and its fixed-lambda sibling
- * (`fvlmm_assoc_packed` core of src/stats/fvlmm.rs:4958-5190 with a caller-rotated null model).
- * model: 0 = exact per-SNP REML (lmm), 1 = fixed lambda (fvlmm; `low` carries log10 lambda), 2 = LMM2
- * (`lmm_reml_lmm2_assoc_bed_to_tsv_f32` core, src/stats/lmm.rs:2779-3037; needs nullml; out (m, 6)).
- * warm: 0 none (parity contract), 1 seed with init_log10_lbd.  out (m, 3), or (m, 4) with has_nullml (plrt column,
- * src/stats/lmm.rs:202-330). */
-int jx_assoc_packed(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                    const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                    const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model, double low,
-                    double high, int max_iter, double tol, int warm, double init_log10_lbd, int has_nullml,
-                    double nullml, double *out);
-/* The same with the `model` / `genetic_model` argument of the reference's entry points (`PackedGeneticModel`,
- * src/decode/decode.rs:100-147: 0 add, 1 dom (g > 0), 2 rec (g = 2), 3 het (g = 1) applied to the decode table
- * [0 | 2, 2 maf, 1, 2 | 0] INCLUDING its imputed entry (:163-178), then the row is centred by its own mean (:181-189)).
- * jx_assoc_packed is genetic_model = 0.  Non-additive rows are not affine in the allele count: they take the general
- * (fp16 hi / lo) rotation. */
-int jx_assoc_packed_gm(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                    const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                    const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model, double low,
-                    double high, int max_iter, double tol, int warm, double init_log10_lbd, int has_nullml,
-                    double nullml, double *out, int genetic_model);
-/* lmm_reml_assoc_packed_f32 with the reference's default warm-start chains (src/stats/lmm.rs:3244-3245 `true, true`; the BED
- * route's `use_warm_start`, :2627): the exact scan (model 0) where chain c = rows [chain_off[c], chain_off[c + 1]) of the payload
- * in order (host int64 offsets, chain_off[0] = 0, ascending, chain_off[n_chains] = m; the reference's chains are its blocks of
- * `rotate_block_rows` rows, cut further by rayon's work splitting).  The first valid SNP of a chain starts from init_log10_lbd
- * (warm != 0) or the interval midpoint, every later one from the optimum of the valid SNP before it (:134-161). */
-int jx_assoc_packed_chain(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip, const float *row_maf,
-                          const double *s, const double *xcov, const double *y_rot, const float *u_t, int p,
-                          const int64_t *sample_indices, int n_sel, double low, double high, int max_iter, double tol, int warm,
-                          double init_log10_lbd, int has_nullml, double nullml, double *out, int genetic_model,
-                          const int64_t *chain_off, int64_t n_chains);
-
 /* `lm_block_assoc_packed` (src/stats/glm.rs:3550-3860): the plain LM scan `jx gwas -lmm / -fvlmm` switches to when the null
  * likelihood-ratio test (jx_gwas_lmm_lm_null_lrt_decision) finds no polygenic variance
  * (python/janusx/assoc/workflow_model_stream.py:930-963).  x (n, q0) row-major INCLUDING the intercept column, ixx (q0, q0) =
  * (X'X)^-1 (`_lm_precompute_ixx_qr`, python/janusx/pyBLUP/assoc.py:453-480), decode = mean-imputed additive
  * ([0, clamp(2 maf, 0, 2), 1, 2] or flipped, src/math/bedmath.rs:984-989).  out (m, 4) = beta, se, pwald (two-sided Student t,
- * df = n - q0 - 1), plrt. */
-int jx_lm_assoc_packed(const double *y, const double *x, const double *ixx, int q0, const uint8_t *packed, int64_t m,
-                       int n_samples, const uint8_t *row_flip, const float *row_maf, const int64_t *sample_indices,
-                       int n_sel, double *out);
+ * df = n - q0 - 1), plrt: `jx_lm_residualize` on the host, `jxg_lm_scan_p32` on the device (`pipeline.scan_rows_lm`). */
 /* Host half of the LM scan (glm.rs:3635-3672): r_y = y - X (ixx X'y), *yy_r = r_y'r_y, xr_out (n, q0 + 1) = [X | r_y]
  * rounded through f32 as the reference does before its sgemm. */
 int jx_lm_residualize(const double *y, const double *x, const double *ixx, int n, int q0, double *xr_out,

@@ -23,7 +23,6 @@ c_f = C.c_float
 SIGNATURES = {
     "jx_last_error": [],
     "jx_version": [],
-    "jx_set_progress": [c_p, c_p, c_l],
     "jxg_device_count": [],
     "jxg_set_device": [c_i],
     "jxg_device_info": [c_p],
@@ -132,15 +131,11 @@ SIGNATURES = {
     "jx_rrblup_pcg_packed": [c_p, c_l, c_i, c_p, c_l, c_p, c_p, c_i, c_p, c_p, c_i, c_d, c_d, c_i, c_p, c_p, c_p, c_p],
     "jx_rrblup_exact_snp_packed": [c_p, c_l, c_i, c_p, c_l, c_p, c_p, c_i, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_p, c_p,
                                    c_p, c_p],
-    "jx_assoc_packed": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_d, c_d, c_i, c_d, c_i,
-                        c_d, c_i, c_d, c_p],
     "jxg_sps_ldr": [c_i],
     "jxg_sps_work_doubles": [c_i, c_i],
     "jxg_sps_rows_to_cols_f64": [c_p, c_i, c_i, c_l, c_p, c_i, c_p],
     "jxg_sps_solve_multi": [c_i, c_p, c_p, c_p, c_d, c_p, c_p, c_i, c_i, c_d, c_i, c_p, c_p, c_p, c_p],
     "jxg_sps_scan_sums": [c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p],
-    "jx_assoc_packed_chain": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_d, c_d, c_i, c_d, c_i,
-                              c_d, c_i, c_d, c_p, c_i, c_p, c_l],
     "jxg_lmm_scan_chain_tab": [c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
     "jxg_lmm_scan_chain": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
     "jxg_lmm_scan_exact_chain": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
@@ -148,8 +143,6 @@ SIGNATURES = {
     "jxg_lmm_series_coef_tab": [c_p, c_i, c_i, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p],
     "jxg_lmm_series_brent_tab": [c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_d, c_i, c_i, c_d, c_p, c_p, c_p, c_i, c_p, c_i, c_d,
                                  c_p, c_p, c_p],
-    "jx_assoc_packed_gm": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_d, c_d, c_i, c_d, c_i,
-                           c_d, c_i, c_d, c_p, c_i],
     "jxg_rotate_packed16x_fused": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
                                    c_p],
     "jxg_fvlmm_finish_dev": [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_d, c_i, c_i, c_d, c_d, c_i, c_p, c_p],
@@ -157,7 +150,6 @@ SIGNATURES = {
     "jxg_splmm_grammar_scan_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_p],
     "jxg_splmm_gamma_sums": [c_p, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
     "jx_lm_residualize": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
-    "jx_lm_assoc_packed": [c_p, c_p, c_p, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_p],
     "jx_lm_assoc_dense": [c_p, c_p, c_p, c_i, c_p, c_l, c_i, c_p],
     "jxg_lm_scan_dense": [c_p, c_i, c_i, c_l, c_p, c_i, c_p, c_d, c_p, c_p, c_p],
     "jxg_decode_rows_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_l, c_p],

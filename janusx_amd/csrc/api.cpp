@@ -112,31 +112,6 @@ static void grm_lut_from_maf(float maf, bool flip, int method, float out[4]) {
     out[3] = (g2 - mean_g) * sc;
 }
 
-// `PackedGeneticModel::apply` (src/decode/decode.rs:132-160): 0 add, 1 dom, 2 rec, 3 het
-static inline float gm_apply(int gm, float gf) {
-    const double g = (double)gf;
-    switch (gm) {
-    case 1: return g > 0.0 ? 1.0f : 0.0f;
-    case 2: return fabs(g - 2.0) < 1e-6 ? 1.0f : 0.0f;
-    case 3: return fabs(g - 1.0) < 1e-6 ? 1.0f : 0.0f;
-    default: return gf;
-    }
-}
-// scan design LUT: the genetic model applied to [0, mu, 1, 2] (or flipped), minus the actual row mean
-// (src/decode/decode.rs:163-189, 218-221). counts = (missing, het, hom_alt) over the n selected samples.
-static void scan_lut_from_counts(float maf, bool flip, const int32_t *cnt, int n, float out[4], int gm = 0) {
-    const float mu = gm_apply(gm, (float)fmax(2.0 * (double)maf, 0.0));
-    const float v0 = gm_apply(gm, flip ? 2.0f : 0.0f), v2 = gm_apply(gm, 1.0f), v3 = gm_apply(gm, flip ? 0.0f : 2.0f);
-    const double c00 = (double)(n - cnt[0] - cnt[1] - cnt[2]);
-    const double sum = c00 * (double)v0 + (double)cnt[0] * (double)mu + (double)cnt[1] * (double)v2 +
-                       (double)cnt[2] * (double)v3;
-    const float mean = (float)(sum / (double)n);
-    out[0] = v0 - mean;
-    out[1] = mu - mean;
-    out[2] = v2 - mean;
-    out[3] = v3 - mean;
-}
-
 // denominators, src/stats/grm.rs:91-111 (full-sample centred) and bedmath.rs:1411-1438 (subset route)
 static double grm_varsum(const float *row_maf, int64_t m, int method, bool full) {
     if (method != 1) return (double)m;
@@ -252,37 +227,6 @@ using namespace jx;
 
 extern "C" const char *jx_last_error(void) { return g_err.c_str(); }
 extern "C" int jx_version(void) { return 100; }
-
-// ---- progress hook ------------------------------------------------------------------------------------------------------
-// The reference calls `progress_callback(done, total)` every `progress_every` rows (default: its rotate block) and lets a
-// Python exception raised there (KeyboardInterrupt) end the scan (src/stats/lmm.rs:3214-3330, src/stats/grm.rs:3485-3495).
-// The host layer's row-block loops report through this process-wide hook: `fn` returns nonzero to stop the call, which
-// then fails with "interrupted by the progress callback".  every <= 0: once per internal block.
-typedef int (*jx_progress_fn)(int64_t done, int64_t total, void *user);
-namespace {
-// per calling thread: ctypes runs a call on the Python thread that made it and releases the GIL, so two concurrent
-// scans from different threads each see their own hook
-thread_local jx_progress_fn g_progress = nullptr;
-thread_local void *g_progress_user = nullptr;
-thread_local int64_t g_progress_every = 0;
-struct ProgressTicker {
-    int64_t last = 0;
-    // 0 = go on, 1 = the callback asked to stop
-    int tick(int64_t done, int64_t total, int64_t block) {
-        if (!g_progress) return 0;
-        const int64_t step = g_progress_every > 0 ? g_progress_every : block;
-        if (done < total && done < last + step) return 0;
-        last = done;
-        return g_progress(done, total, g_progress_user) != 0;
-    }
-};
-}  // namespace
-extern "C" int jx_set_progress(jx_progress_fn fn, void *user, int64_t every) {
-    g_progress = fn;
-    g_progress_user = user;
-    g_progress_every = every;
-    return 0;
-}
 
 extern "C" int jxg_device_count(void) {
     int c = 0;
@@ -994,320 +938,6 @@ extern "C" int jx_fvlmm_assoc_chunk(const double *s, const double *xcov, const d
 }
 
 // ---------------------------------------------------------------------------------------------------
-// lmm_reml_assoc_packed_f32 (src/stats/lmm.rs:3040-3362) / fixed-lambda sibling
-// ---------------------------------------------------------------------------------------------------
-extern "C" int jx_assoc_packed_gm(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                                  const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                                  const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model,
-                                  double low, double high, int max_iter, double tol, int warm, double init_log10_lbd,
-                                  int has_nullml, double nullml, double *out, int genetic_model);
-extern "C" int jx_assoc_packed(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                               const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                               const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model,
-                               double low, double high, int max_iter, double tol, int warm, double init_log10_lbd,
-                               int has_nullml, double nullml, double *out) {
-    return jx_assoc_packed_gm(packed, m, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, p, sample_indices, n_sel, model, low,
-                              high, max_iter, tol, warm, init_log10_lbd, has_nullml, nullml, out, 0);
-}
-static int assoc_packed_impl(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                             const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                             const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model,
-                             double low, double high, int max_iter, double tol, int warm, double init_log10_lbd,
-                             int has_nullml, double nullml, double *out, int genetic_model, const int64_t *chain_off,
-                             int64_t n_chains);
-extern "C" int jx_assoc_packed_gm(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                                  const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                                  const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model,
-                                  double low, double high, int max_iter, double tol, int warm, double init_log10_lbd,
-                                  int has_nullml, double nullml, double *out, int genetic_model) {
-    return assoc_packed_impl(packed, m, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, p, sample_indices, n_sel, model, low,
-                             high, max_iter, tol, warm, init_log10_lbd, has_nullml, nullml, out, genetic_model, nullptr, 0);
-}
-// The exact scan (model 0) along the reference's warm-start chains (`carry_warm_start`, src/stats/lmm.rs:134-161: on in
-// `lmm_reml_assoc_packed_f32` :3244-3245 and, unless JX_LMM_UNIFIED_NO_WARM_START is set, in the BED route :2627): chain c is the
-// rows [chain_off[c], chain_off[c + 1]) of the payload in order (chain_off[0] = 0, ascending, chain_off[n_chains] = m); the
-// first valid SNP of a chain starts from init_log10_lbd (warm != 0) or the interval midpoint, every later one from the optimum
-// of the valid SNP before it.  The chains run in parallel, the rows of a chain in sequence.
-extern "C" int jx_assoc_packed_chain(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                                     const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                                     const float *u_t, int p, const int64_t *sample_indices, int n_sel, double low, double high,
-                                     int max_iter, double tol, int warm, double init_log10_lbd, int has_nullml, double nullml,
-                                     double *out, int genetic_model, const int64_t *chain_off, int64_t n_chains) {
-    if (m > 0) {
-        if (!chain_off || n_chains <= 0) return fail("jx_assoc_packed_chain: chain offsets are required");
-        if (chain_off[0] != 0 || chain_off[n_chains] != m) return fail("jx_assoc_packed_chain: chain offsets must run from 0 to m");
-        for (int64_t c = 0; c < n_chains; ++c)
-            if (chain_off[c + 1] < chain_off[c]) return fail("jx_assoc_packed_chain: chain offsets must ascend");
-    }
-    return assoc_packed_impl(packed, m, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, p, sample_indices, n_sel, 0, low, high,
-                             max_iter, tol, warm, init_log10_lbd, has_nullml, nullml, out, genetic_model, chain_off, n_chains);
-}
-static int assoc_packed_impl(const uint8_t *packed, int64_t m, int n_samples, const uint8_t *row_flip,
-                             const float *row_maf, const double *s, const double *xcov, const double *y_rot,
-                             const float *u_t, int p, const int64_t *sample_indices, int n_sel, int model,
-                             double low, double high, int max_iter, double tol, int warm, double init_log10_lbd,
-                             int has_nullml, double nullml, double *out, int genetic_model, const int64_t *chain_off,
-                             int64_t n_chains) {
-    if (genetic_model < 0 || genetic_model > 3) return fail("model must be one of: add, dom, rec, het");
-    const int cols = model == 2 ? 6 : (has_nullml ? 4 : 3);
-    if (model < 0 || model > 2) return fail("model must be 0 (lmm), 1 (fvlmm) or 2 (lmm2)");
-    if (model == 2 && !(has_nullml && std::isfinite(nullml))) return fail("nullml must be finite");
-    if (n_samples <= 0) return fail("n_samples must be > 0");
-    if (model != 1 && low >= high) return fail("low must be < high");
-    if (model != 1 && !(isfinite(tol) && tol > 0.0)) return fail("tol must be positive and finite");
-    if (m <= 0) return 0;
-    SampleSel sel;
-    if (make_sample_sel(sample_indices, n_sel, n_samples, sel)) return 1;
-    const int n = sel.n;
-    DevBuf p32, dcnt;
-    if (stage_p32(packed, m, n_samples, sel, p32)) return 1;
-    if (dcnt.alloc(sizeof(int32_t) * 3 * (size_t)m)) return 1;
-    if (jxg_row_counts_p32(p32.as<uint8_t>(), m, n, dcnt.as<int32_t>(), nullptr)) return 1;
-    std::vector<int32_t> cnt((size_t)m * 3);
-    JX_HIP(hipMemcpy(cnt.data(), dcnt.p, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    std::vector<float> lut((size_t)m * 4);
-    for (int64_t j = 0; j < m; ++j)
-        scan_lut_from_counts(row_maf[j], row_flip[j] != 0, &cnt[(size_t)j * 3], n, &lut[(size_t)j * 4], genetic_model);
-
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    FvDev fv;
-    if (model == 1 && fv.prepare(nd, n, p, pow(10.0, low))) return 1;
-
-    const int64_t npad = (int64_t)num_tiles(n) * JXG_TILE;
-    DevBuf dut, uhi, ulo, dlut, drot, dout;
-    if (dut.alloc(sizeof(float) * (size_t)n * n)) return 1;
-    JX_HIP(hipMemcpy(dut.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-    if (uhi.alloc(sizeof(uint16_t) * (size_t)(npad * npad)) || ulo.alloc(sizeof(uint16_t) * (size_t)(npad * npad)))
-        return 1;
-    const int scale_exp = 10;
-    if (jxg_ut_split(dut.as<float>(), n, uhi.as<uint16_t>(), ulo.as<uint16_t>(), scale_exp, nullptr)) return 1;
-    DevBuf dusum, dlut16, drowoff;
-    if (dusum.alloc(sizeof(float) * (size_t)npad)) return 1;
-    if (jxg_ut_rowsum(dut.as<float>(), n, dusum.as<float>(), nullptr)) return 1;
-    JX_HIP(hipDeviceSynchronize());
-    dut.release();
-    if (dlut.alloc(lut.size() * sizeof(float))) return 1;
-    JX_HIP(hipMemcpy(dlut.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-    // fp16 LUT records once for all rows; rows without missing calls as integer LUT + offset (exact-row rotation)
-    if (dlut16.alloc((size_t)16 * (size_t)m) || drowoff.alloc(sizeof(float) * (size_t)m)) return 1;
-    const int64_t brows = 8192;
-    // From n = 4096 the rows of a block are dealt to the int8 rotation (design rows without a missing call: three int8 planes
-    // of U, k_rotate_i8.hip) and the 256-tile fp16 kernel by position lists, as pipeline.scan_rows does (JXGPU_ROT_I8=0: off)
-    static const bool q_env = !(getenv("JXGPU_ROT_I8") && atoi(getenv("JXGPU_ROT_I8")) == 0);
-    const int fused_mode = getenv("JXGPU_FVLMM_FUSED") ? atoi(getenv("JXGPU_FVLMM_FUSED")) : 1;
-    const bool use_q = n >= 4096 && q_env && !(model == 1 && p <= 8 && fused_mode == 2);
-    // fixed lambda below that size: the rotation kernel's fused epilogue reduces the tile in place, G~ is never written
-    const bool fused = model == 1 && p <= 8 && fused_mode != 0 && !use_q;
-    // rows with a few missing calls keep the exact rotation where the int8 kernel runs; their missing-call term is added behind
-    // it (jxg_rotate_missing_correct), exactly as pipeline.scan_rows does
-    DevBuf drowmiss, dusamp;
-    // mean missing calls per row over the rows that can pass a quality filter (<= n / 10 missing calls), as
-    // pipeline.Panel.mean_missing does: mostly-missing junk rows must not decide the path of the others
-    double miss_sum = 0.0;
-    int64_t miss_rows = 0;
-    for (int64_t j = 0; j < m; ++j) {
-        const double mi = (double)cnt[(size_t)j * 3];
-        if (mi <= (double)n / 10.0) {
-            miss_sum += mi;
-            ++miss_rows;
-        }
-    }
-    const int miss_max = use_q ? jxg_rot_miss_max(n, miss_rows > 0 ? miss_sum / (double)miss_rows : 0.0) : 0;
-    bool any_rowmiss = false;
-    if (miss_max > 0) {
-        if (drowmiss.alloc(sizeof(float) * (size_t)m)) return 1;
-        JX_HIP(hipMemset(drowmiss.p, 0, sizeof(float) * (size_t)m));
-    }
-    if (jxg_lut_split_rows_m(p32.as<uint8_t>(), m, n, nullptr, dlut.as<float>(), m, dlut16.p, drowoff.as<float>(),
-                             miss_max > 0 ? drowmiss.as<float>() : nullptr, miss_max, nullptr))
-        return 1;
-    // beyond n / 300 missing calls per row (limit > 256 = none): the missing-call term as one more int8 product
-    // (jxg_rotate_missing_dense) over the rows that have one, instead of the gather form
-    const bool miss_dense = miss_max > 256;
-    std::vector<float> hm;
-    if (miss_max > 0) {
-        hm.resize((size_t)m);
-        JX_HIP(hipMemcpy(hm.data(), drowmiss.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < m && !any_rowmiss; ++i) any_rowmiss = hm[(size_t)i] != 0.0f;
-    }
-    DevBuf dq, dumax, dsel, dselm;
-    std::vector<float> hrowoff;
-    std::vector<int32_t> hsel;
-    if (use_q) {
-        if (dq.alloc((size_t)3 * (size_t)(npad * npad)) || dumax.alloc(sizeof(float) * (size_t)npad)) return 1;
-        DevBuf dut2;
-        if (dut2.alloc(sizeof(float) * (size_t)n * n)) return 1;
-        JX_HIP(hipMemcpy(dut2.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-        if (jxg_ut_quant3(dut2.as<float>(), n, dq.as<int8_t>(), dumax.as<float>(), nullptr)) return 1;
-        if (any_rowmiss && !miss_dense) {
-            if (dusamp.alloc(sizeof(float) * (size_t)n * n)) return 1;
-            if (jxg_transpose_f32(dut2.as<float>(), n, dusamp.as<float>(), nullptr)) return 1;
-        }
-        JX_HIP(hipDeviceSynchronize());
-        hrowoff.resize((size_t)m);
-        JX_HIP(hipMemcpy(hrowoff.data(), drowoff.p, sizeof(float) * (size_t)m, hipMemcpyDeviceToHost));
-        if (dsel.alloc(sizeof(int32_t) * (size_t)brows)) return 1;
-        hsel.resize((size_t)brows);
-        if (any_rowmiss && miss_dense && dselm.alloc(sizeof(int32_t) * (size_t)brows)) return 1;
-    }
-    DevBuf dsums, dachol;
-    if (fused) {
-        if (dsums.alloc(sizeof(double) * (size_t)num_tiles(n) * brows * (p + 2)) || dachol.alloc(sizeof(double) * (size_t)p * p))
-            return 1;
-        JX_HIP(hipMemcpy(dachol.p, fv.a_chol.data(), sizeof(double) * (size_t)p * p, hipMemcpyHostToDevice));
-    } else if (drot.alloc(sizeof(float) * (size_t)brows * n)) {
-        return 1;
-    }
-    if (dout.alloc(sizeof(double) * (size_t)brows * cols)) return 1;
-    DevBuf drows;
-    if (drows.alloc(sizeof(int32_t) * (size_t)brows)) return 1;
-    std::vector<int32_t> hrows((size_t)brows);
-    // ---- warm-start chains (model 0) ------------------------------------------------------------------------------------
-    // carry: one state per chain (NaN: none).  With the series form (k_scan_fast.hip) the series of a SUPER-BLOCK of rows are kept
-    // and ONE Brent launch walks every chain that touches it -- a block of 8192 rows holds 16 chains of 512 rows, far too few
-    // sequential jobs for 256 CUs; without it (wide bounds, many covariates) the chains are walked block by block.  A chain cut
-    // by a block or super-block boundary continues from its carry state.
-    const bool chain = chain_off != nullptr && model == 0;
-    DevBuf dcarry, dchoff, dtab, dscoef, dsssq, dout_sb;
-    std::vector<int32_t> hchoff;
-    int64_t sd = 0, sb_rows = 0, sb0 = 0;            // series doubles per row; rows per super-block; first row of the open one
-    if (chain) {
-        if (dcarry.alloc(sizeof(double) * (size_t)n_chains)) return 1;
-        std::vector<double> hc((size_t)n_chains, (warm && std::isfinite(init_log10_lbd)) ? init_log10_lbd : std::nan(""));
-        JX_HIP(hipMemcpy(dcarry.p, hc.data(), sizeof(double) * (size_t)n_chains, hipMemcpyHostToDevice));
-        const int64_t tb = jxg_lmm_tables_bytes(n, p, low, high);
-        sd = tb > 0 ? jxg_lmm_series_doubles(p, low, high) : 0;
-        if (sd > 0) {
-            if (dtab.alloc((size_t)tb)) return 1;
-            if (jxg_lmm_tables_build(nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), n, p, low, high, dtab.p, nullptr))
-                return 1;
-            const int64_t cap = ((int64_t)8 << 30) / (8 * (sd + 1 + cols));
-            sb_rows = std::min<int64_t>(m, std::max<int64_t>(brows, cap / brows * brows));
-            if (dscoef.alloc(sizeof(double) * (size_t)(sb_rows * sd)) || dsssq.alloc(sizeof(double) * (size_t)sb_rows) ||
-                dout_sb.alloc(sizeof(double) * (size_t)(sb_rows * cols)))
-                return 1;
-        }
-        if (dchoff.alloc(sizeof(int32_t) * (size_t)(std::min<int64_t>(n_chains, sd > 0 ? sb_rows : brows) + 2))) return 1;
-    }
-    // chains touching the rows [a, b): local offsets into hchoff, -> index of the first one
-    auto chain_segments = [&](int64_t a, int64_t b, int64_t &c_first) -> int {
-        const int64_t *lo = std::upper_bound(chain_off, chain_off + n_chains + 1, a) - 1;       // last offset <= a
-        c_first = lo - chain_off;
-        if (c_first >= n_chains) c_first = n_chains - 1;
-        hchoff.clear();
-        int64_t c = c_first;
-        for (; c < n_chains && chain_off[c] < b; ++c)
-            hchoff.push_back((int32_t)(std::max<int64_t>(chain_off[c], a) - a));
-        hchoff.push_back((int32_t)(std::min<int64_t>(chain_off[c], b) - a));
-        return (int)(c - c_first);
-    };
-    auto chain_brent_superblock = [&](int64_t a, int64_t b) -> int {
-        int64_t c_first = 0;
-        const int nch = chain_segments(a, b, c_first);
-        if ((size_t)(nch + 1) * sizeof(int32_t) > dchoff.bytes && dchoff.alloc(sizeof(int32_t) * (size_t)(nch + 1))) return 1;
-        JX_HIP(hipMemcpy(dchoff.p, hchoff.data(), sizeof(int32_t) * (size_t)(nch + 1), hipMemcpyHostToDevice));
-        if (jxg_lmm_series_brent_tab((int)(b - a), n, nd.s.as<double>(), nd.x.as<double>(), p, low, high, dtab.p, tol, max_iter, 0,
-                                     0.0, dscoef.as<double>(), dsssq.as<double>(), dchoff.as<int32_t>(), nch,
-                                     dcarry.as<double>() + c_first, has_nullml, nullml, dout_sb.as<double>(), nullptr, nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)a * cols, dout_sb.p, sizeof(double) * (size_t)(b - a) * cols, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    ProgressTicker ticker;
-    for (int64_t r0 = 0; r0 < m; r0 += brows) {
-        const int rows = (int)std::min<int64_t>(brows, m - r0);
-        for (int i = 0; i < rows; ++i) hrows[i] = (int32_t)(r0 + i);
-        JX_HIP(hipMemcpy(drows.p, hrows.data(), sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-        if (fused) {
-            if (jxg_rotate_packed16x_fused(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), rows,
-                                           (const uint8_t *)dlut16.p + (size_t)r0 * 16, drowoff.as<float>() + r0,
-                                           dusum.as<float>(), uhi.as<uint16_t>(), ulo.as<uint16_t>(), scale_exp,
-                                           fv.w.as<float>(), fv.py.as<float>(), fv.wx.as<float>(), p, dsums.as<double>(),
-                                           p + 2, 0, nullptr) ||
-                jxg_fvlmm_finish_dev(dsums.as<double>(), num_tiles(n), p + 2, rows, n, p, dachol.as<double>(), fv.sc[0], (int)fv.sc[2],
-                                     has_nullml, nullml, fv.sc[1], 0, dout.as<double>(), nullptr))
-                return 1;
-        } else if (use_q) {
-            // positions of the exact rows (finite row offset) first, the others behind them
-            int ne = 0;
-            for (int i = 0; i < rows; ++i)
-                if (!std::isnan(hrowoff[(size_t)r0 + i])) hsel[ne++] = i;
-            int nx = ne;
-            for (int i = 0; i < rows; ++i)
-                if (std::isnan(hrowoff[(size_t)r0 + i])) hsel[nx++] = i;
-            JX_HIP(hipMemcpy(dsel.p, hsel.data(), sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-            if (jxg_rotate_packed16x_q(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), rows,
-                                       (const uint8_t *)dlut16.p + (size_t)r0 * 16, drowoff.as<float>() + r0, dusum.as<float>(),
-                                       uhi.as<uint16_t>(), ulo.as<uint16_t>(), scale_exp, dq.as<int8_t>(), dumax.as<float>(),
-                                       ne > 0 ? dsel.as<int32_t>() : nullptr, ne, rows > ne ? dsel.as<int32_t>() + ne : nullptr,
-                                       rows - ne, drot.as<float>(), nullptr))
-                return 1;
-            if (any_rowmiss && miss_dense) {
-                int nm = 0;
-                for (int i = 0; i < rows; ++i)
-                    if (hm[(size_t)r0 + i] != 0.0f) hsel[nm++] = i;
-                if (nm > 0) {
-                    JX_HIP(hipMemcpy(dselm.p, hsel.data(), sizeof(int32_t) * (size_t)nm, hipMemcpyHostToDevice));
-                    if (jxg_rotate_missing_dense(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), dselm.as<int32_t>(), nm,
-                                                 drowmiss.as<float>() + r0, dq.as<int8_t>(), dumax.as<float>(), drot.as<float>(), n,
-                                                 nullptr))
-                        return 1;
-                }
-            } else if (any_rowmiss && jxg_rotate_missing_correct(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), rows,
-                                                                 drowmiss.as<float>() + r0, dusamp.as<float>(), drot.as<float>(), n,
-                                                                 nullptr))
-                return 1;
-        } else if (jxg_rotate_packed16x(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), rows,
-                                        (const uint8_t *)dlut16.p + (size_t)r0 * 16, drowoff.as<float>() + r0,
-                                        dusum.as<float>(), uhi.as<uint16_t>(), ulo.as<uint16_t>(), scale_exp,
-                                        drot.as<float>(), nullptr)) {
-            return 1;
-        }
-        if (fused) {
-        } else if (chain && sd > 0) {
-            // series of this block behind those of the open super-block; Brent when the super-block is full or the payload ends
-            if (jxg_lmm_series_coef_tab(drot.as<float>(), rows, n, nd.x.as<double>(), p, low, high, dtab.p,
-                                        dscoef.as<double>() + (size_t)(r0 - sb0) * sd, dsssq.as<double>() + (r0 - sb0), nullptr))
-                return 1;
-            if (r0 + rows - sb0 >= sb_rows || r0 + rows >= m) {
-                if (chain_brent_superblock(sb0, r0 + rows)) return 1;
-                sb0 = r0 + rows;
-            }
-            if (ticker.tick(r0 + rows, m, brows)) return fail("interrupted by the progress callback");
-            continue;
-        } else if (chain) {
-            int64_t c_first = 0;
-            const int nch = chain_segments(r0, r0 + rows, c_first);
-            if ((size_t)(nch + 1) * sizeof(int32_t) > dchoff.bytes && dchoff.alloc(sizeof(int32_t) * (size_t)(nch + 1))) return 1;
-            JX_HIP(hipMemcpy(dchoff.p, hchoff.data(), sizeof(int32_t) * (size_t)(nch + 1), hipMemcpyHostToDevice));
-            if (jxg_lmm_scan_chain(drot.as<float>(), rows, n, nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), p, low, high,
-                                   tol, max_iter, dchoff.as<int32_t>(), nch, dcarry.as<double>() + c_first, has_nullml, nullml,
-                                   dout.as<double>(), nullptr, nullptr))
-                return 1;
-        } else if (model == 0) {
-            if (jxg_lmm_scan(drot.as<float>(), rows, n, nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), p, low,
-                             high, tol, max_iter, warm, init_log10_lbd, has_nullml, nullml, dout.as<double>(), nullptr,
-                             nullptr))
-                return 1;
-        } else if (model == 2) {
-            if (jxg_lmm2_scan(drot.as<float>(), rows, n, nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), p, low,
-                              high, tol, max_iter, warm, init_log10_lbd, nullml, dout.as<double>(), nullptr))
-                return 1;
-        } else {
-            if (jxg_fvlmm_scan(drot.as<float>(), rows, n, p, fv.w.as<float>(), fv.py.as<float>(), fv.wx.as<float>(),
-                               fv.a_chol.data(), fv.sc[0], (int)fv.sc[2], has_nullml, nullml, fv.sc[1],
-                               dout.as<double>(), nullptr))
-                return 1;
-        }
-        JX_HIP(hipMemcpy(out + (size_t)r0 * cols, dout.p, sizeof(double) * (size_t)rows * cols, hipMemcpyDeviceToHost));
-        if (ticker.tick(r0 + rows, m, brows)) return fail("interrupted by the progress callback");
-    }
-    return 0;
-}
-
-
-// ---------------------------------------------------------------------------------------------------
 // lm_block_assoc_packed (src/stats/glm.rs:3550-3860): the plain LM scan the mixed-model routes fall back to
 // ---------------------------------------------------------------------------------------------------
 extern "C" int jxg_lm_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows,
@@ -1339,54 +969,6 @@ extern "C" int jx_lm_residualize(const double *y, const double *x, const double 
         xr_out[(size_t)i * ld + q0] = (double)(float)resid;
     }
     *yy_r_out = yy;
-    return 0;
-}
-
-extern "C" int jx_lm_assoc_packed(const double *y, const double *x, const double *ixx, int q0, const uint8_t *packed,
-                                  int64_t m, int n_samples, const uint8_t *row_flip, const float *row_maf,
-                                  const int64_t *sample_indices, int n_sel, double *out) {
-    if (n_samples <= 0) return fail("n_samples must be > 0");
-    if (m <= 0) return 0;
-    SampleSel sel;
-    if (make_sample_sel(sample_indices, n_sel, n_samples, sel)) return 1;
-    const int n = sel.n;
-    std::vector<double> xr((size_t)n * (q0 + 1));
-    double yy_r = 0.0;
-    if (jx_lm_residualize(y, x, ixx, n, q0, xr.data(), &yy_r)) return 1;
-    DevBuf p32;
-    if (stage_p32(packed, m, n_samples, sel, p32)) return 1;
-    std::vector<float> lut((size_t)m * 4);
-    for (int64_t j = 0; j < m; ++j) {                       // `decode_mean_imputed_additive_packed_block_rows_f32`,
-        const float mean_g = std::min(std::max(2.0f * row_maf[j], 0.0f), 2.0f);   // src/math/bedmath.rs:984-989
-        float *l = &lut[(size_t)j * 4];
-        if (row_flip[j]) l[0] = 2.0f, l[1] = mean_g, l[2] = 1.0f, l[3] = 0.0f;
-        else l[0] = 0.0f, l[1] = mean_g, l[2] = 1.0f, l[3] = 2.0f;
-    }
-    DevBuf dlut, dxr, dixx, dwork, dout;
-    if (dlut.alloc(lut.size() * sizeof(float)) || dxr.alloc(xr.size() * sizeof(double)) ||
-        dixx.alloc(sizeof(double) * (size_t)std::max(q0 * q0, 1)))
-        return 1;
-    JX_HIP(hipMemcpy(dlut.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-    JX_HIP(hipMemcpy(dxr.p, xr.data(), xr.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (q0 > 0) JX_HIP(hipMemcpy(dixx.p, ixx, sizeof(double) * (size_t)q0 * q0, hipMemcpyHostToDevice));
-    const int64_t brows = 1 << 20;
-    if (dwork.alloc(sizeof(double) * (size_t)std::min(brows, m) * (q0 + 2)) ||
-        dout.alloc(sizeof(double) * (size_t)std::min(brows, m) * 4))
-        return 1;
-    DevBuf drows;
-    if (drows.alloc(sizeof(int32_t) * (size_t)std::min(brows, m))) return 1;
-    std::vector<int32_t> hrows((size_t)std::min(brows, m));
-    ProgressTicker ticker;
-    for (int64_t r0 = 0; r0 < m; r0 += brows) {
-        const int rows = (int)std::min<int64_t>(brows, m - r0);
-        for (int i = 0; i < rows; ++i) hrows[i] = (int32_t)(r0 + i);
-        JX_HIP(hipMemcpy(drows.p, hrows.data(), sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice));
-        if (jxg_lm_scan_p32(p32.as<uint8_t>(), m, n, drows.as<int32_t>(), rows, dlut.as<float>() + (size_t)r0 * 4,
-                            dxr.as<double>(), q0, dixx.as<double>(), yy_r, dwork.as<double>(), dout.as<double>(), nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)r0 * 4, dout.p, sizeof(double) * (size_t)rows * 4, hipMemcpyDeviceToHost));
-        if (ticker.tick(r0 + rows, m, brows)) return fail("interrupted by the progress callback");
-    }
     return 0;
 }
 

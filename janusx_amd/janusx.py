@@ -5,8 +5,9 @@ replaces (signatures: /root/reference/src/lib.rs:691-1005 registrations, ``#[pyo
 lines) and forwards to the HIP library through the C ABI (``include/jxgpu.h``, host layer).  Arguments that only
 steer CPU threading in the reference (``threads``, ``block_cols``, ``rotate_block_rows``, ``mmap_window_mb``) are
 accepted and ignored; ``progress_callback(done, total)`` follows the reference's cadence on the packed association
-scans (C-ABI hook `jx_set_progress`: every `progress_every` rows, default one 8192-row block; an exception raised by the
-callback stops the scan) and is called once at completion elsewhere.
+scans (`pipeline.scan_rows` / `scan_rows_lm`: every `progress_every` rows, default one 8192-row block; an exception raised by
+the callback stops the scan) and is called once at completion elsewhere.  The packed association scans build a `Panel` of the
+payload and run `pipeline.scan_rows` on a caller-rotated `SpectralModel`: the one orchestration `jx gwas` runs as well.
 
 A reference call site such as ``jxrs.grm_packed_f32(packed, n, flip, maf, idx, method=1)`` works unchanged
 with ``import janusx_amd.janusx as jxrs``.
@@ -82,34 +83,35 @@ def _done(cb, total):
         cb(int(total), int(total))
 
 
-class _progress_hook:
-    """Installs `progress_callback(done, total)` as the C-ABI progress hook for the duration of one host-layer call
-    (the reference's cadence: every `progress_every` rows, default one internal block; src/stats/lmm.rs:3214-3330).  An
-    exception raised by the callback (KeyboardInterrupt included) stops the native loop and is re-raised here."""
-    _CB = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_int64, C.c_void_p)
+def _device_payload(pk):
+    """A payload checked by `_payload` as a torch CUDA tensor: a device tensor as it is, a host array uploaded."""
+    import torch
+    if _is_device_tensor(pk):
+        return pk
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)          # a read-only host array: only read on its way to the device
+        return torch.from_numpy(pk).to(torch.device("cuda", torch.cuda.current_device()))
 
-    def __init__(self, cb, every):
-        self.cb, self.every, self.exc, self.fn = cb, int(every or 0), None, None
 
-    def __enter__(self):
-        if self.cb is not None:
-            def tramp(done, total, _user):
-                try:
-                    self.cb(int(done), int(total))
-                    return 0
-                except BaseException as e:      # noqa: BLE001 - handed back to the caller of the native function
-                    self.exc = e
-                    return 1
-            self.fn = self._CB(tramp)
-            lib().jx_set_progress(self.fn, None, self.every)
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if self.cb is not None:
-            lib().jx_set_progress(None, None, 0)
-        if self.exc is not None:
-            raise self.exc
-        return False
+def _panel(packed, n_samples, sample_indices=None):
+    """`pipeline.Panel` (P32 image in HBM) of a host (numpy) or device (torch CUDA) payload over the selected samples.  Refuses,
+    before anything is allocated, when the device images do not fit the free HBM; the raw device copy of a host payload is
+    dropped once it is re-tiled."""
+    import torch
+    from . import pipeline as pl
+    pk, _ptr_unused, m = _payload(packed, n_samples)
+    if m == 0:
+        raise RuntimeError("packed matrix has zero SNP rows")
+    idx = None if sample_indices is None else _c(sample_indices, np.int64).ravel()
+    bps = (int(n_samples) + 3) // 4
+    n_sel = int(n_samples) if idx is None else int(idx.shape[0])
+    need = (0.0 if _is_device_tensor(pk) else float(m * bps)) + float(lib().jxg_num_tiles(n_sel)) * m * 32.0
+    free = torch.cuda.mem_get_info()[0]
+    if need > 0.95 * free:
+        raise RuntimeError(f"packed payload of {(m * bps) >> 20} MiB: its device images need {int(need / 1048576.0)} MiB of HBM, "
+                           f"{free >> 20} MiB are free (split the SNP rows over several calls)")
+    return pl.Panel(_device_payload(pk), int(n_samples), idx)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1434,9 +1436,8 @@ def splmm_exact_scan_from_jxgrm(jxgrm_path, y, packed, packed_n_samples, maf, ro
     lut[:, 2] = 1.0
     lut[:, 3] = np.where(flip[rows], 0.0, 2.0)
     if getattr(model, "factor_route", False):
-        dev = torch.device("cuda", torch.cuda.current_device())
-        packed_t = pk.to(dev) if _is_device_tensor(pk) else torch.from_numpy(pk if pk.flags.writeable else pk.copy()).to(dev)
-        panel = pl.Panel(packed_t, n_full, panel_idx)
+        panel = _panel(pk, n_full, panel_idx)
+        dev = panel.device
         rows_t = torch.from_numpy(rows.astype(np.int32)).to(dev)
         lut_t = torch.from_numpy(lut).to(dev)
         vinv_x, py, a_chol, ypy = model.null_state(lam)
@@ -1449,19 +1450,14 @@ def splmm_exact_scan_from_jxgrm(jxgrm_path, y, packed, packed_n_samples, maf, ro
         out = pl.scan_rows_splmm_factor(rows_f32, len(rows), model.n, model.p, model.device_csr(), model.diag, lam, vinv_x, py,
                                         a_chol, ypy, dev)
         return out.cpu().numpy(), float(log10_lambda), null
-    dev = model.s_dev.device
     fv_state = _splmm_exact_null_state(model, lam)
-    if _is_device_tensor(pk):
-        packed_t = pk.to(dev)
-    else:   # torch.from_numpy wants a writable array (memmapped payloads are not)
-        packed_t = torch.from_numpy(pk if pk.flags.writeable else pk.copy()).to(dev)
     if model.blocks is not None:
         if panel_idx is None:
             panel_idx = np.arange(n_full, dtype=np.int64)
-        rot = pl.BlockRotation(packed_t, n_full, panel_idx, model.blocks)
+        rot = pl.BlockRotation(_device_payload(pk), n_full, panel_idx, model.blocks)
         out = _scan_my_rows(lambda r, l: pl.scan_rows_splmm_blocks(rot, model.p, r, l, fv_state), rows.astype(np.int32), lut)
     else:
-        panel = pl.Panel(packed_t, n_full, panel_idx)
+        panel = _panel(pk, n_full, panel_idx)
         sm = pl.SpectralModel(model.s_dev, model.ut_dev, model.x_design, model.y_raw, fit_null=False)
         out = _scan_my_rows(lambda r, l: pl.scan_rows(panel, sm, r, l, mode="splmm", fv_state=fv_state),
                             rows.astype(np.int32), lut)
@@ -1808,27 +1804,26 @@ def _splmm_assoc(prefix, y, lbd, x_cov, sample_indices, operator_sample_indices,
     if sp_idx is not None and sp_idx.shape[0] != inp["n"]:
         raise RuntimeError(f"sparse_sample_indices length mismatch: got {sp_idx.shape[0]}, expected {inp['n']}")
     lam = float(lbd)
-    with _progress_hook(progress_callback, progress_every):
-        if mode == "exact":
-            if inp["gm_code"] != 0:      # `exact_scan_blocks_core`, src/stats/splmm.rs:2662-2664
-                raise RuntimeError("SparseLMM exact denominator mode requires additive model")
-            if not lam > 0.0:
-                raise RuntimeError("K + lambda I is not positive definite at lambda=0")
-            out, _l10, _null = splmm_exact_scan_from_jxgrm(path, inp["y"], inp["pk"], inp["n_full"],
-                                                           _expand_rows(inp["maf"], inp["rows"], inp["pk"].shape[0]),
-                                                           _expand_rows(inp["flip"], inp["rows"], inp["pk"].shape[0]),
-                                                           inp["x_cov"], inp["scan_idx"], inp["rows"], math.log10(lam),
-                                                           grm_sample_indices=sp_idx)
-            r_hat, req, used = float("nan"), 0, 0
-        else:
-            spm = _sparse_reml_model(path, inp["y"], inp["x_cov"], sp_idx)
-            if not spm.factorizable(lam) and not (lam == 0.0 and spm.smin > 0.0):
-                raise RuntimeError(f"K + lambda I is not positive definite at lambda={lam}")
-            r_hat, out_t, req, used = _splmm_approx_scan(spm, lam, inp["pk"], inp["n_full"], inp["maf"], inp["flip"],
-                                                         inp["rows"], inp["scan_idx"], int(rhat_markers), int(rhat_seed),
-                                                         rhat_rows, gm_code=inp["gm_code"])
-            out = out_t.cpu().numpy()
-            req = int(rhat_markers)
+    if mode == "exact":
+        if inp["gm_code"] != 0:      # `exact_scan_blocks_core`, src/stats/splmm.rs:2662-2664
+            raise RuntimeError("SparseLMM exact denominator mode requires additive model")
+        if not lam > 0.0:
+            raise RuntimeError("K + lambda I is not positive definite at lambda=0")
+        out, _l10, _null = splmm_exact_scan_from_jxgrm(path, inp["y"], inp["pk"], inp["n_full"],
+                                                       _expand_rows(inp["maf"], inp["rows"], inp["pk"].shape[0]),
+                                                       _expand_rows(inp["flip"], inp["rows"], inp["pk"].shape[0]),
+                                                       inp["x_cov"], inp["scan_idx"], inp["rows"], math.log10(lam),
+                                                       grm_sample_indices=sp_idx)
+        r_hat, req, used = float("nan"), 0, 0
+    else:
+        spm = _sparse_reml_model(path, inp["y"], inp["x_cov"], sp_idx)
+        if not spm.factorizable(lam) and not (lam == 0.0 and spm.smin > 0.0):
+            raise RuntimeError(f"K + lambda I is not positive definite at lambda={lam}")
+        r_hat, out_t, req, used = _splmm_approx_scan(spm, lam, inp["pk"], inp["n_full"], inp["maf"], inp["flip"],
+                                                     inp["rows"], inp["scan_idx"], int(rhat_markers), int(rhat_seed),
+                                                     rhat_rows, gm_code=inp["gm_code"])
+        out = out_t.cpu().numpy()
+        req = int(rhat_markers)
     _done(progress_callback, len(inp["rows"]))
     n_all, col_ptr, _r, _v = load_spgrm(path)
     return inp, r_hat, out, req, used, int(col_ptr[-1])
@@ -2407,8 +2402,12 @@ def _resolve_warm_start(warm_start, route_env=None):
 def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, model,
                   low, high, max_iter, tol, warm, init, nullml=None, progress_callback=None, progress_every=0,
                   genetic_model="add", chain_off=None):
-    from .stats import genetic_model_code
-    gm = genetic_model_code(genetic_model)          # `PackedGeneticModel::parse` (src/decode/decode.rs:107-119)
+    """The packed scans of the mirror: model 0 exact per-SNP REML (along `chain_off` when given), 1 fixed lambda at
+    log10 lambda = `low`, 2 LMM2 (needs `nullml`) -> f64 (m, 3 | 4 with nullml | 6 for LMM2).  `pipeline.scan_rows` over a
+    `Panel` of the (row-subsetted) payload with the caller's rotated null model, in blocks of 8192 rows."""
+    from . import pipeline as pl
+    from .stats import genetic_model_code, scan_lut_from_counts
+    genetic_model_code(genetic_model)               # `PackedGeneticModel::parse` (src/decode/decode.rs:107-119)
     s, xcov, y, n, p = _null_args(s, xcov, y_rot)
     if row_indices is not None:
         ri = np.asarray(row_indices, dtype=np.int64)
@@ -2417,8 +2416,8 @@ def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sam
             packed = packed[torch.from_numpy(ri).to(packed.device)]
         else:
             packed = np.ascontiguousarray(_c(packed, np.uint8)[ri])
-    packed, pk_ptr, m = _payload(packed, n_samples)           # host array or device tensor
-    flip = _c(np.asarray(row_flip).astype(np.uint8), np.uint8).ravel()
+    packed, _pk_ptr, m = _payload(packed, n_samples)           # host array or device tensor
+    flip = np.asarray(row_flip).astype(bool).ravel()
     maf = _c(row_maf, np.float32).ravel()
     u_t = _c(u_t, np.float32)
     if u_t.shape != (n, n):
@@ -2427,21 +2426,37 @@ def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sam
     n_eff = n_sel if idx is not None else int(n_samples)
     if n_eff != n:
         raise RuntimeError(f"selected sample count {n_eff} != len(y_rot) {n}")
-    out = np.zeros((m, 6 if int(model) == 2 else (4 if nullml is not None else 3)), dtype=np.float64)
-    if chain_off is not None and int(model) == 0 and m > 0:
+    model = int(model)
+    chain = chain_off is not None and model == 0
+    if chain and m > 0:
         co = np.ascontiguousarray(chain_off, dtype=np.int64)
-        with _progress_hook(progress_callback, progress_every):
-            check(lib().jx_assoc_packed_chain(pk_ptr, m, int(n_samples), _p(flip), _p(maf), _p(s), _p(xcov), _p(y), _p(u_t), p,
-                                              _p(idx), n_sel, float(low), float(high), int(max_iter), float(tol), int(warm),
-                                              float(init), 1 if nullml is not None else 0,
-                                              float(nullml if nullml is not None else 0.0), _p(out), gm, _p(co), len(co) - 1))
-        return out
-    with _progress_hook(progress_callback, progress_every):
-        check(lib().jx_assoc_packed_gm(pk_ptr, m, int(n_samples), _p(flip), _p(maf), _p(s), _p(xcov), _p(y), _p(u_t), p,
-                                       _p(idx), n_sel, int(model), float(low), float(high), int(max_iter), float(tol),
-                                       int(warm), float(init), 1 if nullml is not None else 0,
-                                       float(nullml if nullml is not None else 0.0), _p(out), gm))
-    return out
+        if co.ndim != 1 or len(co) < 2:
+            raise RuntimeError("chain offsets are required")
+        if co[0] != 0 or co[-1] != m:
+            raise RuntimeError("chain offsets must run from 0 to m")
+        if np.any(np.diff(co) < 0):
+            raise RuntimeError("chain offsets must ascend")
+    if model not in (0, 1, 2):
+        raise RuntimeError("model must be 0 (lmm), 1 (fvlmm) or 2 (lmm2)")
+    if model == 2 and not (nullml is not None and np.isfinite(nullml)):
+        raise RuntimeError("nullml must be finite")
+    if int(n_samples) <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    if model != 1 and low >= high:
+        raise RuntimeError("low must be < high")
+    if model != 1 and not (np.isfinite(tol) and tol > 0.0):
+        raise RuntimeError("tol must be positive and finite")
+    if m == 0:
+        return np.zeros((0, 6 if model == 2 else (4 if nullml is not None else 3)), dtype=np.float64)
+    panel = _panel(packed, n_samples, idx)       # of the rows handed: its mean missing-call count picks the rotation path
+    sm = pl.SpectralModel.rotated(s, u_t, xcov, y, panel.device)
+    lut = scan_lut_from_counts(maf, flip, panel.counts(), n, model=genetic_model)
+    start = float(low) if model == 1 else (float(init) if warm else None)       # fixed lambda: 10 ** low
+    out = pl.scan_rows(panel, sm, np.arange(m), lut, ("lmm", "fvlmm", "lmm2")[model], low=float(low), high=float(high),
+                       max_iter=int(max_iter), tol=float(tol), init_log10_lbd=start, block_rows=8192,
+                       nullml=None if nullml is None else float(nullml), chain_off=co if chain else None,
+                       progress=progress_callback, progress_every=progress_every)
+    return out.cpu().numpy()
 
 
 def lmm_reml_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices=None,
@@ -3059,11 +3074,12 @@ def lm_block_assoc_packed(y, x, ixx, packed, n_samples, row_flip, row_maf, sampl
         raise RuntimeError("ixx must be (q0,q0)")
     if n <= q0 + 1:
         raise RuntimeError(f"n too small: require n > q0+1, got n={n}, q0={q0}")
-    out = np.zeros((m, 4), dtype=np.float64)
-    with _progress_hook(progress_callback, progress_every):
-        check(lib().jx_lm_assoc_packed(_p(y), _p(x), _p(ixx), q0, _p(packed), m, int(n_samples), _p(flip), _p(maf),
-                                       _p(idx), n_sel, _p(out)))
-    return out
+    if m == 0:
+        return np.zeros((0, 4), dtype=np.float64)
+    from . import pipeline as pl
+    out = pl.scan_rows_lm(_panel(packed, n_samples, idx), np.arange(m), maf, x, y, flip=flip, ixx=ixx,
+                          progress=progress_callback, progress_every=progress_every)
+    return out.cpu().numpy()
 
 
 def _resolve_assoc_tsv_metadata(bed_prefix, chrom, pos, snp, allele0, allele1, row_indices, expected_len):
@@ -4435,30 +4451,6 @@ def _rsvd_engine(op, kp, k_eff, varsum, seed, power, tol, mode):
     return eigvals, eigvecs, rounds
 
 
-def _rsvd_panel(packed, n_samples, sample_indices):
-    """Panel of a host (numpy) or device (torch CUDA) payload over the selected samples."""
-    import torch
-    from . import pipeline as pl
-    pk, _ptr_unused, m = _payload(packed, n_samples)
-    if m == 0:
-        raise RuntimeError("packed matrix has zero SNP rows")
-    idx = None
-    if sample_indices is not None:
-        idx = _c(sample_indices, np.int64).ravel()
-        if idx.size == 0:
-            raise RuntimeError("sample_indices must not be empty")
-        if idx.min() < 0 or idx.max() >= int(n_samples):
-            raise RuntimeError("sample_indices out of range")
-    if _is_device_tensor(pk):
-        payload = pk
-    else:
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)          # a read-only host array: only read on its way to the device
-            payload = torch.from_numpy(pk).to(torch.device("cuda", torch.cuda.current_device()))
-    return pl.Panel(payload, int(n_samples), idx)
-
-
 def rsvd_packed_subset(packed, n_samples, k, sample_indices=None, seed=42, power=5, tol=1e-1):
     """src/stats/rsvd.rs:1548-1782: randomized SVD of the centred additive design of a packed payload (m, ceil(n / 4)) over the
     selected samples -> (eigvals f32 (k_eff), eigvecs f32 (n, k_eff), row_maf f32 (m), row_flip bool (m)).  Row statistics over
@@ -4478,7 +4470,13 @@ def _rsvd_packed_subset(packed, n_samples, k, sample_indices, seed, power, tol):
     tol = float(np.float32(tol))
     if not (math.isfinite(tol) and tol > 0.0):
         raise RuntimeError("tol must be positive and finite")
-    panel = _rsvd_panel(packed, n_samples, sample_indices)
+    if sample_indices is not None:
+        idx = _c(sample_indices, np.int64).ravel()
+        if idx.size == 0:
+            raise RuntimeError("sample_indices must not be empty")
+        if idx.min() < 0 or idx.max() >= n_samples:
+            raise RuntimeError("sample_indices out of range")
+    panel = _panel(packed, n_samples, sample_indices)
     n, m = panel.n, panel.m
     c = panel.counts().astype(np.int64)
     nm = n - c[:, 0]
@@ -4528,7 +4526,7 @@ def _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload, who, w
         packed, n_fam, bim = payload
     if before_panel is not None:
         before_panel(packed, n_fam)
-    panel = _rsvd_panel(packed, n_fam, None)
+    panel = _panel(packed, n_fam)
     n = panel.n
     c = panel.counts()
     keep, _miss, af, _std = st.packed_prep_row_stats(c, n, float(maf), float(missing_rate), 0.0)

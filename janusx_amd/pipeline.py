@@ -23,6 +23,8 @@ from . import stats as st
 from ._lib import check, lib
 
 SCALE_EXP = 10  # U^T planes are scaled by 2^10 before the fp16 split (keeps the lo plane out of subnormals)
+SERIES_CAP_BYTES = 8 << 30   # chain-series storage of the exact scan: rows per super-block = this / (8 (series + 1 + columns))
+LM_BLOCK_ROWS = 1 << 20      # rows per launch (and per progress report) of the plain LM scan
 
 
 def _ptr(t):
@@ -70,8 +72,9 @@ class Panel:
             idx = np.asarray(sample_idx, dtype=np.int64)
             if idx.size == 0:
                 raise RuntimeError("sample_indices must not be empty")
-            if idx.min() < 0 or idx.max() >= self.n_src:
-                raise RuntimeError(f"sample index out of range: {int(idx.max())} >= {self.n_src}")
+            bad = idx[(idx < 0) | (idx >= self.n_src)]
+            if bad.size:
+                raise RuntimeError(f"sample index out of range: {int(bad[0])} >= {self.n_src}")
             if not (idx.size == self.n_src and np.array_equal(idx, np.arange(self.n_src))):
                 idx_t = torch.from_numpy(idx.astype(np.int32)).to(self.device)
             self.n = int(idx.size)
@@ -94,7 +97,7 @@ class Panel:
         """Mean number of missing calls per row over the rows of the payload that CAN pass a quality filter (at most n / 10
         missing calls: a few percent of mostly-missing junk rows must not push every kept row into the dense missing-call form;
         ADVICE r4), cached: the call-independent statistic behind the choice of the rotation path for rows with a few missing
-        calls (`jxg_rot_miss_max`; api.cpp applies the same rule to the rows it is handed).  Under a distributed run the sum and
+        calls (`jxg_rot_miss_max`).  Under a distributed run the sum and
         the row count are added over the ranks, so that every rank of a payload-sharded scan decides from the same number (with
         a replicated payload every rank already holds the same rows)."""
         if self._mean_missing is None:
@@ -388,6 +391,19 @@ class SpectralModel:
         self._planes = None
         self._fv = None
 
+    @classmethod
+    def rotated(cls, s, u_t, xcov, y, device):
+        """A model from what a caller has rotated already (the mirror's packed entry points): s (n) f64, u_t (n, n) f32 row-major
+        U^T kept as given, X~ (n, p) and y~ (n) f64.  No rotation and no null fit (null = None)."""
+        def dev(a, dtype):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return torch.from_numpy(a if a.flags.writeable else a.copy()).to(device)
+        self = cls.__new__(cls)
+        self.S, self.ut, self.xcov, self.y = dev(s, np.float64), dev(u_t, np.float32), dev(xcov, np.float64), dev(y, np.float64)
+        self.n, self.p = int(self.S.shape[0]), int(self.xcov.shape[1])
+        self.null = self._planes = self._fv = None
+        return self
+
     def _profile(self, lbd, ml0, reml0) -> NullFit:
         # assoc.py:907-951 `_lmm_profile_exact_vc` + :1845-1876 (host, O(n p^2))
         s = np.maximum(self.S.cpu().numpy(), 0.0)
@@ -479,18 +495,38 @@ def _fused_fixed_lambda(p: int) -> bool:
     return p <= 8 and os.environ.get("JXGPU_FVLMM_FUSED", "1").strip() != "0"
 
 
+def _chain_segments(co, a, b, dev):
+    """The warm-start chains (offsets `co`) that touch the rows [a, b) -> (index of the first one, their offsets relative to a,
+    clipped to [0, b - a], as an int32 device tensor)."""
+    nch = len(co) - 1
+    c0 = min(int(np.searchsorted(co, a, side="right")) - 1, nch - 1)
+    c1 = c0
+    loc = []
+    while c1 < nch and co[c1] < b:
+        loc.append(max(int(co[c1]), a) - a)
+        c1 += 1
+    loc.append(min(int(co[c1]), b) - a)
+    return c0, torch.from_numpy(np.asarray(loc, dtype=np.int32)).to(dev)
+
+
 def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndarray, mode="lmm", low=None,
-              high=None, max_iter=30, tol=1e-2, init_log10_lbd=None, block_rows=8192, return_evals=False,
-              times: StageTimes = None, nullml=None, fv_state=None, on_block=None, chain_off=None):
+              high=None, max_iter=30, tol=1e-2, init_log10_lbd=None, block_rows=None, return_evals=False,
+              times: StageTimes = None, nullml=None, fv_state=None, on_block=None, chain_off=None, progress=None,
+              progress_every=0):
     """Rotate + scan the given SNP rows. mode: 'lmm' (exact per-SNP REML), 'fvlmm' (fixed lambda) or 'lmm2' (REML Wald +
     ML likelihood ratio, needs `nullml`).  Returns a (len(rows), 3) f64 device tensor [beta, se, p] -- 4 columns
     [.., plrt] when `nullml` is given, 6 columns [beta, se, pwald, lambda, ml, plrt] for 'lmm2' -- (and the per-SNP
     Brent evaluation counts).
+    block_rows: rows per rotation block; None = 8192, or 32768 for the exact scan beyond the LDS-resident limit.
     chain_off ('lmm' only): offsets into `rows` (int64, 0 ... len(rows), ascending; `stats.warm_chain_offsets`) of the
     reference's warm-start chains (src/stats/lmm.rs:134-161): inside a chain every SNP's Brent starts from the optimum of the
     valid SNP before it, the first one from `init_log10_lbd` or the interval midpoint.  The rotation and the per-SNP series stay
-    parallel over all SNPs; the Brent searches run one wave per chain -- in ONE launch behind the last block where the series
-    form exists (`on_block` then receives the whole table at the end), block by block with carried states otherwise."""
+    parallel over all SNPs; the Brent searches run one wave per chain -- where the series form exists in ONE launch per
+    super-block (the series of at most SERIES_CAP_BYTES / (8 (series + 1 + columns)) rows, whole blocks, at least one; a chain cut
+    by a super-block continues from its carried state; `on_block` then receives the whole table at the end), block by block with
+    carried states otherwise.
+    progress(done, total): called after a block when `done` has advanced by `progress_every` rows (default: one block) since the
+    last call, and after the last block; an exception raised there ends the scan."""
     dev = panel.device
     n = model.n
     if panel.n != n:
@@ -523,8 +559,8 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
     # rows with a few missing calls keep the exact (int8) rotation and get their missing-call term added behind it
     # (jxg_rotate_missing_correct: d * the sum of the missing samples' rows of U); only where the int8 rotation runs
     # The limit is decided from a statistic of the PANEL (mean missing calls over all its rows, cached), never from the rows of
-    # this call: a row takes the same path -- and gets the same bits -- in chunked, unchunked and rank-sharded scans, and the
-    # host entry point (api.cpp, all rows of the payload) decides the same way.
+    # this call: a row takes the same path -- and gets the same bits -- in chunked, unchunked and rank-sharded scans (the mirror's
+    # packed entry points build their panel from the rows they are handed).
     miss_max = 0
     if qpl is not None:
         miss_max = int(lib().jxg_rot_miss_max(n, panel.mean_missing()))
@@ -558,13 +594,8 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
             co = np.ascontiguousarray(chain_off, dtype=np.int64)
             if co.ndim != 1 or len(co) < 2 or co[0] != 0 or co[-1] != mk or np.any(np.diff(co) < 0):
                 raise RuntimeError("chain_off must ascend from 0 to len(rows)")
-            nch = len(co) - 1
-            carry = torch.full((nch,), init if warm else float("nan"), dtype=torch.float64, device=dev)
+            carry = torch.full((len(co) - 1,), init if warm else float("nan"), dtype=torch.float64, device=dev)
             sd = int(lib().jxg_lmm_series_doubles(model.p, lo_b, hi_b)) if tables is not None else 0
-            if sd > 0:
-                scoef = torch.empty((mk, sd), dtype=torch.float64, device=dev)
-                sssq = torch.empty(mk, dtype=torch.float64, device=dev)
-                co_t = torch.from_numpy(co.astype(np.int32)).to(dev)
     elif mode == "splmm":
         # null state on the K + lambda I scale, formed in f64 by the caller without the 1e-6 ridge jxg_fvlmm_prepare puts
         # on X'WX (fvlmm.rs): at the large lambda of a trait without polygenic signal that ridge is a 1e-4 relative error
@@ -573,10 +604,10 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
     else:
         lbd, w, py, wx, a_chol, ypy, log_det_v, df = model.fv_cache(init_log10_lbd)
         a_dev = torch.from_numpy(a_chol).to(dev)
-    if mode == "lmm" and block_rows == 8192 and (8 * n * (2 + model.p) > 156 * 1024 or model.p + 1 > 4):
+    if block_rows is None:
         # beyond the LDS-resident limit the exact scan runs its tiled form: one workgroup per CU walks a queue of SNPs in
         # lock step over LDS tiles of (s, X~, y~); longer blocks keep every wave's queue deep (8 SNPs per wave)
-        block_rows = 32768
+        block_rows = 32768 if mode == "lmm" and (8 * n * (2 + model.p) > 156 * 1024 or model.p + 1 > 4) else 8192
     br = int(min(block_rows, mk))
     if miss_dense:
         # per block: positions of the rows with a missing-call term (a row's path does not depend on the blocking)
@@ -589,6 +620,11 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
             parts.append(a)
         sel_miss_t = torch.from_numpy(np.concatenate(parts) if nm_ else np.zeros(1, np.int32)).to(dev)
     chain_series = mode == "lmm" and chain_off is not None and sd > 0
+    if chain_series:
+        cap = SERIES_CAP_BYTES // (8 * (sd + 1 + out.shape[1]))
+        sb_rows, sb0 = min(mk, max(br, cap // br * br)), 0     # rows per super-block; first row of the open one
+        scoef = torch.empty((sb_rows, sd), dtype=torch.float64, device=dev)
+        sssq = torch.empty(sb_rows, dtype=torch.float64, device=dev)
     nbuf = 2 if mk > br else 1
     fused = mode in ("fvlmm", "splmm") and _fused_fixed_lambda(model.p) and qpl is None
     if qpl is not None:
@@ -622,6 +658,7 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
     ev_scan = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(len(ev_rot))]
     pending = None          # (i0, i1, event recorded behind the block's scan)
     copy_stream = torch.cuda.Stream(device=dev) if on_block is not None else None
+    step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
 
     def hand_over(item):
         i0, i1, ev = item
@@ -681,22 +718,23 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
         elif mode == "lmm" and chain_off is not None:
             ev_p = evals[r0:].data_ptr() if evals is not None else None
             if sd > 0:
-                # the series of this block; the Brent searches follow behind the last block, all chains in one launch
+                # the series of this block behind those of the open super-block; when it is full or the rows end, its Brent
+                # searches: one launch over the chains that touch it
                 check(lib().jxg_lmm_series_coef_tab(_ptr(grot), nr, n, _ptr(model.xcov), model.p, lo_b, hi_b, _ptr(tables),
-                                                    scoef[r0:].data_ptr(), sssq[r0:].data_ptr(), _stream()))
+                                                    scoef[r0 - sb0:].data_ptr(), sssq[r0 - sb0:].data_ptr(), _stream()))
+                if r0 + nr - sb0 >= sb_rows or r0 + nr >= mk:
+                    c0, loc_t = _chain_segments(co, sb0, r0 + nr, dev)
+                    check(lib().jxg_lmm_series_brent_tab(r0 + nr - sb0, n, _ptr(model.S), _ptr(model.xcov), model.p, lo_b, hi_b,
+                                                         _ptr(tables), float(tol), int(max_iter), 0, 0.0, _ptr(scoef), _ptr(sssq),
+                                                         _ptr(loc_t), len(loc_t) - 1, carry[c0:].data_ptr(), with_plrt, nullml_v,
+                                                         out[sb0:].data_ptr(),
+                                                         evals[sb0:].data_ptr() if evals is not None else None, _stream()))
+                    sb0 = r0 + nr
             else:
                 # no series form (wide bounds, many covariates): the chains that touch this block, states carried across blocks
-                c0 = int(np.searchsorted(co, r0, side="right")) - 1
-                c0 = min(c0, nch - 1)
-                c1 = c0
-                loc = []
-                while c1 < nch and co[c1] < r0 + nr:
-                    loc.append(max(int(co[c1]), r0) - r0)
-                    c1 += 1
-                loc.append(min(int(co[c1]), r0 + nr) - r0)
-                loc_t = torch.from_numpy(np.asarray(loc, dtype=np.int32)).to(dev)
+                c0, loc_t = _chain_segments(co, r0, r0 + nr, dev)
                 check(lib().jxg_lmm_scan_chain(_ptr(grot), nr, n, _ptr(model.S), _ptr(model.xcov), _ptr(model.y), model.p, lo_b,
-                                               hi_b, float(tol), int(max_iter), _ptr(loc_t), c1 - c0, carry[c0:].data_ptr(),
+                                               hi_b, float(tol), int(max_iter), _ptr(loc_t), len(loc_t) - 1, carry[c0:].data_ptr(),
                                                with_plrt, nullml_v, o.data_ptr(), ev_p, _stream()))
         elif mode == "lmm":
             ev_p = evals[r0:].data_ptr() if evals is not None else None
@@ -722,19 +760,13 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
             if pending is not None:
                 hand_over(pending)       # the previous block, while this one runs
             pending = (r0, r0 + nr, done)
-    if chain_series:
-        ev_c = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev_c[0].record()
-        check(lib().jxg_lmm_series_brent_tab(mk, n, _ptr(model.S), _ptr(model.xcov), model.p, lo_b, hi_b, _ptr(tables), float(tol),
-                                             int(max_iter), 0, 0.0, _ptr(scoef), _ptr(sssq), _ptr(co_t), nch, _ptr(carry),
-                                             with_plrt, nullml_v, _ptr(out), _ptr(evals) if evals is not None else None,
-                                             _stream()))
-        ev_c[1].record()
-        ev_scan.append(ev_c)
-        if on_block is not None:
-            done = torch.cuda.Event()
-            done.record()
-            pending = (0, mk, done)
+        if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
+            last_tick = r0 + nr
+            progress(r0 + nr, mk)
+    if chain_series and on_block is not None:
+        done = torch.cuda.Event()
+        done.record()
+        pending = (0, mk, done)
     if pending is not None:
         hand_over(pending)
     if times is not None:
@@ -943,10 +975,13 @@ def scan_rows_grammar(panel: Panel, rows: np.ndarray, lut: np.ndarray, x: np.nda
     return out
 
 
-def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, y: np.ndarray, on_block=None):
+def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, y: np.ndarray, on_block=None, flip=None,
+                 ixx=None, progress=None, progress_every=0):
     """Plain LM scan of the given SNP rows of a resident panel (`lm_block_assoc_packed`, src/stats/glm.rs:3550-3860; the `LM`
-    wrapper python/janusx/pyBLUP/assoc.py:2185-2228): mean-imputed additive decode with the rows' allele frequencies, `x`
-    includes the intercept.  Returns a (len(rows), 4) f64 device tensor [beta, se, pwald (Student t), plrt]."""
+    wrapper python/janusx/pyBLUP/assoc.py:2185-2228): mean-imputed additive decode with the rows' allele frequencies
+    ([0, mean, 1, 2], or [2, mean, 1, 0] where `flip`), `x` includes the intercept, `ixx` = (X'X)^-1 (default: from `x`).
+    One launch per LM_BLOCK_ROWS rows; `progress(done, total)` as in `scan_rows`.  Returns a (len(rows), 4) f64 device tensor
+    [beta, se, pwald (Student t), plrt]."""
     from .janusx import lm_precompute_ixx_qr
     dev = panel.device
     n = panel.n
@@ -959,20 +994,28 @@ def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, 
     out = torch.empty((mk, 4), dtype=torch.float64, device=dev)
     if mk == 0:
         return out
-    ixx = lm_precompute_ixx_qr(x)
+    ixx = lm_precompute_ixx_qr(x) if ixx is None else np.ascontiguousarray(ixx, dtype=np.float64)
     xr = np.empty((n, q0 + 1), dtype=np.float64)
     yy = np.zeros(1, dtype=np.float64)
     check(lib().jx_lm_residualize(y.ctypes.data, x.ctypes.data, ixx.ctypes.data, n, q0, xr.ctypes.data, yy.ctypes.data))
     mean_g = np.clip(np.float32(2.0) * np.asarray(af, dtype=np.float32), np.float32(0.0), np.float32(2.0))
+    fl = np.zeros(mk, dtype=bool) if flip is None else np.asarray(flip, dtype=bool)
     lut = np.zeros((mk, 4), dtype=np.float32)
-    lut[:, 1], lut[:, 2], lut[:, 3] = mean_g, 1.0, 2.0
+    lut[:, 0], lut[:, 1], lut[:, 2], lut[:, 3] = np.where(fl, 2.0, 0.0), mean_g, 1.0, np.where(fl, 0.0, 2.0)
     rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
     lut_t = torch.from_numpy(lut).to(dev)
     xr_t = torch.from_numpy(xr).to(dev)
     ixx_t = torch.from_numpy(ixx).to(dev)
-    work = torch.empty(mk * (q0 + 2), dtype=torch.float64, device=dev)
-    check(lib().jxg_lm_scan_p32(_ptr(panel.p32), panel.m, n, _ptr(rows_t), mk, _ptr(lut_t), _ptr(xr_t), q0, _ptr(ixx_t),
-                                float(yy[0]), _ptr(work), _ptr(out), _stream()))
+    br = min(LM_BLOCK_ROWS, mk)
+    step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
+    work = torch.empty(br * (q0 + 2), dtype=torch.float64, device=dev)
+    for r0 in range(0, mk, br):
+        nr = min(br, mk - r0)
+        check(lib().jxg_lm_scan_p32(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr, lut_t[r0:].data_ptr(), _ptr(xr_t),
+                                    q0, _ptr(ixx_t), float(yy[0]), _ptr(work), out[r0:].data_ptr(), _stream()))
+        if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
+            last_tick = r0 + nr
+            progress(r0 + nr, mk)
     if on_block is not None:
         on_block(0, out[:, :3].cpu().numpy())
     return out

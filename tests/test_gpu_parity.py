@@ -643,7 +643,7 @@ def test_assoc_packed(oracle, oracle_c, null_case):
 def test_scan_exact_design_rows(oracle, oracle_c):
     """Design rows without missing calls are rotated as (c U) + beta * usum (integer LUT, two MFMA products per tile when
     all 128 rows of a tile qualify): a panel without missing genotypes (every tile exact), one with missing calls in
-    a third of the SNPs (mixed tiles), flipped alleles, on the host C-ABI route and the device pipeline route."""
+    a third of the SNPs (mixed tiles), flipped alleles, through the mirror's packed entry point and the device pipeline route."""
     import torch
     from janusx_amd import janusx as jxrs
     from janusx_amd import pipeline, stats
@@ -757,7 +757,8 @@ def test_full_size_rotation_kernels_with_mixed_rows(oracle, oracle_c, monkeypatc
     res_e = pipeline.scan_rows(p, model, rows[ex], lut[ex], mode="lmm", low=lo_b, high=hi_b, max_iter=30, tol=1e-2).cpu().numpy()
     assert lib().jxg_last_kernel_ms(14) == 1.0 and lib().jxg_last_kernel_ms(13) == 1.0
     assert np.array_equal(res_e, res[ex])
-    # the host C-ABI route (`jx_assoc_packed`, 8192-row blocks) deals its rows to the same two kernels: same bits
+    # the mirror's packed entry points (a panel of the rows handed, the caller's rotated model, 8192-row blocks) deal their rows
+    # to the same two kernels: same bits
     from janusx_amd import janusx as jxrs
     s_h, x_h, y_h, ut_h = s_t.cpu().numpy(), model.xcov.cpu().numpy(), model.y.cpu().numpy(), model.ut.cpu().numpy()
     out_h = jxrs.lmm_reml_assoc_packed_f32(np.ascontiguousarray(packed[rows]), n, flip_k, maf[rows], s_h, x_h, y_h, ut_h,
@@ -766,8 +767,7 @@ def test_full_size_rotation_kernels_with_mixed_rows(oracle, oracle_c, monkeypatc
     l10 = math.log10(model.null.lbd)
     fv_h = jxrs.fvlmm_assoc_packed_f32(np.ascontiguousarray(packed[rows]), n, flip_k, maf[rows], s_h, x_h, y_h, ut_h, l10)
     fv_p = pipeline.scan_rows(p, model, rows, lut, mode="fvlmm", init_log10_lbd=l10).cpu().numpy()
-    be, se, pe = _assoc_err(fv_h, fv_p)
-    assert max(be, se, pe) < 1e-9, (be, se, pe)          # same rotated rows; the two routes prepare W / Py on different sides
+    assert np.array_equal(fv_h, fv_p, equal_nan=True)
     # (iii) every row through the fp16 kernels
     monkeypatch.setenv("JXGPU_ROT_I8", "0")
     res_h = pipeline.scan_rows(p, model, rows, lut, mode="lmm", low=lo_b, high=hi_b, max_iter=30, tol=1e-2).cpu().numpy()
@@ -1867,7 +1867,7 @@ def test_exact_scan_with_covariates_block_form(oracle, oracle_c, q):
     u = M X~'Wy~ tabulated as Chebyshev series, no factorisation per evaluation: last pivot, beta_k, log det and r'V^-1 r
     from c'Mc, c'u, u'z, |z|^2) inside the tiled kernel; against the oracle's line-by-line restatement of
     `run_rotated_reml_assoc_block_f32` (src/stats/lmm.rs:94-199, src/stats/reml.rs:255-568) on the same rotated rows, the
-    device pipeline route and the host C-ABI route."""
+    device pipeline route and the mirror's packed entry point."""
     import torch
     from janusx_amd import janusx as jxrs
     from janusx_amd import pipeline, stats
@@ -4180,8 +4180,8 @@ def test_rotation_rows_with_many_missing_calls_stay_exact(oracle, oracle_c, monk
     (`jxg_rotate_missing_dense`, csrc/k_rotate_i8.hip MODE 1) -- the rows took the fp16 hi / lo kernel before, which is noisier
     than the reference's f32 SGEMM.  n = 4300, 5 .. 60 missing calls per SNP (1 % of the calls), flipped alleles: (i) beta / SE
     against the scan of the EXACT (f64) rotation at the int8 path's own bound (1e-6; the fp16 kernel: a few 1e-6); (ii) chunked ==
-    unchunked and host C-ABI route == pipeline bit for bit; (iii) JXGPU_ROT_MISS_DENSE=0 restores the fp16 kernel (other bits,
-    same result within the tolerance)."""
+    unchunked and the mirror's packed entry point == pipeline bit for bit; (iii) JXGPU_ROT_MISS_DENSE=0 restores the fp16 kernel
+    (other bits, same result within the tolerance)."""
     import torch
     from janusx_amd import pipeline, stats
     from janusx_amd._lib import lib
@@ -4241,8 +4241,8 @@ def test_rotation_rows_with_a_few_missing_calls_take_the_exact_path(oracle, orac
     keeps the int8 rotation; its missing-call term d * sum_{i missing} U[i, :] is added behind it (`jxg_lut_split_rows_m`,
     `jxg_rotate_missing_correct`; the decode of src/decode/decode.rs:192-271 puts the centred mean at a missing call).
     n = 4300: 0 .. 7 missing calls per SNP, flipped alleles.  (i) beta / SE / p against the oracle's scan of the f64 rotation;
-    (ii) chunked == unchunked and host C-ABI route == pipeline bit for bit, also with a forced limit of 3 (rows above it on the
-    fp16 kernel); (iii) the switch changes the path, not the result."""
+    (ii) chunked == unchunked and the mirror's packed entry point == pipeline bit for bit, also with a forced limit of 3 (rows
+    above it on the fp16 kernel); (iii) the switch changes the path, not the result."""
     import torch
     from janusx_amd import pipeline, stats
     from janusx_amd._lib import lib

@@ -228,6 +228,39 @@ def test_warm_start_chain_device_pipeline_matches_trajectories(oracle, oracle_c,
         assert same > 0.995, f"only {same:.4f} of the SNPs took the oracle's number of Brent evaluations"
 
 
+def test_warm_start_chain_series_super_blocks(chain_case, monkeypatch):
+    """The chain series of `pipeline.scan_rows` are kept for at most `SERIES_CAP_BYTES` worth of rows (a super-block of whole
+    blocks), one Brent launch per super-block, a chain cut by its end carried into the next.  With the cap lowered so that the
+    kept rows of `chain_case` fall into at least three super-blocks and every cut lies inside a chain: the table (plrt column
+    included) and the per-SNP Brent evaluation counts are bit-identical to the uncapped run (one launch)."""
+    import torch
+    from janusx_amd import pipeline
+    from janusx_amd import stats as st
+    from janusx_amd._lib import lib
+    c = chain_case
+    n, nm, kept = c["n"], c["nm"], c["kept"]
+    dev = torch.device("cuda", 0)
+    panel = pipeline.Panel(torch.from_numpy(c["packed"]).to(dev), n)
+    model = pipeline.SpectralModel(torch.from_numpy(nm.S).to(dev), torch.from_numpy(nm.Dh.astype(np.float64)).to(dev), c["x"],
+                                   c["y"])
+    lut = st.scan_lut_from_counts(c["maf"][kept], np.zeros(len(kept), bool), panel.counts()[kept], n)
+    co = st.warm_chain_offsets(st.warm_chain_blocks_bed(kept, panel.m, 500), len(kept))
+    lo, hi = model.null.bounds
+    sd = int(lib().jxg_lmm_series_doubles(model.p, lo, hi))
+    assert sd > 0                                                  # the series form
+    br, sb = 300, 900
+    kw = dict(low=lo, high=hi, max_iter=30, tol=1e-2, init_log10_lbd=min(max(math.log10(model.null.lbd), lo), hi), block_rows=br,
+              return_evals=True, chain_off=co, nullml=nm.ML0)
+    one, ev_one = pipeline.scan_rows(panel, model, kept, lut, "lmm", **kw)
+    monkeypatch.setattr(pipeline, "SERIES_CAP_BYTES", sb * 8 * (sd + 1 + 4))      # 4 columns: with the plrt column
+    cuts = np.arange(sb, len(kept), sb)
+    assert len(cuts) >= 2 and not np.isin(cuts, co).any(), (cuts, co)
+    split, ev_split = pipeline.scan_rows(panel, model, kept, lut, "lmm", **kw)
+    assert one.shape[1] == 4
+    assert np.array_equal(split.cpu().numpy(), one.cpu().numpy(), equal_nan=True)
+    assert np.array_equal(ev_split.cpu().numpy(), ev_one.cpu().numpy())
+
+
 def test_warm_start_chain_bed_route_tsv_text(oracle, oracle_c, chain_case, tmp_path, monkeypatch):
     """`lmm_reml_assoc_bed_to_tsv_f32` as the reference's workflow calls it (init_log10_lbd = log10 lambda0, rotate_block_rows = the
     chunk size; chain on unless JX_LMM_UNIFIED_NO_WARM_START, src/stats/lmm.rs:2627): the TSV text equals the oracle's rendering of
