@@ -196,3 +196,76 @@ def test_als_stall_rolls_back_like_restatement():
     assert itr < 400 and it < 400                      # the stall branch ended both loops, not max_iter
     assert it == itr
     assert np.allclose(p.numpy(), pr, atol=1e-9) and np.allclose(q.numpy(), qr, atol=1e-9)
+
+
+# ---- the slicing of the EM pass and its work buffer (`ax_grid`, `ax_work_bytes`, csrc/k_admx.hip), restated ----
+
+AX_CAP = 8 << 30
+
+
+def _ax_grid(nrows, n, k):
+    """`ax_grid` of csrc/k_admx.hip restated (tests/test_gpu_admx.py imports this copy)
+    -> (s1, s2, gps, tps): SNP slices, sample slices, groups of 32 rows per slice, 128-sample tiles per slice."""
+    ngroups, ntiles = (nrows + 31) // 32, (n + 127) // 128
+    s1 = min(ngroups, 256)
+    s2 = max(1, min(2048 // max(s1, 1), ntiles))
+    s1 = max(s1, 1)
+    while True:
+        pa, pt = 8 * k * s2 * nrows, 4 * k * s1 * n
+        if pa + pt <= AX_CAP or (s1 == 1 and s2 == 1):
+            break
+        if (pt >= pa and s1 > 1) or s2 == 1:
+            s1 = (s1 + 1) // 2
+        else:
+            s2 = (s2 + 1) // 2
+    gps = (ngroups + s1 - 1) // s1
+    tps = (ntiles + s2 - 1) // s2
+    return max((ngroups + gps - 1) // gps, 1), (ntiles + tps - 1) // tps, gps, tps
+
+
+def _ax_work_bytes(nrows, n, k):
+    if not (1 <= k <= 64 and n >= 1 and nrows >= 1):
+        return 0
+    s1, s2, _gps, _tps = _ax_grid(nrows, n, k)
+    al = lambda b: (b + 255) & ~255
+    return 2 * al(4 * k * s2 * nrows) + al(4 * k * s1 * n) + al(4 * k * n) + al(8 * s1 * s2) + al(4 * n)
+
+
+_AX_SHAPES = [(1, 1), (31, 100), (32, 128), (33, 129), (64, 256), (420, 300), (8200, 1100), (8192, 32768), (65536, 300),
+              (10 ** 6, 200_000), (10 ** 6, 2_000_000), (3 * 10 ** 7, 5000), (5 * 10 ** 7, 1 << 23), (100, 1 << 23),
+              (4 * 10 ** 6, 1_000_000), (250_000, 4_000_000)]
+_AX_K = [1, 2, 3, 4, 5, 8, 10, 16, 17, 32, 33, 63, 64]
+
+
+def test_work_bytes_match_the_restated_grid():
+    from janusx_amd._lib import lib
+    capped = 0
+    for nrows, n in _AX_SHAPES:
+        for k in _AX_K:
+            if k > n:
+                continue
+            assert lib().jxg_admx_work_bytes(nrows, n, k) == _ax_work_bytes(nrows, n, k), (nrows, n, k)
+            s1, s2, gps, tps = _ax_grid(nrows, n, k)
+            ngroups, ntiles = (nrows + 31) // 32, (n + 127) // 128
+            # the slices cover every group and tile, and none is empty
+            assert s1 * gps >= ngroups > (s1 - 1) * gps and s2 * tps >= ntiles > (s2 - 1) * tps, (nrows, n, k)
+            part = 4 * k * (2 * s2 * nrows + s1 * n)
+            assert part <= AX_CAP or (s1 == 1 and s2 == 1), (nrows, n, k, part)
+            full = 4 * k * (2 * min(ntiles, max(1, 2048 // min(ngroups, 256))) * nrows + min(ngroups, 256) * n)
+            capped += full > AX_CAP
+    assert 10 <= capped < len(_AX_SHAPES) * len(_AX_K) - 10         # shapes on both sides of the cap
+    for bad in ((100, 100, 0), (100, 100, 65), (100, 0, 4), (0, 100, 4), (100, 100, -1), (-5, 100, 4)):
+        assert lib().jxg_admx_work_bytes(*bad) == 0 == _ax_work_bytes(*bad), bad
+
+
+def test_design_figures_of_the_partial_memory():
+    """configs[4] (n = 200 000, 10^6 rows) takes 1.08 / 2.69 / 4.30 GB at K = 4 / 10 / 16, and the partial sums stay
+    within 8 GiB at K = 64 (where the slices are halved to fit)."""
+    from janusx_amd._lib import lib
+    n, m = 200_000, 10 ** 6
+    for k, gb in ((4, "1.08"), (10, "2.69"), (16, "4.30")):
+        assert f"{lib().jxg_admx_work_bytes(m, n, k) / 1e9:.2f}" == gb
+        assert _ax_grid(m, n, k)[:2] == (255, 8)
+    s1, s2, _gps, _tps = _ax_grid(m, n, 64)
+    assert (s1, s2) != (255, 8) and 4 * 64 * (2 * s2 * m + s1 * n) <= AX_CAP
+    assert 2048 >= s1 * s2 >= 256                                  # still hundreds of workgroups after the halving

@@ -146,40 +146,256 @@ def _exact(z, varsum, k):
     return ev[::-1][:k], v[:, ::-1][:, :k], float(np.trace(kk))
 
 
+# ---- the two skinny products against the bound their digit form gives ---------------------------------------------------------
+#
+# A column x of the dense block is written as xmax (q1/127 + q2/(127 254) + q3/(127 254^2) + q4/(127 254^3)) with the residual
+# after four digits at most half a unit of the last one: |x / xmax - digits| <= RS_D.  Every integer plane sum is exact, so in
+# exact arithmetic
+#     |W[r][c] - (Z Q)[r][c]|  <= RS_D qmax_c sum_i |z_ri|
+#     |Y[i][c] - (Z' W)[i][c]| <= RS_D (umax_c sum_r G_ri + vmax_c sum_r M_ri),     u = b W, v = a W
+# (G the 0 / 1 / 2 dose plane of the stored code, M the missing plane).  What is left is float64 rounding: of the numpy reference
+# (a sum of N products: N 2^-53 sum |terms|), of the kernel's merge of its exact sums (a dozen operations on terms no larger than
+# the ones below) and, for Z' W, of the column constant sum_r a_r W_rc (N terms again), together under (N + 64) 2^-52 sum |terms|:
+#     Z Q:  terms = |a_r| (sum_i |q_ic| + sum_i M_ri |q_ic|) + |b_r| sum_i G_ri |q_ic|
+#     Z' W: terms = sum_r |v_rc| + sum_r G_ri |u_rc| + sum_r M_ri |v_rc|
+# which dominate sum |z| |q| resp. sum |z| |w| of the reference.  A column whose entries are exact four-digit numbers of its
+# maximum (`_exact_digit_block`) has no residual: there the bound is the rounding term alone.
+RS_D = 0.5 / (127.0 * 254.0 ** 3)
+RS_KP = [1, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64]                   # both sides of every rs_nt step and of the 32-column pass
+
+
+# The launch arithmetic of csrc/k_rsvd.hip restated: `rs_nt` (columns per pass / 4), the constexpr ST of `rs_main` (record tiles
+# per LDS stage) and the slices / tps block of `jxg_packed_tmm_cols`.  The library exports none of them, so a change there has
+# to be carried over here by hand; the shape assertions of the two edge tests then say which case lost its property.
+def _rs_nt(kp):
+    return 1 if kp <= 4 else 2 if kp <= 8 else 4 if kp <= 16 else 8
+
+
+def _rs_st(kp, nv):
+    """LDS stage length in record tiles (`rs_main`: ST) for Z Q (nv = 1) and Z' W (nv = 2)."""
+    return min(8, max(1, 256 // (16 * _rs_nt(kp) * nv)))
+
+
+def _rs_slices(n, nrows, kp):
+    """-> (nst, slices, tps) of `jxg_packed_tmm_cols`."""
+    cpp = 4 * _rs_nt(kp)
+    ncb = (kp + cpp - 1) // cpp
+    nst = (nrows + 127) // 128
+    gx = (n + 255) // 256
+    slices = max(1, min((1024 + gx * ncb - 1) // (gx * ncb), 64, nst))
+    tps = min((nst + slices - 1) // slices, (1 << 23) // 128)
+    return nst, (nst + tps - 1) // tps, tps
+
+
+def _scales(kp):
+    """Column scales over 300 decades, the two extremes in columns 0 and 2 (every block of three or more columns has both)."""
+    order = [0, 31, 63] + [i for i in range(64) if i not in (0, 31, 63)]
+    return (10.0 ** np.linspace(-150.0, 150.0, 64))[order][:kp]
+
+
+def _gauss_block(rng, rows, kp):
+    x = rng.standard_normal((rows, kp)) * _scales(kp)[None, :]
+    if kp >= 3:
+        x[:, 1] = 0.0                                             # a column of zeros between live columns
+    return x
+
+
+def _exact_digit_block(rng, rows, kp, top_row=0):
+    """Columns x = s (q1/127 + q2/(127 254) + q3/(127 254^2) + q4/(127 254^3)) with integer digits in [-126, 126] and the
+    entry of row `top_row` at digits (+-127, 0, 0, 0): the column maximum is exactly s and `rs_digits` recovers every digit."""
+    dg = rng.integers(-126, 127, (rows, kp, 4)).astype(np.float64)
+    dg[top_row] = 0.0
+    dg[top_row, :, 0] = 127.0 * np.where(np.arange(kp) % 2 == 0, 1.0, -1.0)
+    t = (((dg[..., 3] / 254.0 + dg[..., 2]) / 254.0 + dg[..., 1]) / 254.0 + dg[..., 0]) / 127.0
+    x = t * _scales(kp)[None, :]
+    if kp >= 3:
+        x[:, 1] = 0.0
+    return x
+
+
+def _assert_within(err, bound, tag):
+    ok = err <= bound                                             # False for a NaN error
+    worst = float(np.max(err[~ok] / np.maximum(bound[~ok], np.finfo(np.float64).tiny))) if not ok.all() else 0.0
+    assert ok.all(), (tag, "error / bound", worst)
+
+
+class _Case:
+    """One panel, row list and (a, b), with the float64 design z of the listed rows and their codes (for the planes G, M)."""
+
+    def __init__(self, g, rows, ab):
+        import torch
+        from janusx_amd import janusx as jxrs
+        from janusx_amd import pipeline as pl
+        self.dev = torch.device("cuda", 0)
+        self.n, self.nrows, self.ab = g.shape[1], len(rows), ab
+        self.gr = np.ascontiguousarray(g[rows])
+        self._gm = None
+        self.z = np.where(self.gr >= 0, ab[:, :1] + ab[:, 1:] * np.maximum(self.gr, 0), 0.0)
+        panel = pl.Panel(torch.from_numpy(bed.pack_dosage(g)).to(self.dev), self.n)
+        self.op = jxrs._RsvdOperator(panel, np.asarray(rows, dtype=np.int32), ab)
+
+    def _planes(self):
+        """G and M as float64: kept for a small case, rebuilt per check for a large one (2 x 168 MB at 70 000 x 300)."""
+        if self._gm is not None:
+            return self._gm
+        gm = np.maximum(self.gr, 0).astype(np.float64), (self.gr < 0).astype(np.float64)
+        if self.gr.size <= 1 << 22:
+            self._gm = gm
+        return gm
+
+    def check_zq(self, q, exact, tag):
+        import torch
+        qt = torch.from_numpy(np.ascontiguousarray(q)).to(self.dev)
+        w = self.op.zq(qt)
+        assert torch.equal(w, self.op.zq(qt)), tag                # two runs, the same bits
+        gp, mp = self._planes()
+        aq = np.abs(q)
+        a, b = np.abs(self.ab[:, :1]), np.abs(self.ab[:, 1:])
+        bound = (self.n + 64) * 2.0 ** -52 * (a * (aq.sum(0)[None, :] + mp @ aq) + b * (gp @ aq))
+        if not exact:
+            bound = bound + RS_D * aq.max(0)[None, :] * np.abs(self.z).sum(1)[:, None]
+        _assert_within(np.abs(w.cpu().numpy() - self.z @ q), bound, tag)
+
+    def check_ztw(self, w, exact, tag):
+        import torch
+        wt = torch.from_numpy(np.ascontiguousarray(w)).to(self.dev)
+        y = self.op.ztw(wt)
+        assert torch.equal(y, self.op.ztw(wt)), tag               # the fixed-order merge of the slices
+        gp, mp = self._planes()
+        u, v = np.abs(w * self.ab[:, 1:]), np.abs(w * self.ab[:, :1])
+        bound = (self.nrows + 64) * 2.0 ** -52 * (v.sum(0)[None, :] + gp.T @ u + mp.T @ v)
+        if not exact:
+            bound = bound + RS_D * (u.max(0)[None, :] * gp.sum(0)[:, None] + v.max(0)[None, :] * mp.sum(0)[:, None])
+        _assert_within(np.abs(y.cpu().numpy() - self.z.T @ w), bound, tag)
+
+
+def _edge_dosage(n, m, seed):
+    """2 % missing; row 5 monomorphic, row 6 all missing, sample 3 all missing (where the panel has them)."""
+    g = _panel_dosage(n, m, 0.02, seed=seed)
+    if m > 6:
+        g[5] = 0
+        g[6] = -1
+    if n > 3:
+        g[:, 3] = -1
+    return g
+
+
+def _descending_rows(m, nrows):
+    """The lowest `nrows` of m rows in descending order (m_total != nrows; rows 5 and 6 are listed from 7 rows on)."""
+    assert nrows < m
+    return np.arange(nrows - 1, -1, -1)
+
+
+def _real_case(n, m, nrows, seed):
+    """The GRM method-1 design (a = -2 maf, b = 1; a = 2 - 2 maf, b = -1 on a flipped row; a = 0 on rows 5 and 6)."""
+    from janusx_amd.janusx import _rsvd_row_design
+    g = _edge_dosage(n, m, seed)
+    _z, maf, flip, _ = _design(g)
+    rows = _descending_rows(m, nrows)
+    case = _Case(g, rows, _rsvd_row_design(maf[rows], flip[rows]))
+    assert np.array_equal(case.z, _z[rows])                       # the design restated in `_design`, not the one under test
+    return case
+
+
+def _synthetic_case(n, m, nrows, seed):
+    """A synthetic (a, b): a = +-0.8125 or 0, b = +-1.  With an exact-digit W both images of Z' W, u = b W and v = a W, are
+    then exact-digit columns (v_rc = a_r w_rc is the kernel's own product; its maximum sits on row 0, where a != 0)."""
+    g = _edge_dosage(n, m, seed)
+    rng = np.random.default_rng(seed + 1)
+    ab = np.empty((nrows, 2))
+    ab[:, 1] = np.where(rng.random(nrows) < 0.3, -1.0, 1.0)
+    ab[:, 0] = 0.8125 * np.where(rng.random(nrows) < 0.5, -1.0, 1.0)
+    if nrows >= 4:
+        ab[1::7, 0] = 0.0                                         # a = 0 rows
+    return _Case(g, _descending_rows(m, nrows), ab)
+
+
 def test_products_match_numpy_for_several_widths():
-    import torch
-    from janusx_amd import pipeline as pl
-    from janusx_amd._lib import check, lib
+    """The shape this test has always had (n = 700, 777 of 900 rows in random order), held to the digit bound."""
     from janusx_amd.janusx import _rsvd_row_design
     rng = np.random.default_rng(3)
     n, m = 700, 900
     g = _panel_dosage(n, m, 0.02, seed=11)
     g[5] = 0
     g[6] = -1                                                     # monomorphic and all-missing rows
-    z, maf, flip, _ = _design(g)
-    dev = torch.device("cuda", 0)
-    panel = pl.Panel(torch.from_numpy(bed.pack_dosage(g)).to(dev), n)
+    _z, maf, flip, _ = _design(g)
     rows = rng.permutation(m)[:777].astype(np.int32)
-    ab = torch.from_numpy(_rsvd_row_design(maf[rows], flip[rows])).to(dev)
-    rows_t = torch.from_numpy(rows).to(dev)
-    zr = z[rows]
-    t32 = torch.empty(int(lib().jxg_t32_bytes(n, len(rows))), dtype=torch.uint8, device=dev)
-    check(lib().jxg_p32_transpose(panel.p32.data_ptr(), m, n, rows_t.data_ptr(), len(rows), t32.data_ptr(), pl._stream()))
+    case = _Case(g, rows, _rsvd_row_design(maf[rows], flip[rows]))
+    assert np.array_equal(case.z, _z[rows])                       # the design restated in `_design`, not the one under test
     for kp in (1, 5, 16, 33, 64):
-        q = rng.standard_normal((n, kp)) * np.logspace(0, 3, kp)[None, :]
-        w = torch.empty((len(rows), kp), dtype=torch.float64, device=dev)
-        check(lib().jxg_packed_mm_cols(panel.p32.data_ptr(), m, n, rows_t.data_ptr(), len(rows), ab.data_ptr(),
-                                       torch.from_numpy(q).to(dev).data_ptr(), kp, w.data_ptr(), pl._stream()))
-        ref = zr @ q
-        err = np.abs(w.cpu().numpy() - ref) / np.abs(ref).max(axis=0)[None, :]
-        assert err.max() <= 1e-6, kp
-        wt = rng.standard_normal((len(rows), kp))
-        y = torch.empty((n, kp), dtype=torch.float64, device=dev)
-        check(lib().jxg_packed_tmm_cols(t32.data_ptr(), n, len(rows), ab.data_ptr(), torch.from_numpy(wt).to(dev).data_ptr(),
-                                        kp, y.data_ptr(), pl._stream()))
-        ref = zr.T @ wt
-        err = np.abs(y.cpu().numpy() - ref) / np.abs(ref).max(axis=0)[None, :]
-        assert err.max() <= 1e-6, kp
+        case.check_zq(rng.standard_normal((n, kp)) * np.logspace(0, 3, kp)[None, :], False, ("zq", kp))
+        case.check_ztw(rng.standard_normal((len(rows), kp)), False, ("ztw", kp))
+
+
+@pytest.mark.parametrize("n,m,nrows", [(130, 300, 257), (5000, 1100, 1000), (20000, 700, 600)])
+def test_products_hold_the_digit_bound_and_exact_digit_columns(n, m, nrows):
+    """Gaussian columns over 300 decades to the four-digit bound, exact-digit columns to float64 rounding alone."""
+    rng = np.random.default_rng(n)
+    real, syn = _real_case(n, m, nrows, 21), _synthetic_case(n, m, nrows, 22)
+    for kp in (3, 16, 40):
+        real.check_zq(_gauss_block(rng, n, kp), False, ("zq gauss", kp))
+        real.check_ztw(_gauss_block(rng, nrows, kp), False, ("ztw gauss", kp))
+        real.check_zq(_exact_digit_block(rng, n, kp, top_row=n - 1), True, ("zq exact", kp))
+        syn.check_zq(_exact_digit_block(rng, n, kp), True, ("zq exact, synthetic ab", kp))
+        syn.check_ztw(_exact_digit_block(rng, nrows, kp), True, ("ztw exact", kp))
+        syn.check_ztw(_gauss_block(rng, nrows, kp), False, ("ztw gauss, synthetic ab", kp))
+
+
+_CASES = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_cases():
+    """The cached cases (host planes, P32 / T32 images) live for this module only."""
+    yield
+    _CASES.clear()
+
+
+def _cached(key, make):
+    if key not in _CASES:
+        _CASES[key] = make()
+    return _CASES[key]
+
+
+@pytest.mark.parametrize("kp", RS_KP)
+def test_zq_through_its_stage_edges(kp):
+    """Z Q at sample counts below, at and above one tile, and at 11 tiles: two or more LDS stages with a ragged last one for
+    every stage length, a last tile of 21 samples."""
+    st = _rs_st(kp, 1)
+    assert st == {1: 8, 2: 8, 4: 4, 8: 2}[_rs_nt(kp)]
+    for n in (100, 128, 129, 1301):
+        tiles = (n + 127) // 128
+        if n == 1301:
+            assert tiles == 11 and tiles > st and tiles % st != 0 and n % 128 == 21 and n % 16 != 0
+        real = _cached(("zq real", n), lambda: _real_case(n, 400, 333, 31))
+        syn = _cached(("zq syn", n), lambda: _synthetic_case(n, 400, 333, 32))
+        rng = np.random.default_rng(1000 * n + kp)
+        real.check_zq(_gauss_block(rng, n, kp), False, ("gauss", n, kp))
+        real.check_zq(_exact_digit_block(rng, n, kp, top_row=n - 1), True, ("exact", n, kp))
+        syn.check_zq(_exact_digit_block(rng, n, kp), True, ("exact, synthetic ab", n, kp))
+
+
+@pytest.mark.parametrize("kp", RS_KP)
+def test_ztw_through_its_slice_edges(kp):
+    """Z' W with one slice (1, 127, 128 rows), two slices of one tile (129 rows) and 70 000 rows x 300 samples: 61 slices of
+    9 tiles, longer than the longest LDS stage, the last slice of 7."""
+    n = 300
+    st = _rs_st(kp, 2)
+    assert st == {1: 8, 2: 4, 4: 2, 8: 1}[_rs_nt(kp)]
+    for nrows in (1, 127, 128, 129, 70000):
+        nst, slices, tps = _rs_slices(n, nrows, kp)
+        if nrows <= 128:
+            assert (nst, slices, tps) == (1, 1, 1)
+        elif nrows == 129:
+            assert (nst, slices, tps) == (2, 2, 1)
+        else:
+            assert (nst, slices, tps) == (547, 61, 9) and tps > st and nst - (slices - 1) * tps == 7
+        real = _cached(("ztw real", nrows), lambda: _real_case(n, nrows + 13, nrows, 41))
+        syn = _cached(("ztw syn", nrows), lambda: _synthetic_case(n, nrows + 13, nrows, 42))
+        rng = np.random.default_rng(1000 * nrows + kp)
+        real.check_ztw(_gauss_block(rng, nrows, kp), False, ("gauss", nrows, kp))
+        syn.check_ztw(_exact_digit_block(rng, nrows, kp), True, ("exact", nrows, kp))
+        syn.check_ztw(_gauss_block(rng, nrows, kp), False, ("gauss, synthetic ab", nrows, kp))
 
 
 def test_rsvd_packed_subset_parity_with_restatement():

@@ -38,6 +38,21 @@ def test_rsvd_omega_is_a_deterministic_standard_normal():
     assert abs(a.mean()) < 0.01 and abs(a.std() - 1.0) < 0.01
 
 
+def test_product_entry_points_refuse_before_any_device_work():
+    """`jxg_packed_mm_cols` / `jxg_packed_tmm_cols` check kp and the sample count (exact i32 plane sums up to 2^23 samples)
+    before they touch a pointer or the device: called here with null pointers on a machine without a GPU."""
+    from janusx_amd._lib import check, lib
+    with pytest.raises(RuntimeError, match=r"jxg_packed_mm_cols: kp must be >= 1"):
+        check(lib().jxg_packed_mm_cols(None, 10, 10, None, 10, None, None, 0, None, None))
+    with pytest.raises(RuntimeError, match=r"jxg_packed_tmm_cols: kp must be >= 1"):
+        check(lib().jxg_packed_tmm_cols(None, 10, 10, None, None, 0, None, None))
+    with pytest.raises(RuntimeError, match=r"jxg_packed_mm_cols: at most 8 388 608 samples \(exact i32 plane sums\)"):
+        check(lib().jxg_packed_mm_cols(None, 10, (1 << 23) + 1, None, 10, None, None, 1, None, None))
+    # an empty row list or panel is a no-op at the limit itself, not a refusal
+    assert lib().jxg_packed_mm_cols(None, 10, 1 << 23, None, 0, None, None, 1, None, None) == 0
+    assert lib().jxg_packed_tmm_cols(None, 0, 10, None, None, 1, None, None) == 0
+
+
 def test_admx_rsvd_refuses_out_of_range_thresholds(tmp_path):
     from janusx_amd.janusx import admx_rsvd_stream_sample
     prefix = _tiny_bed(tmp_path)
