@@ -720,6 +720,36 @@ int jxg_sps_solve_multi(int n, const int64_t *d_rowptr, const int32_t *d_col, co
 int jxg_sps_scan_sums(int n, const double *d_g, const double *d_z, int nrhs, int ldr, const double *d_py, const double *d_vinvx,
                       int p, double *d_sums, double *d_work, void *stream);
 
+/* ---- LD pruning and LD-block r^2 on the packed genotypes (csrc/k_ld.hip; `bed_packed_ld_prune_maf_priority`, src/stats/ld.rs:4245-4361
+ * with the strict greedy of :270-402, and `bed_ldblock_r2_rust`, :4721-4811).  A banded SNP x SNP Gram of the P32 image over the
+ * samples on the int8 matrix pipes gives, per pair, the integer sums D = sum g_i g_j, N = sum v_i v_j, S_i = sum g_i v_j,
+ * S_j = sum v_i g_j, Q_i = sum g_i^2 v_j, Q_j = sum v_i g_j^2 (g dosage with 0 at a missing call, v called indicator).
+ * Rows are addressed by "position" p in a row list d_rows (nrows records of the image; NULL = records 0 .. nrows - 1).
+ *   jx_ld_window_ends    : host.  Chromosome-grouped order of the file rows (order[p] = row, groups chrom_off[0 .. *n_chrom], m + 1
+ *                          slots), the reference's window end win_end[p] of the window that starts at position p (0: none starts
+ *                          there) for a base-pair window (window_bp > 0; it wins) or a variant-count window, and band_end[p] =
+ *                          the largest end over the windows that contain p.
+ *   jxg_ld_band_mask_p32 : bit (j - i - 1) of row i - r0 of d_mask ((r1 - r0) rows of wpr 32-bit words) = pair (i, j) is in LD
+ *                          (r^2 finite and > r2_threshold (1 + 1e-12)) for i in [r0, r1), i < j < min(band_end[i], i + 1 + 32 wpr);
+ *                          r^2 in f64 in the reference's operation order from the sums and the per-position d_mean, d_std,
+ *                          d_hasmiss (row statistics of src/stats/ld.rs:469-543, computed by the caller from the row counts).
+ *   jx_ld_prune_greedy   : host, no GPU call.  The strict greedy over the windows that start in [ws0, ws1), reading such a mask
+ *                          of the rows [r0, r1); first_unchecked (start: p + 1) and dropped (start: 0) carry the state from range
+ *                          to range.
+ *   jxg_ld_sums_p32      : d_sums (6, i1 - i0, j1 - j0) int32 = D, N, S_i, S_j, Q_i, Q_j of the pairs i in [i0, i1), j in [j0, j1).
+ * n <= 2^24 samples (exact i32 sums and exact f64 products of two of them). */
+int jx_ld_window_ends(const int32_t *chrom_codes, const int64_t *positions, int64_t m, int64_t window_bp,
+                      int64_t window_variants, int64_t step_variants, int64_t *order, int64_t *chrom_off, int64_t *n_chrom,
+                      int64_t *win_end, int64_t *band_end);
+int jx_ld_prune_greedy(const double *maf, int64_t nrows, const int64_t *chrom_off, int64_t n_chrom, const int64_t *win_end,
+                       int64_t ws0, int64_t ws1, const uint32_t *mask, int64_t r0, int64_t r1, int64_t wpr,
+                       int64_t *first_unchecked, uint8_t *dropped);
+int jxg_ld_band_mask_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int r0, int r1,
+                         const int32_t *d_band_end, const double *d_mean, const double *d_std, const uint8_t *d_hasmiss,
+                         double r2_threshold, int wpr, uint32_t *d_mask, void *stream);
+int jxg_ld_sums_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int i0, int i1, int j0,
+                    int j1, int32_t *d_sums, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

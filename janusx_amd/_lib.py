@@ -158,6 +158,10 @@ SIGNATURES = {
     "jxg_lut_split_rows_m": [c_p, c_l, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_p],
     "jxg_transpose_f32": [c_p, c_i, c_p, c_p],
     "jxg_rotate_missing_correct": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_l, c_p],
+    "jx_ld_window_ends": [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_p],
+    "jx_ld_prune_greedy": [c_p, c_l, c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_p],
+    "jxg_ld_band_mask_p32": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_p],
+    "jxg_ld_sums_p32": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

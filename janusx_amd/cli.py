@@ -9,6 +9,7 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
                                  [-solver adam-em|adam|auto] [-max-iter 500] [-check 5] [-tol 1e-5] [-snps-only]  (fastpop: same)
+  python -m janusx_amd gformat -bfile PREFIX -prune WINDOW STEP R2 [-o OUT | -o DIR/ -prefix NAME]   (LD pruning; WINDOW: 50, 500kb, 100bp)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
@@ -857,6 +858,116 @@ def _write_pca(out, ids, eigvec, eigval, dim, total_variance=None):
     np.savetxt(f"{out}.eigenval", np.column_stack([ev, ratio]), fmt=["%.8f", "%.8f"], delimiter="\t")
 
 
+_PRUNE_UNITS = (("kb", 1000.0, " (kb)"), ("bp", 1.0, " (bp)"))   # suffix of a physical window, base pairs per unit, error tag
+
+
+def _parse_prune_window(token):
+    """WINDOW of `-prune` -> (window_variants, window_bp), one of them None.  Behaviour and messages of the reference's parser
+    (python/janusx/script/gformat.py:617-641): case and blanks are ignored; `kb` / `bp` suffixes give a physical window in base
+    pairs, rounded and at least 1; a bare number is a variant count and must be a whole number."""
+    text = str(token).strip().lower()
+    if not text:
+        raise ValueError("Empty prune window token.")
+    for suffix, scale, tag in _PRUNE_UNITS:
+        if text.endswith(suffix):
+            size = float(text[:-len(suffix)].strip())
+            if not (np.isfinite(size) and size > 0):
+                raise ValueError(f"Invalid prune window{tag}: {token}")
+            return None, max(1, int(round(size * scale)))
+    count = float(text)
+    if not (np.isfinite(count) and count > 0):
+        raise ValueError(f"Invalid prune window: {token}")
+    whole = int(round(count))
+    if abs(count - whole) > 1e-9:
+        raise ValueError(f"Invalid prune window: {token}. Use an integer variant count, "
+                         "or add kb/bp suffix for a physical window.")
+    return max(1, whole), None
+
+
+def _parse_prune_args(values):
+    """`-prune WINDOW STEP R2` -> (window_variants, window_bp, step_variants, r2_threshold); None when the flag is absent.
+    Behaviour and messages of python/janusx/script/gformat.py:644-664: STEP is a number truncated to an integer > 0, R2 a finite
+    number in (0, 1]."""
+    if values is None:
+        return None
+    if len(values) != 3:
+        raise ValueError("Invalid --prune usage. Expected 3 values: "
+                         "--prune <window size['kb']> <step size (variant ct)> <r^2 threshold>")
+    window, step_text, r2_text = values
+    variants, bp = _parse_prune_window(window)
+    step = int(float(str(step_text).strip()))
+    if step < 1:
+        raise ValueError(f"--prune step must be > 0, got {step_text!r}")
+    r2 = float(str(r2_text).strip())
+    if not (np.isfinite(r2) and 0.0 < r2 <= 1.0):
+        raise ValueError(f"--prune r^2 threshold must be in (0, 1], got {r2_text!r}")
+    return variants, bp, step, r2
+
+
+def _prune_chrom_codes(chroms):
+    """Consecutive integers by first appearance of the `.bim` chromosome string (python/janusx/script/gformat.py:1509-1519)."""
+    codes, out = {}, np.zeros(len(chroms), dtype=np.int32)
+    for i, c in enumerate(chroms):
+        out[i] = codes.setdefault(str(c), len(codes))
+    return out
+
+
+def cmd_gformat(args):
+    """`jx gformat -bfile PREFIX -prune WINDOW STEP R2` (python/janusx/script/gformat.py:1456-1546, 2563-2575): LD pruning with MAF
+    priority (`bed_packed_ld_prune_maf_priority`) and the pruned PLINK set written beside the project's other outputs.  The other
+    conversions and filters of the reference's gformat, and its external-PLINK backend, are not built."""
+    for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"gformat: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    for flag, what in (("format", "-fmt"), ("maf", "-maf"), ("geno", "-geno"), ("het", "-het"), ("keep", "-keep"),
+                       ("extract", "-extract"), ("snps_only", "-snps-only"), ("biallelic_only", "-biallelic-only"),
+                       ("snp_name", "-snp-name"), ("chr", "-chr"), ("from_bp", "-from-bp"), ("to_bp", "-to-bp")):
+        if getattr(args, flag, None) not in (None, False):
+            raise SystemExit(f"gformat: {what} (format conversion and site / sample filters) is out of scope on this build; "
+                             "only -bfile PREFIX -prune WINDOW STEP R2 is built")
+    if os.environ.get("JX_LD_PRUNE_BACKEND", "").strip().lower() in ("plink", "plink-external", "external-plink"):
+        raise SystemExit("gformat: the external PLINK prune backend (JX_LD_PRUNE_BACKEND) is out of scope on this build")
+    if not args.bfile:
+        raise SystemExit("gformat needs -bfile PREFIX")
+    try:
+        spec = _parse_prune_args(args.prune)
+    except ValueError as e:
+        raise SystemExit(f"gformat: {e}") from None
+    if spec is None:
+        raise SystemExit("gformat: only LD pruning is built; give -prune WINDOW STEP R2")
+    w_var, w_bp, step, r2 = spec
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    from . import janusx as jxrs
+    from .bed import Bim, read_bed_payload, read_fam_ids, write_bed
+    src = jxrs._bed_prefix(args.bfile)
+    out = _resolve_out(args, src)
+    if os.path.abspath(out) == os.path.abspath(src):
+        raise SystemExit(f"gformat: the output prefix {out} is the input; give another with -o / -prefix")
+    t0 = time.perf_counter()
+    packed, n, bim = read_bed_payload(src)
+    packed = np.ascontiguousarray(packed)
+    keep = jxrs.bed_packed_ld_prune_maf_priority(packed, n, _prune_chrom_codes(bim.chrom), np.asarray(bim.pos, dtype=np.int64),
+                                                 window_bp=w_bp, window_variants=w_var, step_variants=step, r2_threshold=r2)
+    rows = np.nonzero(keep)[0]
+    with open(f"{src}.bim") as fh:
+        bim_lines = [ln for ln in fh if len(ln.split()) >= 6]    # the rows `read_bim` keeps
+    if len(bim_lines) != len(keep):
+        raise SystemExit(f"gformat: {src}.bim has {len(bim_lines)} variant lines, the keep mask {len(keep)} rows")
+    pick = lambda col: [col[i] for i in rows]   # noqa: E731
+    write_bed(out, packed[rows], read_fam_ids(src), Bim(pick(bim.chrom), pick(bim.snp), pick(bim.pos), pick(bim.a0), pick(bim.a1)))
+    # `write_bed` makes the .fam from ids alone and the .bim with a zero map distance: put the input's own lines back
+    with open(f"{out}.bim", "w") as fh:
+        fh.writelines(bim_lines[i] for i in rows)
+    with open(f"{src}.fam") as fi, open(f"{out}.fam", "w") as fo:
+        fo.write(fi.read())
+    window = f"{w_bp}bp" if w_bp is not None else f"{w_var} variants"
+    print(f"gformat: LD prune window={window}, step={step}, r2={r2:.4f}: kept {len(rows)} / {len(keep)} variants "
+          f"({time.perf_counter() - t0:.2f} s) -> {out}.bed/.bim/.fam")
+    return 0
+
+
 def cmd_pca(args):
     """`jx pca` (python/janusx/script/pca.py:1134-1265): -bfile -> method-1 GRM with QC and its eigendecomposition, or with -rsvd
     the randomized SVD of the genotypes (`admx_rsvd_stream_sample`); -k -> eigendecomposition of a GRM file."""
@@ -1216,6 +1327,24 @@ def main(argv=None):
     c.set_defaults(func=cmd_pca)
     _add_admixture_parser(sub, "adamixture")
     _add_admixture_parser(sub, "fastpop")
+    f = sub.add_parser("gformat")
+    f.add_argument("-bfile", "--bfile", default=None)
+    f.add_argument("-prune", "--prune", nargs=3, default=None, metavar=("WINDOW", "STEP", "R2"),
+                   help="LD prune with MAF priority: window (variant count, or with a kb / bp suffix), step (variants), r^2")
+    f.add_argument("-o", "--out", default=None)
+    f.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
+    f.add_argument("-t", "--thread", "--threads", dest="thread", type=int, default=0, help="accepted for compatibility; unused")
+    for flag in ("vcf", "hmp", "file", "keep", "extract", "snp-name", "chr"):
+        f.add_argument(f"-{flag}", f"--{flag}", dest=flag.replace("-", "_"), default=None, help=argparse.SUPPRESS)
+    f.add_argument("-fmt", "--fmt", dest="format", default=None, help=argparse.SUPPRESS)
+    for flag in ("maf", "geno", "het"):
+        f.add_argument(f"-{flag}", f"--{flag}", type=float, default=None, help=argparse.SUPPRESS)
+    for flag in ("from-bp", "to-bp"):
+        f.add_argument(f"-{flag}", f"--{flag}", dest=flag.replace("-", "_"), type=int, default=None, help=argparse.SUPPRESS)
+    for flag in ("snps-only", "biallelic-only"):
+        f.add_argument(f"-{flag}", f"--{flag}", dest=flag.replace("-", "_"), action="store_true", default=False,
+                       help=argparse.SUPPRESS)
+    f.set_defaults(func=cmd_gformat)
     args = ap.parse_args(argv)
     return args.func(args)
 

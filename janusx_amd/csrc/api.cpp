@@ -1116,3 +1116,164 @@ extern "C" int64_t jx_assoc_tsv_append(const char *path, const char *prefix_blob
     }
     return rows;
 }
+
+// ---- LD pruning, host half (src/stats/ld.rs:270-402, 545-549): windows and the strict greedy.  No GPU call.
+//
+// Rows are put in chromosome-grouped order (groups by first appearance of the code, file order inside a group), so that a
+// chromosome is a contiguous range of "positions" p and every window is a range [p, win_end[p]) of them; all indices below are
+// such positions.  order[p] = file row.  chrom_off[0 .. *n_chrom] bounds the groups.  win_end[p] = end (exclusive) of the window
+// that starts at p, 0 where the reference starts none (p is not a multiple of the step inside its chromosome, lies behind the
+// window whose end reached the chromosome's last row, or the chromosome has one row).  band_end[p] = the largest window end
+// over the windows that contain p (p + 1 where none does).
+//
+// Why band_end bounds every pair the greedy can ask for: the greedy evaluates a pair (li, lj) only inside one window, with
+// bs <= li < lj < end of that window.  That window contains li, so lj < end <= band_end[li].  Within a chromosome the windows
+// are visited with growing start, so the largest end over the windows that start at or before p is a running maximum; if it
+// exceeds p, the window that attains it starts at or before p and ends behind p, so it contains p and the maximum is band_end[p].
+extern "C" int jx_ld_window_ends(const int32_t *chrom_codes, const int64_t *positions, int64_t m, int64_t window_bp,
+                                 int64_t window_variants, int64_t step_variants, int64_t *order, int64_t *chrom_off, int64_t *n_chrom,
+                                 int64_t *win_end, int64_t *band_end) {
+    if (m < 0) return fail("jx_ld_window_ends: m must be >= 0");
+    if (step_variants <= 0) return fail("step_variants must be > 0");
+    if (window_bp <= 0 && window_variants <= 0) return fail("provide one of window_bp or window_variants");
+    const bool use_bp = window_bp > 0;                        // the bp window wins when both are given
+    // groups by first appearance
+    std::vector<int32_t> codes;                               // code of group g
+    std::vector<int64_t> group((size_t)m), count;
+    {
+        std::vector<std::pair<int32_t, int64_t>> seen;        // sorted (code, group)
+        for (int64_t i = 0; i < m; ++i) {
+            const int32_t c = chrom_codes[i];
+            auto it = std::lower_bound(seen.begin(), seen.end(), std::make_pair(c, (int64_t)-1));
+            if (it == seen.end() || it->first != c) {
+                it = seen.insert(it, std::make_pair(c, (int64_t)codes.size()));
+                codes.push_back(c);
+                count.push_back(0);
+            }
+            group[(size_t)i] = it->second;
+            ++count[(size_t)it->second];
+        }
+    }
+    const int64_t ng = (int64_t)codes.size();
+    *n_chrom = ng;
+    chrom_off[0] = 0;
+    for (int64_t g = 0; g < ng; ++g) chrom_off[g + 1] = chrom_off[g] + count[(size_t)g];
+    {
+        std::vector<int64_t> fill(chrom_off, chrom_off + ng);
+        for (int64_t i = 0; i < m; ++i) order[fill[(size_t)group[(size_t)i]]++] = i;
+    }
+    for (int64_t p = 0; p < m; ++p) {
+        win_end[p] = 0;
+        band_end[p] = p + 1;
+    }
+    auto sat_add = [](int64_t a, int64_t b) {
+        int64_t r;
+        return __builtin_add_overflow(a, b, &r) ? (b > 0 ? INT64_MAX : INT64_MIN) : r;
+    };
+    auto sat_sub = [](int64_t a, int64_t b) {
+        int64_t r;
+        return __builtin_sub_overflow(a, b, &r) ? (b > 0 ? INT64_MIN : INT64_MAX) : r;
+    };
+    for (int64_t g = 0; g < ng; ++g) {
+        const int64_t c0 = chrom_off[g], l = chrom_off[g + 1] - c0;
+        if (l <= 1) continue;
+        auto pos = [&](int64_t k) { return positions[order[c0 + k]]; };
+        bool pos_sorted = true;
+        for (int64_t k = 1; k < l; ++k)
+            if (pos(k) < pos(k - 1)) {
+                pos_sorted = false;
+                break;
+            }
+        int64_t bp_end_ptr = 1, block_start = 0, run_max = 0, next_band = 0;
+        while (block_start < l) {
+            int64_t end;
+            if (use_bp) {
+                if (pos_sorted) {
+                    if (bp_end_ptr < block_start + 1) bp_end_ptr = block_start + 1;
+                    const int64_t target = sat_add(pos(block_start), window_bp);
+                    while (bp_end_ptr < l && pos(bp_end_ptr) <= target) ++bp_end_ptr;
+                    end = bp_end_ptr;
+                } else {
+                    int64_t e = block_start + 1;
+                    const int64_t p0 = pos(block_start);
+                    while (e < l) {
+                        const int64_t d = sat_sub(pos(e), p0);
+                        if (d <= window_bp) ++e;
+                        else if (pos(e) > p0) break;
+                        else ++e;
+                    }
+                    end = e;
+                }
+            } else {
+                end = std::min(sat_add(block_start, window_variants), l);
+            }
+            // rows in front of this window's start have seen every window that can contain them
+            for (; next_band < block_start; ++next_band)
+                if (run_max > next_band) band_end[c0 + next_band] = c0 + run_max;
+            run_max = std::max(run_max, end);
+            win_end[c0 + block_start] = c0 + end;
+            if (end >= l) break;
+            block_start = sat_add(block_start, step_variants);
+        }
+        for (; next_band < l; ++next_band)
+            if (run_max > next_band) band_end[c0 + next_band] = c0 + run_max;
+    }
+    return 0;
+}
+
+// The strict greedy over the windows that start at the positions [ws0, ws1), from a band mask of the rows [r0, r1) in the
+// layout of `jxg_ld_band_mask_p32`: bit (lj - li - 1) of row li, wpr 32-bit words per row, set where the pair is in LD.
+// maf, first_unchecked and dropped are indexed by position; first_unchecked (start: p + 1) and dropped (start: 0) carry the
+// state from one call to the next, so a long panel is pruned range by range with a mask of bounded size.  Every window of the
+// call must lie inside one chromosome group and inside [r0, r1).
+extern "C" int jx_ld_prune_greedy(const double *maf, int64_t nrows, const int64_t *chrom_off, int64_t n_chrom, const int64_t *win_end,
+                                  int64_t ws0, int64_t ws1, const uint32_t *mask, int64_t r0, int64_t r1, int64_t wpr,
+                                  int64_t *first_unchecked, uint8_t *dropped) {
+    if (nrows < 0 || ws0 < 0 || ws1 < ws0 || ws1 > nrows) return fail("jx_ld_prune_greedy: window starts outside the rows");
+    if (r0 < 0 || r1 < r0 || r1 > nrows || wpr < 1) return fail("jx_ld_prune_greedy: mask rows outside the rows");
+    const double eps = 1e-12;
+    int64_t g = 0;
+    for (int64_t bs = ws0; bs < ws1; ++bs) {
+        const int64_t end = win_end[bs];
+        if (end == 0) continue;
+        while (g < n_chrom && chrom_off[g + 1] <= bs) ++g;
+        if (g >= n_chrom || bs < chrom_off[g] || end > chrom_off[g + 1] || end <= bs)
+            return fail("jx_ld_prune_greedy: window [" + std::to_string(bs) + ", " + std::to_string(end) + ") crosses its chromosome group");
+        if (bs < r0 || end > r1)
+            return fail("jx_ld_prune_greedy: window [" + std::to_string(bs) + ", " + std::to_string(end) + ") outside the mask rows");
+        if (end - bs - 1 > 32 * wpr) return fail("jx_ld_prune_greedy: window wider than a mask row");
+        if (end <= bs + 1) continue;
+        for (;;) {
+            bool at_least_one_prune = false;
+            for (int64_t li = bs; li < end - 1; ++li) {
+                if (dropped[li]) continue;
+                const int64_t scan_min = std::max(first_unchecked[li], bs + 1);
+                if (scan_min >= end) {
+                    first_unchecked[li] = end;
+                    continue;
+                }
+                const uint32_t *row = mask + (li - r0) * wpr;
+                bool pruned_this_round = false;
+                for (int64_t lj = scan_min; lj < end; ++lj) {
+                    if (dropped[lj]) continue;
+                    const int64_t o = lj - li - 1;
+                    if (!((row[o >> 5] >> (o & 31)) & 1u)) continue;
+                    at_least_one_prune = true;
+                    pruned_this_round = true;
+                    if (maf[li] < (1.0 - eps) * maf[lj]) {
+                        dropped[li] = 1;
+                    } else {
+                        dropped[lj] = 1;
+                        int64_t nxt = lj + 1;
+                        while (nxt < end && dropped[nxt]) ++nxt;
+                        first_unchecked[li] = nxt;
+                    }
+                    break;
+                }
+                if (!pruned_this_round && !dropped[li]) first_unchecked[li] = end;
+            }
+            if (!at_least_one_prune) break;
+        }
+    }
+    return 0;
+}

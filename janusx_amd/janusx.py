@@ -5077,3 +5077,295 @@ def admx_rmse_f32(q1, q2):
         return 0.0
     d = (a - b).astype(np.float64)
     return float(np.float32(np.float32(np.sum(d * d) / a.size) ** np.float32(0.5)))
+
+
+# ---- LD pruning and LD-block r^2 on the packed genotypes (`jx gformat -prune`; csrc/k_ld.hip) ------------------------------------
+
+LD_MASK_BUDGET_BYTES = 256 << 20   # device band mask of one SNP range (and the integer sums of one block of LD-block rows)
+
+
+def _ld_row_stats(counts, n):
+    """src/stats/ld.rs:469-543 from the integer row counts (missing, het, hom_alt) -> (mean, std, maf f64, has_missing bool),
+    in the reference's operation order (numpy's f64 elementwise operations are the IEEE ones the reference's are)."""
+    c = np.asarray(counts, dtype=np.int64)
+    non_missing = int(n) - c[:, 0]
+    has = non_missing > 0
+    obs_n = np.where(has, non_missing, 1).astype(np.float64)
+    sum_g = (c[:, 1] + 2 * c[:, 2]).astype(np.float64)
+    sum_g2 = (c[:, 1] + 4 * c[:, 2]).astype(np.float64)
+    denom = float(max(int(n) - 1, 1))
+    p = sum_g / (2.0 * obs_n)
+    maf = np.minimum(p, 1.0 - p)
+    mean = sum_g / obs_n
+    ss = np.maximum(sum_g2 - (sum_g * sum_g / obs_n), 0.0)
+    std = np.sqrt(np.maximum(ss / denom, 1e-12))
+    return (np.where(has, mean, 0.0), np.where(has, std, 1e-6), np.where(has, maf, 0.0), non_missing < int(n))
+
+
+def _ld_window_ends(chrom_codes, positions, window_bp, window_variants, step_variants):
+    """`jx_ld_window_ends` (host, no device): chromosome-grouped order of the rows, group offsets, window end per window start and
+    band end per row, all in positions of that order."""
+    cc, ps = _c(chrom_codes, np.int32).ravel(), _c(positions, np.int64).ravel()
+    m = int(cc.shape[0])
+    order, off = np.zeros(m, dtype=np.int64), np.zeros(m + 1, dtype=np.int64)
+    win_end, band_end, ng = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    check(lib().jx_ld_window_ends(_p(cc), _p(ps), m, int(window_bp or 0), 0 if window_bp else int(window_variants or 0),
+                                  int(step_variants), _p(order), _p(off), _p(ng), _p(win_end), _p(band_end)))
+    return order, off[:int(ng[0]) + 1].copy(), win_end, band_end
+
+
+def _ld_prune_greedy(maf, chrom_off, win_end, ws0, ws1, mask, r0, r1, first_unchecked, dropped):
+    """`jx_ld_prune_greedy` (host, no device) over the windows that start in [ws0, ws1) with the band mask (r1 - r0, wpr) uint32 of
+    the rows [r0, r1); `first_unchecked` (int64) and `dropped` (uint8) are updated in place."""
+    mask = _c(mask, np.uint32)
+    if mask.ndim != 2 or mask.shape[0] != r1 - r0:
+        raise RuntimeError(f"band mask shape mismatch: got {mask.shape}, expected ({r1 - r0}, words per row)")
+    check(lib().jx_ld_prune_greedy(_p(maf), int(maf.shape[0]), _p(chrom_off), int(chrom_off.shape[0]) - 1, _p(win_end), int(ws0),
+                                   int(ws1), _p(mask), int(r0), int(r1), int(mask.shape[1]), _p(first_unchecked), _p(dropped)))
+
+
+def _ld_ranges(win_end, band_end, budget_bytes):
+    """SNP ranges whose band masks stay under `budget_bytes`: [(ws0, ws1, r1, wpr)] = the windows that start in [ws0, ws1), all of
+    which end at or before r1, and the words per mask row of the rows [ws0, r1).  The ranges partition the window starts in
+    order, so the greedy runs them one after the other; rows shared by two ranges get their mask rows computed twice."""
+    m = int(win_end.shape[0])
+    idx = np.arange(m, dtype=np.int64)
+    width = np.maximum(band_end - idx - 1, 0)
+    wpr_all = max(1, (int(width.max()) + 31) // 32) if m else 1
+    longest = int((win_end - idx)[win_end > 0].max()) if np.any(win_end > 0) else 1
+    rows_cap = min(int(budget_bytes) // (4 * wpr_all), 1 << 20)
+    if rows_cap < longest:
+        raise RuntimeError(f"LD prune: a band mask budget of {int(budget_bytes)} bytes holds {rows_cap} rows of {wpr_all} words, the "
+                           f"longest window has {longest} rows; use a smaller window or a larger budget")
+    out, a = [], 0
+    while a < m:
+        r1 = min(a + rows_cap, m)
+        over = np.nonzero(win_end[a:r1] > r1)[0]
+        ws1 = a + int(over[0]) if over.size else r1
+        ends = win_end[a:ws1]
+        top = int(ends.max()) if ends.size else 0
+        if top > a:
+            wpr = max(1, (int(width[a:top].max()) + 31) // 32)
+            out.append((a, ws1, top, wpr))
+        a = ws1
+    return out
+
+
+def _ld_prune_check_args(ndim, bps, n_samples, n_chrom, n_pos, m, window_bp, window_variants, step_variants, r2_threshold):
+    """Argument checks of src/stats/ld.rs:4269-4329, in its order and with its texts."""
+    import math
+    if ndim != 2:
+        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
+    if int(n_samples) <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    r2 = float(r2_threshold)
+    if not (math.isfinite(r2) and r2 > 0.0 and r2 <= 1.0):
+        raise RuntimeError("r2_threshold must be finite and in (0, 1]")
+    if int(step_variants) <= 0:
+        raise RuntimeError("step_variants must be > 0")
+    if window_bp is None and window_variants is None:
+        raise RuntimeError("provide one of window_bp or window_variants")
+    if window_bp is not None and int(window_bp) <= 0:
+        raise RuntimeError("window_bp must be > 0")
+    if window_variants is not None and int(window_variants) <= 0:
+        raise RuntimeError("window_variants must be > 0")
+    expected = (int(n_samples) + 3) // 4
+    if bps != expected:
+        raise RuntimeError(f"packed second dimension mismatch: got {bps}, expected {expected} for n_samples={int(n_samples)}")
+    if n_chrom != m:
+        raise RuntimeError(f"chrom_codes length mismatch: got {n_chrom}, expected {m}")
+    if n_pos != m:
+        raise RuntimeError(f"positions length mismatch: got {n_pos}, expected {m}")
+
+
+def bed_packed_ld_prune_maf_priority(packed, n_samples, chrom_codes, positions, window_bp=None, window_variants=None,
+                                     step_variants=1, r2_threshold=0.2, threads=0, mask_budget_bytes=None, timings=None):
+    """src/stats/ld.rs:4245-4361: LD pruning of a packed payload (m, ceil(n / 4)) with MAF priority -> bool keep mask (m).  Windows
+    of `window_bp` base pairs (it wins when both are given) or `window_variants` rows, moved by `step_variants` rows, per
+    chromosome code; inside a window the strict greedy of :270-402 drops, of the first pair with r^2 > r2_threshold, the row of
+    the lower MAF.  The pair predicate comes from the device (`jxg_ld_band_mask_p32`: exact integer sums, r^2 in f64 in the
+    reference's operation order), range by range so that the device mask stays under `mask_budget_bytes` (extension, default
+    `LD_MASK_BUDGET_BYTES`); the greedy runs on the host (`jx_ld_prune_greedy`).  The keep mask equals the reference algorithm's
+    bit for bit.  `threads` is accepted and unused; `packed` may be a torch CUDA uint8 tensor (used in place); `timings`
+    (extension): a dict that receives `mask_s` (wall seconds of the band-mask launches with the device-to-host mask copies and
+    their synchronisation), `greedy_s` (host greedy) and `ranges`."""
+    shape = tuple(packed.shape) if hasattr(packed, "shape") else np.asarray(packed).shape
+    cc = np.asarray(chrom_codes).ravel()
+    ps = np.asarray(positions).ravel()
+    m = int(shape[0]) if len(shape) >= 1 else 0
+    _ld_prune_check_args(len(shape), int(shape[1]) if len(shape) == 2 else -1, n_samples, int(cc.shape[0]), int(ps.shape[0]), m,
+                         window_bp, window_variants, step_variants, r2_threshold)
+    if m == 0:
+        return np.zeros(0, dtype=bool)
+    n = int(n_samples)
+    order, chrom_off, win_end, band_end = _ld_window_ends(cc, ps, window_bp, window_variants, step_variants)
+    ranges = _ld_ranges(win_end, band_end, LD_MASK_BUDGET_BYTES if mask_budget_bytes is None else int(mask_budget_bytes))
+    if not ranges:                                            # no window holds two rows
+        return np.ones(m, dtype=bool)
+    import torch
+    from .pipeline import _ptr, _stream
+    panel = _panel(packed, n)
+    mean, std, maf, hasmiss = _ld_row_stats(panel.counts(), n)
+    dev = panel.device
+    identity = bool(np.array_equal(order, np.arange(m)))
+    rows_t = None if identity else torch.from_numpy(order.astype(np.int32)).to(dev)
+    mean_t = torch.from_numpy(np.ascontiguousarray(mean[order])).to(dev)
+    std_t = torch.from_numpy(np.ascontiguousarray(std[order])).to(dev)
+    miss_t = torch.from_numpy(np.ascontiguousarray(hasmiss[order].astype(np.uint8))).to(dev)
+    band_t = torch.from_numpy(band_end.astype(np.int32)).to(dev)
+    maf_s = np.ascontiguousarray(maf[order])
+    first_unchecked = np.arange(1, m + 1, dtype=np.int64)
+    dropped = np.zeros(m, dtype=np.uint8)
+    words = max((r1 - a) * wpr for a, _ws1, r1, wpr in ranges)
+    mask_t = torch.empty(words, dtype=torch.int32, device=dev)
+    t_kernel = t_greedy = 0.0
+    for a, ws1, r1, wpr in ranges:
+        t0 = time.perf_counter()
+        check(lib().jxg_ld_band_mask_p32(_ptr(panel.p32), m, n, _ptr(rows_t), m, a, r1, _ptr(band_t), _ptr(mean_t), _ptr(std_t),
+                                         _ptr(miss_t), float(r2_threshold), wpr, _ptr(mask_t), _stream()))
+        mask = mask_t[:(r1 - a) * wpr].cpu().numpy().view(np.uint32).reshape(r1 - a, wpr)
+        t1 = time.perf_counter()
+        _ld_prune_greedy(maf_s, chrom_off, win_end, a, ws1, mask, a, r1, first_unchecked, dropped)
+        t_kernel += t1 - t0
+        t_greedy += time.perf_counter() - t1
+    if timings is not None:
+        timings.update(mask_s=t_kernel, greedy_s=t_greedy, ranges=len(ranges))
+    keep = np.ones(m, dtype=bool)
+    keep[order] = dropped == 0
+    return keep
+
+
+def _ld_sums(panel, i0, i1, j0, j1):
+    """(6, i1 - i0, j1 - j0) int32 D, N, S_i, S_j, Q_i, Q_j of a block of row pairs of a panel (`jxg_ld_sums_p32`)."""
+    import torch
+    from .pipeline import _ptr, _stream
+    out = torch.empty((6, i1 - i0, j1 - j0), dtype=torch.int32, device=panel.device)
+    check(lib().jxg_ld_sums_p32(_ptr(panel.p32), panel.m, panel.n, None, panel.m, int(i0), int(i1), int(j0), int(j1), _ptr(out),
+                                _stream()))
+    return out.cpu().numpy()
+
+
+def ld_r2_matrix_packed(packed_rows, n_samples):
+    """`ld_r2_matrix_from_packed_rows_blas`, src/stats/ld.rs:1095-1198: r^2 (m, m) f32 of the rows of a packed payload, each row
+    centred by its mean rounded to f32 with missing calls at 0, r^2 = clamp((gram_ij / sqrt(gram_ii gram_jj))^2, 0, 1), 0 where
+    the root is <= 1e-20, 1 on the diagonal.  The Gram comes from the exact integer sums of `jxg_ld_sums_p32`:
+    gram_ij = D - mu_i S_j - mu_j S_i + mu_i mu_j N in f64 (the reference adds f32 products in its BLAS)."""
+    shape = tuple(packed_rows.shape)
+    if len(shape) != 2:
+        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
+    m, n = int(shape[0]), int(n_samples)
+    if m == 0:
+        return np.zeros((0, 0), dtype=np.float32)
+    if m == 1:
+        return np.ones((1, 1), dtype=np.float32)
+    if n <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    if shape[1] != (n + 3) // 4:
+        raise RuntimeError(f"packed row length mismatch: got {m * shape[1]}, expected {m * ((n + 3) // 4)}")
+    panel = _panel(packed_rows, n)
+    c = panel.counts().astype(np.int64)
+    mean = _ld_row_stats(c, n)[0]
+    mu = mean.astype(np.float32).astype(np.float64)
+    nm = (n - c[:, 0]).astype(np.float64)
+    alt, sq = (c[:, 1] + 2 * c[:, 2]).astype(np.float64), (c[:, 1] + 4 * c[:, 2]).astype(np.float64)
+    diag = np.maximum(sq - 2.0 * mu * alt + mu * mu * nm, 0.0)
+    out = np.empty((m, m), dtype=np.float32)
+    step = max(32, min(m, (LD_MASK_BUDGET_BYTES // (24 * m)) // 32 * 32))
+    for i0 in range(0, m, step):
+        i1 = min(m, i0 + step)
+        s = _ld_sums(panel, i0, i1, 0, m).astype(np.float64)
+        mi = mu[i0:i1, None]
+        gram = s[0] - mi * s[3] - mu[None, :] * s[2] + (mi * mu[None, :]) * s[1]
+        den = np.sqrt(diag[i0:i1, None] * diag[None, :])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            corr = np.where(den > 1e-20, gram / np.where(den > 1e-20, den, 1.0), 0.0)
+            r2 = corr * corr
+        r2 = np.clip(np.where(np.isfinite(r2), r2, 0.0), 0.0, 1.0)
+        out[i0:i1] = r2.astype(np.float32)
+    np.fill_diagonal(out, 1.0)
+    return out
+
+
+def _ld_chr_token(s):
+    """`normalize_chr_token`, src/stats/ld.rs:621-628: trimmed, a leading `chr` (any case) stripped."""
+    t = str(s).strip()
+    return t[3:] if len(t) >= 3 and t[:3].lower() == "chr" else t
+
+
+def _ld_select_bim(bfile, chrom_ranges, start_bp, end_bp, selected_chrom=None, selected_pos=None):
+    """Row selection of `bed_ldblock_r2_rust` (src/stats/ld.rs:793-825, 871-921, 4741-4773; host only) -> (total rows, row indices,
+    chromosome tokens, positions)."""
+    prefix = _bed_prefix(bfile)
+    if not prefix:
+        raise RuntimeError("bfile must not be empty")
+    chrom_ranges, start_bp, end_bp = list(chrom_ranges), [int(v) for v in start_bp], [int(v) for v in end_bp]
+    if len(chrom_ranges) != len(start_bp) or len(chrom_ranges) != len(end_bp):
+        raise RuntimeError(f"bimrange length mismatch: chrom_ranges={len(chrom_ranges)}, start_bp={len(start_bp)}, "
+                           f"end_bp={len(end_bp)}")
+    if not chrom_ranges:
+        raise RuntimeError("bimrange list must not be empty")
+    ranges = {}
+    for i, (ch, s, e) in enumerate(zip(chrom_ranges, start_bp, end_bp)):
+        if s < 0 or e < 0:
+            raise RuntimeError(f"bimrange[{i}] start/end must be >= 0, got ({s}, {e})")
+        if s > e:
+            s, e = e, s
+        ranges.setdefault(_ld_chr_token(ch), []).append((s, e))
+    sites = None
+    if (selected_chrom is None) != (selected_pos is None):
+        raise RuntimeError("selected_chrom and selected_pos must be provided together")
+    if selected_chrom is not None:
+        if len(selected_chrom) != len(selected_pos):
+            raise RuntimeError(f"selected_chrom/selected_pos length mismatch: {len(selected_chrom)} vs {len(selected_pos)}")
+        sites = {(_ld_chr_token(ch), int(p)) for ch, p in zip(selected_chrom, selected_pos)}
+    total, idx, chrom, pos = 0, [], [], []
+    path = f"{prefix}.bim"
+    try:
+        fh = open(path)
+    except OSError as e:
+        raise RuntimeError(f"{path}: {e}") from None
+    with fh:
+        for line_no, line in enumerate(fh, 1):
+            parts = line.split()
+            if len(parts) < 4:
+                raise RuntimeError(f"{path}:{line_no}: malformed .bim line")
+            try:
+                p = int(parts[3])
+            except ValueError:
+                raise RuntimeError(f"{path}:{line_no}: invalid position {parts[3]!r}") from None
+            ch = _ld_chr_token(parts[0])
+            keep = any(s <= p <= e for s, e in ranges.get(ch, ()))
+            if keep and sites is not None and (ch, p) not in sites:
+                keep = False
+            if keep:
+                idx.append(total)
+                chrom.append(ch)
+                pos.append(p)
+            total += 1
+    if total == 0:
+        raise RuntimeError(f"no variant rows in {path}")
+    return total, idx, chrom, pos
+
+
+def bed_ldblock_r2_rust(bfile, chrom_ranges, start_bp, end_bp, selected_chrom=None, selected_pos=None, threads=0):
+    """src/stats/ld.rs:4721-4811: r^2 matrix of the `.bim` rows of a PLINK prefix that lie in the inclusive ranges
+    (chrom_ranges[i], start_bp[i], end_bp[i]) (a `chr` prefix is stripped, a reversed range is swapped) and, when given, in the site
+    set (selected_chrom, selected_pos) -> (r2 f32 (k, k), chromosome tokens, positions).  An empty selection gives a (0, 0) array
+    and two empty lists.  `threads` is accepted and unused."""
+    from .bed import BED_MAGIC, read_fam_ids
+    prefix = _bed_prefix(bfile)
+    total, idx, chrom, pos = _ld_select_bim(bfile, chrom_ranges, start_bp, end_bp, selected_chrom, selected_pos)
+    if not idx:
+        return np.zeros((0, 0), dtype=np.float32), [], []
+    n = len(read_fam_ids(prefix))
+    if n == 0:
+        raise RuntimeError("empty PLINK input (no samples in .fam)")
+    bps = (n + 3) // 4
+    path = f"{prefix}.bed"
+    with open(path, "rb") as fh:
+        if fh.read(3) != BED_MAGIC:
+            raise RuntimeError(f"{path}: not a SNP-major PLINK .bed (bad magic)")
+    if os.path.getsize(path) != 3 + total * bps:
+        raise RuntimeError(f"{path}: size {os.path.getsize(path)} != 3 + {total}*{bps}")
+    rows = np.ascontiguousarray(np.memmap(path, dtype=np.uint8, mode="r", offset=3, shape=(total, bps))[np.asarray(idx)])
+    return ld_r2_matrix_packed(rows, n), chrom, pos
