@@ -5235,12 +5235,15 @@ def bed_packed_ld_prune_maf_priority(packed, n_samples, chrom_codes, positions, 
     return keep
 
 
-def _ld_sums(panel, i0, i1, j0, j1):
-    """(6, i1 - i0, j1 - j0) int32 D, N, S_i, S_j, Q_i, Q_j of a block of row pairs of a panel (`jxg_ld_sums_p32`)."""
+def _ld_sums(panel, i0, i1, j0, j1, rows=None):
+    """(6, i1 - i0, j1 - j0) int32 D, N, S_i, S_j, Q_i, Q_j of a block of row pairs of a panel (`jxg_ld_sums_p32`); with `rows`
+    (record numbers of the panel) the block is one of positions of that row list."""
     import torch
     from .pipeline import _ptr, _stream
     out = torch.empty((6, i1 - i0, j1 - j0), dtype=torch.int32, device=panel.device)
-    check(lib().jxg_ld_sums_p32(_ptr(panel.p32), panel.m, panel.n, None, panel.m, int(i0), int(i1), int(j0), int(j1), _ptr(out),
+    rows_t = None if rows is None else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(panel.device)
+    nrows = panel.m if rows is None else int(rows_t.shape[0])
+    check(lib().jxg_ld_sums_p32(_ptr(panel.p32), panel.m, panel.n, _ptr(rows_t), nrows, int(i0), int(i1), int(j0), int(j1), _ptr(out),
                                 _stream()))
     return out.cpu().numpy()
 

@@ -54,9 +54,12 @@ def ref_row_stats(g):
     m, n = g.shape
     v = g >= 0
     g0 = np.where(v, g, 0).astype(np.int64)
-    non_missing = v.sum(axis=1).astype(np.int64)
-    alt_sum = g0.sum(axis=1)
-    sq_sum = (g0 * g0).sum(axis=1)
+    return ref_row_stats_from_counts(v.sum(axis=1).astype(np.int64), g0.sum(axis=1), (g0 * g0).sum(axis=1), n)
+
+
+def ref_row_stats_from_counts(non_missing, alt_sum, sq_sum, n):
+    """The float part of `ref_row_stats` from the integer row sums (called calls, sum g, sum g^2)."""
+    m = len(non_missing)
     denom = float(max(n - 1, 1))
     mean, std, maf = np.zeros(m), np.full(m, 1e-6), np.zeros(m)
     for i in range(m):
@@ -71,20 +74,47 @@ def ref_row_stats(g):
 
 
 def ref_six_sums(g, rows_i, rows_j):
-    """D, N, S_i, S_j, Q_i, Q_j (int64, (len(rows_i), len(rows_j))) of row pairs."""
+    """D, N, S_i, S_j, Q_i, Q_j (int64, (len(rows_i), len(rows_j))) of row pairs.  The products run in float64 (BLAS): every
+    partial sum is an integer <= 4 n < 2^53, so they are exact in any order of addition."""
     g = np.asarray(g)
-    vi, vj = (g[rows_i] >= 0).astype(np.int64), (g[rows_j] >= 0).astype(np.int64)
-    gi, gj = np.where(vi > 0, g[rows_i], 0).astype(np.int64), np.where(vj > 0, g[rows_j], 0).astype(np.int64)
-    return np.stack([gi @ gj.T, vi @ vj.T, gi @ vj.T, vi @ gj.T, (gi * gi) @ vj.T, vi @ (gj * gj).T])
+    vi, vj = (g[rows_i] >= 0).astype(np.float64), (g[rows_j] >= 0).astype(np.float64)
+    gi, gj = np.where(vi > 0, g[rows_i], 0).astype(np.float64), np.where(vj > 0, g[rows_j], 0).astype(np.float64)
+    out = np.stack([gi @ gj.T, vi @ vj.T, gi @ vj.T, vi @ gj.T, (gi * gi) @ vj.T, vi @ (gj * gj).T])
+    return np.rint(out).astype(np.int64)
+
+
+def ref_six_sums_chunked(g, chunk=1 << 20, threads=8):
+    """The six sums of all row pairs of a panel with many samples -> (6, m, m) int64: float64 matrix products over chunks of
+    `chunk` samples (every entry of a chunk's product is an integer <= 4 chunk < 2^53, so the product is exact whatever order
+    the BLAS adds in), added in int64.  One product per chunk, of the stacked planes (d; v; q) with their transpose, holds the
+    six blocks; the chunks are shared among `threads` threads (numpy releases the lock in its loops)."""
+    from concurrent.futures import ThreadPoolExecutor
+    g = np.asarray(g)
+    m, n = g.shape
+    blk = (slice(0, m), slice(m, 2 * m), slice(2 * m, 3 * m))                # d, v, q
+
+    def one(c0):
+        gc = g[:, c0:c0 + chunk]
+        a = np.empty((3 * m, gc.shape[1]), dtype=np.float64)
+        np.maximum(gc, 0, out=a[blk[0]], casting="unsafe")
+        np.greater_equal(gc, 0, out=a[blk[1]], casting="unsafe")
+        np.multiply(a[blk[0]], a[blk[0]], out=a[blk[2]])
+        p = np.rint(a @ a.T).astype(np.int64)
+        return np.stack([p[blk[x], blk[y]] for x, y in ((0, 0), (1, 1), (0, 1), (1, 0), (2, 1), (1, 2))])
+    with ThreadPoolExecutor(threads) as pool:
+        return sum(pool.map(one, range(0, n, chunk)), np.zeros((6, m, m), dtype=np.int64))
 
 
 class LdRef:
     """The pair predicate "in LD" of the reference (src/stats/ld.rs:339-368) with its two formulas, asked lazily."""
 
-    def __init__(self, g, r2_threshold):
+    def __init__(self, g, r2_threshold, st=None, sums=None):
+        """`st` / `sums`: row statistics and the (6, m, m) integer sums of all row pairs computed elsewhere (a panel too long to
+        go through `ref_row_stats` / `ref_six_sums` in one piece)."""
         self.g = np.asarray(g)
         self.n = self.g.shape[1]
-        self.st = ref_row_stats(self.g)
+        self.st = ref_row_stats(self.g) if st is None else st
+        self.sums = sums
         self.thresh = float(r2_threshold) * (1.0 + 1e-12)
         self.hits = {"clean": 0, "pairwise": 0}           # pairs in LD the greedy met, by the formula that decided them
         self.asked = 0
@@ -93,12 +123,24 @@ class LdRef:
 
     def r2_block(self, gi, gjs):
         """r^2 of row gi against the rows gjs (NaN where the reference has no value), and which pairs took the clean formula."""
+        r2, is_clean = self.r2_rect(np.asarray([gi]), np.asarray(gjs))
+        return r2[0], is_clean[0]
+
+    def six_sums(self, gis, gjs):
+        if self.sums is not None:
+            return self.sums[:, np.asarray(gis)[:, None], np.asarray(gjs)[None, :]]
+        return ref_six_sums(self.g, gis, gjs)
+
+    def r2_rect(self, gis, gjs):
+        """r^2 of every row of gis against every row of gjs, each value the per-pair expression (numpy's elementwise f64
+        operations are the IEEE ones) -> ((len(gis), len(gjs)) f64 with NaN where the reference has no value, and which pairs
+        took the clean formula)."""
         st, n = self.st, self.n
-        s = ref_six_sums(self.g, [gi], gjs)[:, 0, :].astype(np.float64)
-        d, nn, si, sj, si2, sj2 = s
+        gis, gjs = np.asarray(gis, dtype=np.int64), np.asarray(gjs, dtype=np.int64)
+        d, nn, si, sj, si2, sj2 = self.six_sums(gis, gjs).astype(np.float64)
         denom = float(max(n - 1, 1))
-        cov = d - float(n) * st["mean"][gi] * st["mean"][gjs]
-        denom_corr = denom * st["std"][gi] * st["std"][gjs]
+        cov = d - (float(n) * st["mean"][gis])[:, None] * st["mean"][gjs][None, :]
+        denom_corr = (denom * st["std"][gis])[:, None] * st["std"][gjs][None, :]
         with np.errstate(divide="ignore", invalid="ignore"):
             corr = np.where(denom_corr > 0.0, cov / denom_corr, 0.0)
             clean = corr * corr
@@ -108,7 +150,7 @@ class LdRef:
             den = var_i * var_j
             pw = (cov_num * cov_num) / den
         pw = np.where((nn > 1) & np.isfinite(den) & (den > 0.0) & np.isfinite(cov_num), pw, np.nan)
-        is_clean = ~st["has_missing"][gi] & ~st["has_missing"][gjs]
+        is_clean = ~st["has_missing"][gis][:, None] & ~st["has_missing"][gjs][None, :]
         return np.where(is_clean, clean, pw), is_clean
 
     def in_ld(self, idx_list, li, lj):
@@ -276,19 +318,186 @@ def _positions_layout(chrom_codes, positions, window_bp, window_variants, step):
     return order, off, win_end, band_end
 
 
-def _numpy_band_mask(ref, order, band_end):
-    """Band mask in the layout of `jxg_ld_band_mask_p32` from the restatement's predicate (every pair of the band)."""
+def band_r2(ref, order, band_end, r0=0, r1=None, wpr=None):
+    """The restatement's r^2 of every pair of the band of the rows [r0, r1) of the row list `order`, in the layout of
+    `jxg_ld_band_mask_p32`: column o of row i - r0 is the pair (i, j = i + 1 + o), o < 32 wpr, and the pair is in the band when
+    j < min(band_end[i], i + 1 + 32 wpr, len(order)).  `wpr` None: the words the widest band of the whole list needs.
+    -> (r2 (r1 - r0, 32 wpr) f64, NaN outside the band and where the reference has no value; inband; took the clean formula)."""
+    order, band_end = np.asarray(order, dtype=np.int64), np.asarray(band_end, dtype=np.int64)
     m = len(order)
-    width = int(np.max(band_end - np.arange(m) - 1)) if m else 0
-    wpr = max(1, (width + 31) // 32)
-    mask = np.zeros((m, wpr), dtype=np.uint32)
-    for p in range(m):
-        if band_end[p] > p + 1:
-            js = np.arange(p + 1, band_end[p])
-            r2, _ = ref.r2_block(order[p], order[js])
-            for o in np.nonzero(np.isfinite(r2) & (r2 > ref.thresh))[0]:
-                mask[p, o >> 5] |= np.uint32(1 << (o & 31))
-    return mask
+    r1 = m if r1 is None else int(r1)
+    if wpr is None:
+        width = int(np.max(band_end - np.arange(m) - 1)) if m else 0
+        wpr = max(1, (width + 31) // 32)
+    w = 32 * int(wpr)
+    rr = max(r1 - r0, 0)
+    r2, inband, clean = np.full((rr, w), np.nan), np.zeros((rr, w), dtype=bool), np.zeros((rr, w), dtype=bool)
+    o = np.arange(w, dtype=np.int64)
+    for a in range(r0, r1, 64):
+        b = min(a + 64, r1)
+        ps = np.arange(a, b, dtype=np.int64)
+        be = np.minimum(np.minimum(band_end[a:b], ps + 1 + w), m)
+        top = int(be.max())
+        if top <= a + 1:
+            continue
+        span = np.arange(a + 1, top, dtype=np.int64)
+        v, c = ref.r2_rect(order[ps], order[span])
+        ok = (ps[:, None] + 1 + o[None, :]) < be[:, None]
+        at = np.minimum((ps - a)[:, None] + o[None, :], len(span) - 1)          # j = i + 1 + o is entry (i - a) + o of the span
+        r2[a - r0:b - r0] = np.where(ok, np.take_along_axis(v, at, 1), np.nan)
+        clean[a - r0:b - r0] = ok & np.take_along_axis(c, at, 1)
+        inband[a - r0:b - r0] = ok
+    return r2, inband, clean
+
+
+def pack_band_bits(hits):
+    """(rows, 32 wpr) bool -> (rows, wpr) uint32, bit o & 31 of word o >> 5."""
+    hits = np.ascontiguousarray(hits)
+    return np.packbits(hits, axis=1, bitorder="little").view("<u4").astype(np.uint32).reshape(hits.shape[0], hits.shape[1] // 32)
+
+
+def band_hits(r2, thresh):
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(r2) & (r2 > thresh)
+
+
+def band_margin(r2, thresh):
+    """Smallest |r2 - thresh| / thresh over the band pairs that have a value (inf when there is none)."""
+    v = r2[np.isfinite(r2)]
+    return float(np.min(np.abs(v - thresh)) / thresh) if v.size else np.inf
+
+
+def _numpy_band_mask(ref, order, band_end, r0=0, r1=None, wpr=None):
+    """Band mask in the layout of `jxg_ld_band_mask_p32` from the restatement's predicate (every pair of the band of the rows
+    [r0, r1), the band of row i cut at min(band_end[i], i + 1 + 32 wpr) as the kernel cuts it)."""
+    r2, _inband, _clean = band_r2(ref, order, band_end, r0, r1, wpr)
+    return pack_band_bits(band_hits(r2, ref.thresh))
+
+
+def band_block_forms(hasmiss, band_end, nrows, r0, r1, wpr, i_block_only=False):
+    """The launch arithmetic of `jxg_ld_band_mask_p32` restated: block (y, x) is the 32 rows from i0 = r0 + 32 y against the 32
+    rows from j0 = i0 + 32 x, x <= wpr; it is computed when j0 < nrows and j0 < max band_end over the i-block's rows < r1, in
+    the six-sum form when any row of the i-block (< r1) or of the j-block (< nrows) has a missing call, else in the clean form.
+    -> int8 (i-blocks, wpr + 1): -1 not computed, 0 clean, 1 six.  `i_block_only`: what a launch that looked at the i-block
+    alone would decide (for counting the pairs that depend on the j-block's part)."""
+    hasmiss, band_end = np.asarray(hasmiss, dtype=bool), np.asarray(band_end, dtype=np.int64)
+    ny = (max(r1 - r0, 0) + 31) // 32
+    forms = np.full((ny, wpr + 1), -1, dtype=np.int8)
+    for y in range(ny):
+        i0 = r0 + 32 * y
+        i1 = min(i0 + 32, r1)
+        be = int(band_end[i0:i1].max())
+        mi = bool(hasmiss[i0:i1].any())
+        for x in range(wpr + 1):
+            j0 = i0 + 32 * x
+            if j0 >= nrows or j0 >= be:
+                continue
+            forms[y, x] = 1 if (mi or (not i_block_only and bool(hasmiss[j0:min(j0 + 32, nrows)].any()))) else 0
+    return forms
+
+
+def band_pair_forms(forms, r0, rows, wpr):
+    """Form of the block that owns each pair of a (rows, 32 wpr) band layout."""
+    i = r0 + np.arange(rows, dtype=np.int64)[:, None]
+    j = i + 1 + np.arange(32 * wpr, dtype=np.int64)[None, :]
+    y = (i - r0) // 32
+    x = (j - (r0 + 32 * y)) // 32
+    return forms[y, np.minimum(x, forms.shape[1] - 1)]
+
+
+def band_form_meetings(hits, clean, pair_form):
+    """-> (mask words that receive set bits from a clean-form block and from a six-form block, set bits of complete pairs (clean
+    formula) inside six-form blocks, set bits by formula)."""
+    rows, w = hits.shape
+    by_word = lambda sel: (hits & sel).reshape(rows, w // 32, 32).any(axis=2)   # noqa: E731
+    both = by_word(pair_form == 0) & by_word(pair_form == 1)
+    return int(both.sum()), int((hits & clean & (pair_form == 1)).sum()), {"clean": int((hits & clean).sum()),
+                                                                            "pairwise": int((hits & ~clean).sum())}
+
+
+def describe_band_diff(got, want, r2, clean, r0, pair_form=None):
+    """Text for a failed mask comparison: the first differing pair, its block, the formula and the restatement's r^2."""
+    diff = np.asarray(got, dtype=np.uint32) ^ np.asarray(want, dtype=np.uint32)
+    if got.shape != want.shape:
+        return f"mask shapes differ: {got.shape} vs {want.shape}"
+    if not diff.any():
+        return "masks equal"
+    row, word = [int(k[0]) for k in np.nonzero(diff)]
+    bit = int(diff[row, word])
+    o = 32 * word + ((bit & -bit).bit_length() - 1)
+    i, j = r0 + row, r0 + row + 1 + o
+    y = row // 32
+    x = (j - (r0 + 32 * y)) // 32
+    form = "" if pair_form is None else f", block form {('none', 'clean', 'six')[int(pair_form[row, o]) + 1]}"
+    return (f"{int(np.count_nonzero(np.unpackbits(diff.view(np.uint8))))} bits differ; first at pair (i={i}, j={j}), mask row {row} "
+            f"word {word} bit {o & 31}, block (y={y}, x={x}){form}, device bit {(int(got[row, word]) >> (o & 31)) & 1}, restatement "
+            f"formula {'clean' if clean[row, o] else 'pairwise'}, restatement r2 {r2[row, o]!r}")
+
+
+# one row; longer than 32 rows; across the 32-row boundary 1504; the second half of an LD block, from a boundary, 40 % missing
+SPARSE_STRETCHES = ((777, 778, 0.03), (1030, 1070, 0.03), (1500, 1530, 0.03), (2048, 2052, 0.4))
+
+
+def sparse_missing_panel(m, seed=13):
+    """`ld_panel(601, m)` without missing calls, then missing calls on the rows of SPARSE_STRETCHES only: blocks of both launch
+    forms lie side by side and share mask words.  The panel's LD blocks of 8 rows are moved by 4 rows, so that they straddle the
+    32-row block boundaries (rows 1020 - 1027 are one of them: a clean block, then one with the row 1030).  Rows 2044 - 2047 are
+    complete and in a block without a missing call; their LD partners 2048 - 2051 lack 40 % of their calls, so the block pair
+    is of the six-sum form through its j-block alone and the clean formula would be far off for these pairs."""
+    g, pos = ld_panel(601, m + 4, seed)
+    g, pos = g[4:].copy(), pos[4:].copy()
+    rng = np.random.default_rng(seed + 1)
+    for a, b, rate in SPARSE_STRETCHES:
+        hole = rng.random((b - a, g.shape[1])) < rate
+        hole[:, 0] = True                                     # every row of a stretch has at least one
+        sub = g[a:b]
+        sub[hole] = -9
+    return g, pos
+
+
+def valueless_panel(m=1003):
+    """Rows whose pairs have no r^2 or an extreme one, inside any band of a few rows: every call missing, one and two calls,
+    monomorphic rows (complete: 0 and 2; with missing calls), identical neighbours and a complement (2 - g), each among complete
+    rows and among rows with missing calls.  -> (g, positions, {kind: rows})."""
+    g, pos = ld_panel(601, 4000, 11, True)
+    g, pos = g[:m].copy(), pos[:m].copy()
+    full = np.nonzero((g >= 0).all(axis=1))[0]
+    holed = np.nonzero((g < 0).any(axis=1))[0]
+    c = int(full[(full > 400) & (full < 600)][0])
+    h = int(holed[(holed > 600) & (holed < 800)][0])
+    g[100] = -9
+    g[101] = -9
+    g[101, :2] = [1, 2]
+    g[102] = -9
+    g[102, 5] = 1
+    g[200] = 0
+    g[201] = np.where(g[201] >= 0, 2, -9)
+    g[201, 7] = -9
+    g[202] = 2
+    g[c + 1] = g[c]
+    g[c + 2] = 2 - g[c]
+    g[h + 1] = g[h]
+    g[h + 2] = np.where(g[h] >= 0, 2 - g[h], -9)
+    kinds = dict(all_missing=[100], few_calls=[101, 102], mono_complete=[200, 202], mono_missing=[201],
+                 twins_complete=[c, c + 1, c + 2], twins_missing=[h, h + 1, h + 2])
+    return g, pos, kinds
+
+
+def band_value_kinds(ref, order, r2, inband, clean):
+    """Counts of the band pairs by what the restatement made of them."""
+    order = np.asarray(order, dtype=np.int64)
+    rows, w = r2.shape
+    i = np.arange(rows, dtype=np.int64)[:, None] + np.zeros((1, w), dtype=np.int64)
+    j = np.minimum(i + 1 + np.arange(w, dtype=np.int64)[None, :], len(order) - 1)
+    gi, gj = order[i[inband]], order[j[inband]]
+    v, cl = r2[inband], clean[inband]
+    st = ref.st
+    nn = np.minimum(st["non_missing"][gi], st["non_missing"][gj])           # N <= min of the two rows' called calls
+    tiny = (st["std"][gi] == 1e-6) | (st["std"][gj] == 1e-6)
+    with np.errstate(invalid="ignore"):
+        return dict(pairs=int(v.size), nan=int(np.isnan(v).sum()), n_le_1=int((~cl & (nn <= 1) & np.isnan(v)).sum()),
+                    zero_variance=int((~cl & (nn > 1) & np.isnan(v)).sum()), std_floor=int((cl & tiny).sum()),
+                    r2_one=int((np.abs(v - 1.0) <= 1e-12).sum()), r2_one_clean=int((cl & (np.abs(v - 1.0) <= 1e-12)).sum()))
 
 
 def _host_prune(g, chrom_codes, positions, window_bp, window_variants, step, r2, split=None):
@@ -551,3 +760,127 @@ def test_row_stats_equal_restatement():
     assert np.array_equal(mean, st["mean"]) and np.array_equal(std, st["std"]) and np.array_equal(maf, st["maf"])
     assert np.array_equal(has, st["has_missing"])
     assert (mean[5], std[5], maf[5], has[5]) == (0.0, 1e-6, 0.0, True) and std[6] == 1e-6 and maf[6] == 0.0
+
+
+# ---- the vectorised band restatement and the inputs of tests/test_gpu_ld_kernel.py --------------------------------------------------
+
+def _slow_band_mask(ref, order, band_end, wpr):
+    """The band mask pair by pair through `LdRef.r2_block`, one row at a time (what `_numpy_band_mask` was before it was
+    vectorised)."""
+    m = len(order)
+    mask = np.zeros((m, wpr), dtype=np.uint32)
+    for p in range(m):
+        be = min(int(band_end[p]), p + 1 + 32 * wpr, m)
+        if be > p + 1:
+            js = np.arange(p + 1, be)
+            r2, _ = ref.r2_block(order[p], order[js])
+            for o in np.nonzero(np.isfinite(r2) & (r2 > ref.thresh))[0]:
+                mask[p, o >> 5] |= np.uint32(1 << (o & 31))
+    return mask
+
+
+def test_vectorised_band_mask_equals_the_row_by_row_one(panels):
+    g, pos, chrom = panels["missing"]
+    g = g[:500]
+    ref = LdRef(g, 0.2)
+    rng = np.random.default_rng(4)
+    order = rng.permutation(500)
+    idx = np.arange(500)
+    band_end = np.minimum(idx + 1 + rng.integers(0, 150, size=500), 500)
+    for wpr in (5, 2, 1):
+        want = _slow_band_mask(ref, order, band_end, wpr)
+        assert 0 < np.count_nonzero(want)
+        assert np.array_equal(_numpy_band_mask(ref, order, band_end, wpr=wpr), want)
+        assert np.array_equal(_numpy_band_mask(ref, order, band_end, 37, 103, wpr), want[37:103])
+    assert _numpy_band_mask(ref, order, band_end, 60, 60, 3).shape == (0, 3)
+    assert np.array_equal(ref_six_sums_chunked(g[:40], chunk=128), ref_six_sums(g, np.arange(40), np.arange(40)))
+
+
+def test_sparse_missing_panel_makes_the_two_launch_forms_meet():
+    """On the sparse-missing panel, under the production bands, mask words receive set bits from a clean-form block and from a
+    six-form block, and six-form blocks hold complete pairs (clean formula) with set bits."""
+    m = 2200
+    g, pos = sparse_missing_panel(m)
+    chrom = np.zeros(m, dtype=np.int32)
+    st = ref_row_stats(g)
+    assert st["has_missing"].sum() == sum(b - a for a, b, _ in SPARSE_STRETCHES)
+    all_clean = dict(st, has_missing=np.zeros(m, dtype=bool))
+    for wbp, wv, step, thr in PARAM_SETS:
+        order, _off, _win_end, band_end = jx._ld_window_ends(chrom, pos, wbp, wv, step)
+        ref = LdRef(g, thr)
+        r2, inband, clean = band_r2(ref, order, band_end)
+        wpr = r2.shape[1] // 32
+        forms = band_block_forms(st["has_missing"][order], band_end, m, 0, m, wpr)
+        assert (forms == 0).any() and (forms == 1).any()
+        pf = band_pair_forms(forms, 0, m, wpr)
+        assert (pf[inband] >= 0).all()                                # every band pair lies in a block that is computed
+        hits = band_hits(r2, ref.thresh)
+        both, complete_in_six, by_formula = band_form_meetings(hits, clean, pf)
+        print(f"sparse panel {(wbp, wv, step, thr)}: {both} mask words fed by both forms, {complete_in_six} set bits of complete "
+              f"pairs in six-form blocks, set bits by formula {by_formula}, margin {band_margin(r2, ref.thresh):.3e}")
+        assert both > 0 and complete_in_six > 0
+        assert by_formula["clean"] > 0 and by_formula["pairwise"] > 0
+        assert band_margin(r2, ref.thresh) > 1e-9
+        # pairs whose block is of the six-sum form through its j-block alone, and whose bit the clean formula would get wrong
+        i_only = band_pair_forms(band_block_forms(st["has_missing"][order], band_end, m, 0, m, wpr, i_block_only=True), 0, m, wpr)
+        wrong = band_hits(band_r2(LdRef(g, thr, st=all_clean), order, band_end)[0], ref.thresh) != hits
+        print(f"  {int(((pf == 1) & (i_only == 0) & inband).sum())} band pairs are six-form through the j-block alone, "
+              f"{int(((pf == 1) & (i_only == 0) & wrong).sum())} of them with a bit the clean formula gets wrong")
+        assert ((pf == 1) & (i_only == 0) & wrong).sum() > 0
+
+
+def test_valueless_panel_holds_every_kind_of_pair():
+    g, pos, kinds = valueless_panel()
+    m = g.shape[0]
+    order, _off, _win_end, band_end = jx._ld_window_ends(np.zeros(m, dtype=np.int32), pos, None, 50, 5)
+    ref = LdRef(g, 0.2)
+    r2, inband, clean = band_r2(ref, order, band_end)
+    k = band_value_kinds(ref, order, r2, inband, clean)
+    print(f"valueless panel: {k}, margin {band_margin(r2, ref.thresh):.3e}")
+    assert k["nan"] > 0 and k["n_le_1"] > 0 and k["zero_variance"] > 0 and k["std_floor"] > 0
+    assert k["r2_one"] >= 4 and k["r2_one_clean"] >= 2               # identical and complement, complete and with missing calls
+    assert band_margin(r2, ref.thresh) > 1e-9
+
+
+def test_ld_entry_points_refuse_before_they_touch_the_device():
+    """Every refusal returns 1 with its message.  The buffers are host arrays of the size the arguments claim: a refusal comes
+    before the first device call, so nothing reads them."""
+    from janusx_amd._lib import lib
+    L = lib()
+    p = lambda a: a.ctypes.data                                      # noqa: E731
+
+    def band(m_total, n, nrows, r0, r1, wpr, tiles=None, mask_words=None):
+        tiles = L.jxg_num_tiles(max(n, 1)) if tiles is None else tiles
+        p32 = np.full((tiles, m_total, 32), 0x55, dtype=np.uint8)
+        be = np.arange(1, nrows + 1, dtype=np.int32)
+        mean, sd, hm = np.zeros(nrows), np.ones(nrows), np.zeros(nrows, dtype=np.uint8)
+        mask = np.zeros(max(1, (max(r1 - r0, 0) * max(wpr, 0)) if mask_words is None else mask_words), dtype=np.uint32)
+        st = L.jxg_ld_band_mask_p32(p(p32), m_total, n, None, nrows, r0, r1, p(be), p(mean), p(sd), p(hm), 0.2, wpr, p(mask), None)
+        assert not mask.any()
+        return st, L.jx_last_error().decode()
+
+    def sums(m_total, n, nrows, i0, i1, j0, j1):
+        p32 = np.full((L.jxg_num_tiles(max(n, 1)), m_total, 32), 0x55, dtype=np.uint8)
+        out = np.zeros(6 * max(i1 - i0, 1) * max(j1 - j0, 1), dtype=np.int32)
+        st = L.jxg_ld_sums_p32(p(p32), m_total, n, None, nrows, i0, i1, j0, j1, p(out), None)
+        assert not out.any()
+        return st, L.jx_last_error().decode()
+
+    too_many = (1 << 24) + 1
+    for n in (0, -5):
+        assert band(4, n, 4, 0, 4, 1) == (1, "jxg_ld_band_mask_p32: n must be > 0")
+        assert sums(4, n, 4, 0, 4, 0, 4) == (1, "jxg_ld_sums_p32: n must be > 0")
+    st, msg = band(2, too_many, 2, 0, 2, 1)
+    assert st == 1 and msg.startswith("jxg_ld_band_mask_p32: at most 16 777 216 samples")
+    st, msg = sums(2, too_many, 2, 0, 2, 0, 2)
+    assert st == 1 and msg.startswith("jxg_ld_sums_p32: at most 16 777 216 samples")
+    for r0, r1 in ((-1, 3), (3, 2), (0, 5), (5, 5)):
+        assert band(4, 100, 4, r0, r1, 1) == (1, "jxg_ld_band_mask_p32: row range outside the row list"), (r0, r1)
+    for blk in ((-1, 2, 0, 2), (0, 5, 0, 2), (2, 1, 0, 2), (0, 2, -1, 2), (0, 2, 0, 5), (0, 2, 3, 2)):
+        assert sums(4, 100, 4, *blk) == (1, "jxg_ld_sums_p32: block outside the row list"), blk
+    for wpr in (0, -1, too_many):
+        assert band(4, 100, 4, 0, 1, wpr) == (1, "jxg_ld_band_mask_p32: words per mask row must be in [1, 2^24]"), wpr
+    assert band(4, 100, 0, 0, 0, 1)[0] == 1 and sums(4, 100, 0, 0, 0, 0, 0)[0] == 1      # no rows
+    # empty ranges inside the list: nothing to do, no device call
+    assert band(4, 100, 4, 2, 2, 1)[0] == 0
+    assert sums(4, 100, 4, 1, 1, 0, 4)[0] == 0 and sums(4, 100, 4, 0, 4, 3, 3)[0] == 0
