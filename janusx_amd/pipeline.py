@@ -14,6 +14,7 @@ from __future__ import annotations
 import math
 import os
 import time
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -388,8 +389,6 @@ class SpectralModel:
                                       _ptr(out3), _stream()))
         lbd, ml0, reml0 = [float(v) for v in out3.cpu().numpy()]
         self.null = self._profile(lbd, ml0, reml0)
-        self._planes = None
-        self._fv = None
 
     @classmethod
     def rotated(cls, s, u_t, xcov, y, device):
@@ -471,6 +470,23 @@ class SpectralModel:
             self._usamp = us
         return self._usamp
 
+    def warm_seed(self):
+        """log10 lambda0 clamped into the null bounds: the start of the per-SNP searches and the null ML; None unless lambda0 > 0."""
+        lo_b, hi_b = self.null.bounds
+        return min(max(math.log10(self.null.lbd), lo_b), hi_b) if self.null.lbd > 0 else None
+
+    def null_ml(self, max_iter, tol):
+        """-> (seed, null ML of the lmm2 scan): Brent on -ml_loglike, seeded with the REML optimum (src/stats/lmm.rs:2902-2921; the
+        workflow passes bounds, max_iter = 30, tol = 1e-2, init_log10_lbd_reml = log10 lambda0: workflow_model_stream.py:1499-1590)."""
+        o2 = torch.empty(2, dtype=torch.float64, device=self.S.device)
+        (lo_b, hi_b), init = self.null.bounds, self.warm_seed()
+        check(lib().jxg_lmm2_null_ml(_ptr(self.S), _ptr(self.xcov), _ptr(self.y), self.n, self.p, lo_b, hi_b, int(max_iter),
+                                     float(tol), 1 if init is not None else 0, float(init or 0.0), o2.data_ptr(), _stream()))
+        ml0 = float(o2.cpu().numpy()[1])
+        if not math.isfinite(ml0):
+            raise RuntimeError("failed to optimize null ML for LMM2 unified scan")
+        return init, ml0
+
     def fv_cache(self, log10_lbd=None):
         lbd = self.null.lbd if log10_lbd is None else 10.0 ** float(log10_lbd)
         if self._fv is None or self._fv[0] != lbd:
@@ -509,271 +525,111 @@ def _chain_segments(co, a, b, dev):
     return c0, torch.from_numpy(np.asarray(loc, dtype=np.int32)).to(dev)
 
 
-def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndarray, mode="lmm", low=None,
-              high=None, max_iter=30, tol=1e-2, init_log10_lbd=None, block_rows=None, return_evals=False,
-              times: StageTimes = None, nullml=None, fv_state=None, on_block=None, chain_off=None, progress=None,
-              progress_every=0):
-    """Rotate + scan the given SNP rows. mode: 'lmm' (exact per-SNP REML), 'fvlmm' (fixed lambda) or 'lmm2' (REML Wald +
-    ML likelihood ratio, needs `nullml`).  Returns a (len(rows), 3) f64 device tensor [beta, se, p] -- 4 columns
-    [.., plrt] when `nullml` is given, 6 columns [beta, se, pwald, lambda, ml, plrt] for 'lmm2' -- (and the per-SNP
-    Brent evaluation counts).
-    block_rows: rows per rotation block; None = 8192, or 32768 for the exact scan beyond the LDS-resident limit.
-    chain_off ('lmm' only): offsets into `rows` (int64, 0 ... len(rows), ascending; `stats.warm_chain_offsets`) of the
-    reference's warm-start chains (src/stats/lmm.rs:134-161): inside a chain every SNP's Brent starts from the optimum of the
-    valid SNP before it, the first one from `init_log10_lbd` or the interval midpoint.  The rotation and the per-SNP series stay
-    parallel over all SNPs; the Brent searches run one wave per chain -- where the series form exists in ONE launch per
-    super-block (the series of at most SERIES_CAP_BYTES / (8 (series + 1 + columns)) rows, whole blocks, at least one; a chain cut
-    by a super-block continues from its carried state; `on_block` then receives the whole table at the end), block by block with
-    carried states otherwise.
-    progress(done, total): called after a block when `done` has advanced by `progress_every` rows (default: one block) since the
-    last call, and after the last block; an exception raised there ends the scan."""
-    dev = panel.device
-    n = model.n
-    if panel.n != n:
-        raise RuntimeError(f"selected sample count {panel.n} != model n {n}")
-    mk = len(rows)
-    with_plrt = 1 if nullml is not None else 0
-    nullml_v = float(nullml) if nullml is not None else 0.0
-    if mode == "lmm2" and nullml is None:
-        raise RuntimeError("lmm2 needs the null ML (nullml)")
-    out = torch.empty((mk, 6 if mode == "lmm2" else (4 if with_plrt else 3)), dtype=torch.float64, device=dev)
-    evals = torch.zeros(mk, dtype=torch.int32, device=dev) if return_evals else None
-    if mk == 0:
-        return (out, evals) if return_evals else out
-    rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-    lut_t = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32)).to(dev)
-    hi, lo, usum = model.planes()
-    # int8 planes of the eigenvectors for the exact-row tiles of full-size blocks (k_rotate_i8.hip)
-    # From n = 4096 the int8 / 256-tile rotation kernels write G~ and the fixed-lambda scans read it back (10 ms per 200 000
-    # SNPs at n = 20 000) instead of the fused epilogue of the 128-tile fp16 kernel: 225 vs 360 ms for the scan of `-fvlmm` at
-    # BASELINE configs[2].  JXGPU_FVLMM_FUSED=2 keeps the fused form at every size.
-    use_q = n >= 4096 and os.environ.get("JXGPU_ROT_I8", "1") != "0"
-    if mode in ("fvlmm", "splmm") and os.environ.get("JXGPU_FVLMM_FUSED", "1").strip() == "2" and _fused_fixed_lambda(model.p):
-        use_q = False
-    qpl = model.qplanes() if use_q else None
-    # one-off per call: fp16 hi/lo LUT records (range-checked; rows without missing calls as integer LUT + offset, see
-    # jxg_lut_split_rows) and, for the exact scan, the Chebyshev tables of the lambda-only REML sums; the block loop
-    # below then only launches kernels (no allocation, no host sync).
-    lut16 = torch.empty((mk, 16), dtype=torch.uint8, device=dev)
-    rowoff = torch.empty(mk, dtype=torch.float32, device=dev)
-    # rows with a few missing calls keep the exact (int8) rotation and get their missing-call term added behind it
-    # (jxg_rotate_missing_correct: d * the sum of the missing samples' rows of U); only where the int8 rotation runs
-    # The limit is decided from a statistic of the PANEL (mean missing calls over all its rows, cached), never from the rows of
-    # this call: a row takes the same path -- and gets the same bits -- in chunked, unchunked and rank-sharded scans (the mirror's
-    # packed entry points build their panel from the rows they are handed).
-    miss_max = 0
-    if qpl is not None:
-        miss_max = int(lib().jxg_rot_miss_max(n, panel.mean_missing()))
-    rowmiss = torch.zeros(mk, dtype=torch.float32, device=dev) if miss_max > 0 else None
-    check(lib().jxg_lut_split_rows_m(_ptr(panel.p32), panel.m, n, _ptr(rows_t), _ptr(lut_t), mk, _ptr(lut16),
-                                     _ptr(rowoff), _ptr(rowmiss) if rowmiss is not None else None, miss_max, _stream()))
-    if rowmiss is not None and not bool((rowmiss != 0).any().item()):
-        rowmiss = None
-    # the missing-call term as one more int8 product (jxg_rotate_missing_dense) when the limit is "none" (> 256: more than n / 300
-    # missing calls per row on average), else as a gather per missing call over U with one row per sample
-    miss_dense = rowmiss is not None and miss_max > 256
-    usamp = model.usamp() if (rowmiss is not None and not miss_dense) else None
-    sel_miss_t, sel_miss_bounds = None, []
-    tables = None
-    if mode == "splmm" and fv_state is None:
-        raise RuntimeError("the SparseLMM exact scan needs its null state (fv_state = w, py, wx, a_chol, ypy)")
-    if mode == "lmm2":
-        lo_b, hi_b = model.null.bounds if low is None else (float(low), float(high))
-        warm = 1 if init_log10_lbd is not None else 0
-        init = float(init_log10_lbd) if init_log10_lbd is not None else 0.0
-    elif mode == "lmm":
-        lo_b, hi_b = model.null.bounds if low is None else (float(low), float(high))
-        warm = 1 if init_log10_lbd is not None else 0
-        init = float(init_log10_lbd) if init_log10_lbd is not None else 0.0
-        nbytes = int(lib().jxg_lmm_tables_bytes(n, model.p, lo_b, hi_b))
-        if nbytes > 0:
-            tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            check(lib().jxg_lmm_tables_build(_ptr(model.S), _ptr(model.xcov), _ptr(model.y), n, model.p, lo_b, hi_b,
-                                             _ptr(tables), _stream()))
-        if chain_off is not None:
-            co = np.ascontiguousarray(chain_off, dtype=np.int64)
-            if co.ndim != 1 or len(co) < 2 or co[0] != 0 or co[-1] != mk or np.any(np.diff(co) < 0):
-                raise RuntimeError("chain_off must ascend from 0 to len(rows)")
-            carry = torch.full((len(co) - 1,), init if warm else float("nan"), dtype=torch.float64, device=dev)
-            sd = int(lib().jxg_lmm_series_doubles(model.p, lo_b, hi_b)) if tables is not None else 0
-    elif mode == "splmm":
-        # null state on the K + lambda I scale, formed in f64 by the caller without the 1e-6 ridge jxg_fvlmm_prepare puts
-        # on X'WX (fvlmm.rs): at the large lambda of a trait without polygenic signal that ridge is a 1e-4 relative error
-        w, py, wx, a_chol, ypy = fv_state
-        a_dev = torch.from_numpy(np.ascontiguousarray(a_chol, dtype=np.float64)).to(dev)
-    else:
-        lbd, w, py, wx, a_chol, ypy, log_det_v, df = model.fv_cache(init_log10_lbd)
-        a_dev = torch.from_numpy(a_chol).to(dev)
-    if block_rows is None:
-        # beyond the LDS-resident limit the exact scan runs its tiled form: one workgroup per CU walks a queue of SNPs in
-        # lock step over LDS tiles of (s, X~, y~); longer blocks keep every wave's queue deep (8 SNPs per wave)
-        block_rows = 32768 if mode == "lmm" and (8 * n * (2 + model.p) > 156 * 1024 or model.p + 1 > 4) else 8192
-    br = int(min(block_rows, mk))
-    if miss_dense:
-        # per block: positions of the rows with a missing-call term (a row's path does not depend on the blocking)
-        has = (rowmiss != 0).cpu().numpy()
-        parts, nm_ = [], 0
-        for b0 in range(0, mk, br):
-            a = np.flatnonzero(has[b0:b0 + br]).astype(np.int32)
-            sel_miss_bounds.append((nm_, nm_ + len(a)))
-            nm_ += len(a)
-            parts.append(a)
-        sel_miss_t = torch.from_numpy(np.concatenate(parts) if nm_ else np.zeros(1, np.int32)).to(dev)
-    chain_series = mode == "lmm" and chain_off is not None and sd > 0
-    if chain_series:
-        cap = SERIES_CAP_BYTES // (8 * (sd + 1 + out.shape[1]))
-        sb_rows, sb0 = min(mk, max(br, cap // br * br)), 0     # rows per super-block; first row of the open one
-        scoef = torch.empty((sb_rows, sd), dtype=torch.float64, device=dev)
-        sssq = torch.empty(sb_rows, dtype=torch.float64, device=dev)
-    nbuf = 2 if mk > br else 1
-    fused = mode in ("fvlmm", "splmm") and _fused_fixed_lambda(model.p) and qpl is None
-    if qpl is not None:
-        # per block: positions of the exact rows (finite row offset: int8 rotation) and of the others (fp16 rotation); a row's
-        # path does not depend on the blocking, so chunked scans stay bit-identical to unchunked ones
-        n_inexact = int(torch.isnan(rowoff).sum().item())
-        se, sr, sel_bounds = [], [], []
-        ne = nx = 0
-        if n_inexact == 0:
-            # every row exact (a panel without missing calls): identity lists, nothing to build
-            for b0 in range(0, mk, br):
-                sel_bounds.append((0, min(br, mk - b0), 0, 0))
-            sel_exact_t = sel_rest_t = None
-        else:
-            ex = ~np.isnan(rowoff.cpu().numpy())
-            for b0 in range(0, mk, br):
-                blk = ex[b0:b0 + br]
-                a, b = np.flatnonzero(blk).astype(np.int32), np.flatnonzero(~blk).astype(np.int32)
-                sel_bounds.append((ne, ne + len(a), nx, nx + len(b)))
-                ne, nx = ne + len(a), nx + len(b)
-                se.append(a)
-                sr.append(b)
-            sel_exact_t = torch.from_numpy(np.concatenate(se) if ne else np.zeros(1, np.int32)).to(dev)
-            sel_rest_t = torch.from_numpy(np.concatenate(sr) if nx else np.zeros(1, np.int32)).to(dev)
-    if fused:
-        sums = [torch.empty((panel.nt, br, model.p + 2), dtype=torch.float64, device=dev) for _ in range(nbuf)]
-        grots = [None] * nbuf
-    else:
-        grots = [torch.empty((br, n), dtype=torch.float32, device=dev) for _ in range(nbuf)]
-    ev_rot = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range((mk + br - 1) // br)]
-    ev_scan = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(len(ev_rot))]
-    pending = None          # (i0, i1, event recorded behind the block's scan)
-    copy_stream = torch.cuda.Stream(device=dev) if on_block is not None else None
-    step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
+def _block_positions(mask, br, dev):
+    """Per block of `br` rows the positions inside the block at which `mask` holds -> per block (int32 device tensor of them, a
+    view of one upload, or None; their number)."""
+    parts = [np.flatnonzero(mask[b0:b0 + br]).astype(np.int32) for b0 in range(0, len(mask), br)]
+    t = torch.from_numpy(np.concatenate(parts)).to(dev)
+    ends = np.cumsum([len(a) for a in parts]).tolist()
+    return [(t[e - len(a):] if len(a) else None, len(a)) for a, e in zip(parts, ends)]
 
-    def hand_over(item):
-        i0, i1, ev = item
-        with torch.cuda.stream(copy_stream):
-            copy_stream.wait_event(ev)
-            host = out[i0:i1].to("cpu", non_blocking=False)
-        on_block(i0, host.numpy())
 
-    for bi, r0 in enumerate(range(0, mk, br)):
-        nr = min(br, mk - r0)
-        grot = grots[bi % nbuf]
-        if times is not None:
-            ev_rot[bi][0].record()
-        if fused:
-            sm = sums[bi % nbuf]
-            check(lib().jxg_rotate_packed16x_fused(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr,
-                                                   lut16[r0:].data_ptr(), rowoff[r0:].data_ptr(), _ptr(usum), _ptr(hi),
-                                                   _ptr(lo), SCALE_EXP, _ptr(w), _ptr(py), _ptr(wx), model.p, _ptr(sm),
-                                                   model.p + 2, 0, _stream()))
-        else:
-            if qpl is not None:
-                e0, e1, x0, x1 = sel_bounds[bi]
-                check(lib().jxg_rotate_packed16x_q(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr,
-                                                   lut16[r0:].data_ptr(), rowoff[r0:].data_ptr(), _ptr(usum), _ptr(hi), _ptr(lo),
-                                                   SCALE_EXP, _ptr(qpl[0]), _ptr(qpl[1]),
-                                                   sel_exact_t[e0:].data_ptr() if (sel_exact_t is not None and e1 > e0) else None,
-                                                   e1 - e0,
-                                                   sel_rest_t[x0:].data_ptr() if (sel_rest_t is not None and x1 > x0) else None,
-                                                   x1 - x0, _ptr(grot), _stream()))
-                if miss_dense:
-                    m0, m1 = sel_miss_bounds[bi]
-                    if m1 > m0:
-                        check(lib().jxg_rotate_missing_dense(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(),
-                                                             sel_miss_t[m0:].data_ptr(), m1 - m0, rowmiss[r0:].data_ptr(),
-                                                             _ptr(qpl[0]), _ptr(qpl[1]), _ptr(grot), n, _stream()))
-                elif rowmiss is not None:
-                    check(lib().jxg_rotate_missing_correct(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr,
-                                                           rowmiss[r0:].data_ptr(), _ptr(usamp), _ptr(grot), n, _stream()))
-            else:
-                check(lib().jxg_rotate_packed16x(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr,
-                                                 lut16[r0:].data_ptr(), rowoff[r0:].data_ptr(), _ptr(usum), _ptr(hi), _ptr(lo),
-                                                 SCALE_EXP, _ptr(grot), _stream()))
-        if times is not None:
-            ev_rot[bi][1].record()
-            ev_scan[bi][0].record()
-        o = out[r0:]
-        if fused:
-            if mode == "splmm":
-                check(lib().jxg_fvlmm_finish_dev(_ptr(sm), panel.nt, model.p + 2, nr, n, model.p, _ptr(a_dev), ypy, n - model.p, 0,
-                                                 0.0, 0.0, 1, o.data_ptr(), _stream()))
-            else:
-                check(lib().jxg_fvlmm_finish_dev(_ptr(sm), panel.nt, model.p + 2, nr, n, model.p, _ptr(a_dev), ypy, df, with_plrt,
-                                                 nullml_v, log_det_v, 0, o.data_ptr(), _stream()))
-        elif mode == "lmm2":
-            check(lib().jxg_lmm2_scan(_ptr(grot), nr, n, _ptr(model.S), _ptr(model.xcov), _ptr(model.y), model.p, lo_b,
-                                      hi_b, float(tol), int(max_iter), warm, init, nullml_v, o.data_ptr(), _stream()))
-        elif mode == "lmm" and chain_off is not None:
-            ev_p = evals[r0:].data_ptr() if evals is not None else None
-            if sd > 0:
-                # the series of this block behind those of the open super-block; when it is full or the rows end, its Brent
-                # searches: one launch over the chains that touch it
-                check(lib().jxg_lmm_series_coef_tab(_ptr(grot), nr, n, _ptr(model.xcov), model.p, lo_b, hi_b, _ptr(tables),
-                                                    scoef[r0 - sb0:].data_ptr(), sssq[r0 - sb0:].data_ptr(), _stream()))
-                if r0 + nr - sb0 >= sb_rows or r0 + nr >= mk:
-                    c0, loc_t = _chain_segments(co, sb0, r0 + nr, dev)
-                    check(lib().jxg_lmm_series_brent_tab(r0 + nr - sb0, n, _ptr(model.S), _ptr(model.xcov), model.p, lo_b, hi_b,
-                                                         _ptr(tables), float(tol), int(max_iter), 0, 0.0, _ptr(scoef), _ptr(sssq),
-                                                         _ptr(loc_t), len(loc_t) - 1, carry[c0:].data_ptr(), with_plrt, nullml_v,
-                                                         out[sb0:].data_ptr(),
-                                                         evals[sb0:].data_ptr() if evals is not None else None, _stream()))
-                    sb0 = r0 + nr
-            else:
-                # no series form (wide bounds, many covariates): the chains that touch this block, states carried across blocks
-                c0, loc_t = _chain_segments(co, r0, r0 + nr, dev)
-                check(lib().jxg_lmm_scan_chain(_ptr(grot), nr, n, _ptr(model.S), _ptr(model.xcov), _ptr(model.y), model.p, lo_b,
-                                               hi_b, float(tol), int(max_iter), _ptr(loc_t), len(loc_t) - 1, carry[c0:].data_ptr(),
-                                               with_plrt, nullml_v, o.data_ptr(), ev_p, _stream()))
-        elif mode == "lmm":
-            ev_p = evals[r0:].data_ptr() if evals is not None else None
-            if tables is not None:
-                check(lib().jxg_lmm_scan_tab(_ptr(grot), nr, n, _ptr(model.S), _ptr(model.xcov), model.p, lo_b, hi_b,
-                                             _ptr(tables), float(tol), int(max_iter), warm, init, with_plrt, nullml_v,
-                                             o.data_ptr(), ev_p, _stream()))
-            else:
-                check(lib().jxg_lmm_scan_exact(_ptr(grot), nr, n, _ptr(model.S), _ptr(model.xcov), _ptr(model.y),
-                                               model.p, lo_b, hi_b, float(tol), int(max_iter), warm, init, with_plrt,
-                                               nullml_v, o.data_ptr(), ev_p, _stream()))
-        elif mode == "splmm":   # score-form test with the null sigma2 = yPy / (n - p) (src/stats/splmm.rs:2567-2880)
-            check(lib().jxg_splmm_exact_scan_dev(_ptr(grot), nr, n, model.p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev),
-                                                 ypy, n - model.p, o.data_ptr(), _stream()))
-        else:
-            check(lib().jxg_fvlmm_scan_dev(_ptr(grot), nr, n, model.p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev),
-                                           ypy, df, with_plrt, nullml_v, log_det_v, o.data_ptr(), _stream()))
-        if times is not None:
-            ev_scan[bi][1].record()
-        if on_block is not None and not chain_series:
-            done = torch.cuda.Event()
-            done.record()
-            if pending is not None:
-                hand_over(pending)       # the previous block, while this one runs
-            pending = (r0, r0 + nr, done)
-        if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
-            last_tick = r0 + nr
-            progress(r0 + nr, mk)
-    if chain_series and on_block is not None:
-        done = torch.cuda.Event()
-        done.record()
-        pending = (0, mk, done)
-    if pending is not None:
-        hand_over(pending)
-    if times is not None:
-        torch.cuda.synchronize()
-        times.add("rotate", sum(a.elapsed_time(b) for a, b in ev_rot) * 1e-3)
-        times.add("scan", sum(a.elapsed_time(b) for a, b in ev_scan) * 1e-3)
-    return (out, evals) if return_evals else out
+class _Fp16Rotation:
+    """What the two rotation stages share: rows and LUT records of a call on the device, and the fp16 hi / lo launches over the
+    `parts` (offset, nb, hi, lo, panel) of an eigenbasis -- one part for a dense basis, the diagonal blocks otherwise."""
+    int8 = False
+
+    def _upload(self, rows, lut, dev):
+        self.rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+        self.lut16 = torch.empty((len(rows), 16), dtype=torch.uint8, device=dev)
+        return torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32)).to(dev)
+
+    def rotate(self, grot, r0, nr, rowoff_p=None, usum_p=None):
+        """G~ of the rows [r0, r0 + nr) -> grot (>= nr, n) f32: every part writes its columns."""
+        rows_p, lut_p = self.rows_t[r0:].data_ptr(), self.lut16[r0:].data_ptr()
+        for off, nb, hi, lo, panel in self.parts:
+            check(lib().jxg_rotate_packed16x_ld(_ptr(panel.p32), panel.m, nb, rows_p, nr, lut_p, rowoff_p, usum_p, _ptr(hi), _ptr(lo),
+                                                SCALE_EXP, grot[:, off:].data_ptr(), self.n, _stream()))
+
+    def fused_sums(self, sums, r0, nr, w, py, wx, p, rowoff_p=None, usum_p=None):
+        """Fused sums of the rows [r0, r0 + nr) against w, Py~, WX~ -> sums (tiles, >= nr, p + 2) f64; G~ is never written."""
+        rows_p, lut_p = self.rows_t[r0:].data_ptr(), self.lut16[r0:].data_ptr()
+        t0 = 0
+        for off, nb, hi, lo, panel in self.parts:
+            check(lib().jxg_rotate_packed16x_fused(_ptr(panel.p32), panel.m, nb, rows_p, nr, lut_p, rowoff_p, usum_p, _ptr(hi),
+                                                   _ptr(lo), SCALE_EXP, w[off:].data_ptr(), py[off:].data_ptr(), wx[off:].data_ptr(),
+                                                   p, _ptr(sums), p + 2, t0, _stream()))
+            t0 += panel.nt
+
+
+class DenseRotation(_Fp16Rotation):
+    """Rotation stage of a dense eigenbasis for the SNP rows of one call in blocks of `block_rows`: what decides the kernel a row
+    takes is fixed here, once; `rotate` / `fused_sums` then only launch (no allocation, no host sync), and a row gets the same bits
+    whatever block, chunk or rank it lands in.  fixed_lambda: for fvlmm / SparseLMM exact; int8=False: the fp16 kernel at every n."""
+
+    def __init__(self, panel: Panel, model: SpectralModel, rows, lut, block_rows, fixed_lambda=False, int8=True):
+        dev, mk, n, br = panel.device, len(rows), model.n, int(block_rows)
+        self.panel, self.n, self.br, self.tiles = panel, n, br, panel.nt
+        lut_t = self._upload(rows, lut, dev)
+        self.hi, self.lo, self.usum = model.planes()
+        self.parts = [(0, n, self.hi, self.lo, panel)]
+        # int8 planes of the eigenvectors for the exact-row tiles of full-size blocks (k_rotate_i8.hip)
+        # From n = 4096 the int8 / 256-tile rotation kernels write G~ and the fixed-lambda scans read it back (10 ms per 200 000
+        # SNPs at n = 20 000) instead of the fused epilogue of the 128-tile fp16 kernel: 225 vs 360 ms for the scan of `-fvlmm` at
+        # BASELINE configs[2].  JXGPU_FVLMM_FUSED=2 keeps the fused form at every size.
+        use_q = int8 and n >= 4096 and os.environ.get("JXGPU_ROT_I8", "1") != "0"
+        if fixed_lambda and os.environ.get("JXGPU_FVLMM_FUSED", "1").strip() == "2" and _fused_fixed_lambda(model.p):
+            use_q = False
+        self.int8, self.qpl = use_q, (model.qplanes() if use_q else None)
+        # fp16 hi/lo LUT records (range-checked; rows without missing calls as integer LUT + offset, see jxg_lut_split_rows)
+        self.rowoff = torch.empty(mk, dtype=torch.float32, device=dev)
+        # rows with a few missing calls keep the exact (int8) rotation and get their missing-call term added behind it
+        # (jxg_rotate_missing_correct: d * the sum of the missing samples' rows of U); only where the int8 rotation runs
+        # The limit is decided from a statistic of the PANEL (mean missing calls over all its rows, cached), never from the rows of
+        # this call: a row takes the same path -- and gets the same bits -- in chunked, unchunked and rank-sharded scans (the mirror's
+        # packed entry points build their panel from the rows they are handed).
+        miss_max = int(lib().jxg_rot_miss_max(n, panel.mean_missing())) if use_q else 0
+        rowmiss = torch.zeros(mk, dtype=torch.float32, device=dev) if miss_max > 0 else None
+        check(lib().jxg_lut_split_rows_m(_ptr(panel.p32), panel.m, n, _ptr(self.rows_t), _ptr(lut_t), mk, _ptr(self.lut16),
+                                         _ptr(self.rowoff), _ptr(rowmiss), miss_max, _stream()))
+        self.rowmiss = rowmiss = rowmiss if (rowmiss is not None and bool((rowmiss != 0).any().item())) else None
+        # the missing-call term as one more int8 product (jxg_rotate_missing_dense) when the limit is "none" (> 256: more than n / 300
+        # missing calls per row on average), else as a gather per missing call over U with one row per sample
+        self.miss_dense = rowmiss is not None and miss_max > 256
+        self.usamp = model.usamp() if (rowmiss is not None and not self.miss_dense) else None
+        # per block: positions of the rows with a missing-call term, of the exact rows (finite row offset: int8 rotation) and of
+        # the others (fp16 rotation); a row's path does not depend on the blocking, so chunked scans stay bit-identical to
+        # unchunked ones
+        self.sel_miss = _block_positions((rowmiss != 0).cpu().numpy(), br, dev) if self.miss_dense else None
+        if use_q and int(torch.isnan(self.rowoff).sum().item()) == 0:
+            # every row exact (a panel without missing calls): identity lists (NULL), nothing to build
+            self.sel_exact = [(None, min(br, mk - b0)) for b0 in range(0, mk, br)]
+            self.sel_rest = [(None, 0)] * len(self.sel_exact)
+        elif use_q:
+            ex = ~np.isnan(self.rowoff.cpu().numpy())
+            self.sel_exact, self.sel_rest = _block_positions(ex, br, dev), _block_positions(~ex, br, dev)
+
+    def rotate(self, grot, r0, nr):
+        panel, n = self.panel, self.n
+        rows_p, lut_p, off_p = self.rows_t[r0:].data_ptr(), self.lut16[r0:].data_ptr(), self.rowoff[r0:].data_ptr()
+        if not self.int8:
+            return super().rotate(grot, r0, nr, off_p, _ptr(self.usum))
+        bi = r0 // self.br
+        (ex, ne), (rs, nx) = self.sel_exact[bi], self.sel_rest[bi]
+        check(lib().jxg_rotate_packed16x_q(_ptr(panel.p32), panel.m, n, rows_p, nr, lut_p, off_p, _ptr(self.usum), _ptr(self.hi),
+                                           _ptr(self.lo), SCALE_EXP, _ptr(self.qpl[0]), _ptr(self.qpl[1]), _ptr(ex), ne, _ptr(rs), nx,
+                                           _ptr(grot), _stream()))
+        if self.miss_dense:
+            sel, nm = self.sel_miss[bi]
+            if nm > 0:
+                check(lib().jxg_rotate_missing_dense(_ptr(panel.p32), panel.m, n, rows_p, _ptr(sel), nm, self.rowmiss[r0:].data_ptr(),
+                                                     _ptr(self.qpl[0]), _ptr(self.qpl[1]), _ptr(grot), n, _stream()))
+        elif self.rowmiss is not None:
+            check(lib().jxg_rotate_missing_correct(_ptr(panel.p32), panel.m, n, rows_p, nr, self.rowmiss[r0:].data_ptr(),
+                                                   _ptr(self.usamp), _ptr(grot), n, _stream()))
+
+    def fused_sums(self, sums, r0, nr, w, py, wx, p):
+        super().fused_sums(sums, r0, nr, w, py, wx, p, self.rowoff[r0:].data_ptr(), _ptr(self.usum))
 
 
 class BlockRotation:
@@ -804,47 +660,233 @@ class BlockRotation:
         self.device = dev
 
 
+class BlockDiagRotation(_Fp16Rotation):
+    """Rotation stage of a block-diagonal eigenbasis (`BlockRotation`) for the SNP rows of one call: the general hi / lo split of
+    every LUT, then per block of rows one fp16 launch per diagonal block (no row offsets, no int8 path)."""
+
+    def __init__(self, rot: BlockRotation, rows, lut):
+        self.parts, self.n = rot.parts, rot.n
+        self.tiles = int(sum(panel.nt for _o, _nb, _h, _l, panel in rot.parts))
+        lut_t = self._upload(rows, lut, rot.device)
+        check(lib().jxg_lut_split(_ptr(lut_t), len(rows), _ptr(self.lut16), _stream()))
+
+
+# What `_run_blocks` drives: a rotation stage, scan(buf, r0, nr) writing the rows [r0, r0 + nr) of the table from their block
+# buffer, whole_table (`on_block` gets the table once at the end) and fused = (w, py, wx, p) where that buffer holds the sums, not G~.
+_Scanner = namedtuple("_Scanner", "stage scan whole_table fused", defaults=(False, None))
+
+
+def _exact_scan(stage, model, out, evals, br, brent, max_iter, tol, nullml, chain_off):
+    """'lmm': exact per-SNP REML.  One-off: the Chebyshev tables of the lambda-only REML sums where they exist; with `chain_off`
+    the chains' carried states and, where the series form exists, the storage of one super-block of series."""
+    dev, mk, n, p = out.device, int(out.shape[0]), model.n, model.p
+    lo_b, hi_b, warm, init = brent
+    tol, max_iter = float(tol), int(max_iter)
+    with_plrt, nullml_v = (1, float(nullml)) if nullml is not None else (0, 0.0)
+    s_p, x_p, y_p, tables = _ptr(model.S), _ptr(model.xcov), _ptr(model.y), None
+    nbytes = int(lib().jxg_lmm_tables_bytes(n, p, lo_b, hi_b))
+    if nbytes > 0:
+        tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(lib().jxg_lmm_tables_build(s_p, x_p, y_p, n, p, lo_b, hi_b, _ptr(tables), _stream()))
+
+    ev_p = (lambda r0: evals[r0:].data_ptr()) if evals is not None else (lambda r0: None)      # noqa: E731
+    if chain_off is None:
+        def scan(grot, r0, nr):
+            if tables is not None:
+                check(lib().jxg_lmm_scan_tab(_ptr(grot), nr, n, s_p, x_p, p, lo_b, hi_b, _ptr(tables), tol, max_iter, warm, init,
+                                             with_plrt, nullml_v, out[r0:].data_ptr(), ev_p(r0), _stream()))
+            else:
+                check(lib().jxg_lmm_scan_exact(_ptr(grot), nr, n, s_p, x_p, y_p, p, lo_b, hi_b, tol, max_iter, warm, init,
+                                               with_plrt, nullml_v, out[r0:].data_ptr(), ev_p(r0), _stream()))
+        return _Scanner(stage, scan)
+    co = np.ascontiguousarray(chain_off, dtype=np.int64)
+    if co.ndim != 1 or len(co) < 2 or co[0] != 0 or co[-1] != mk or np.any(np.diff(co) < 0):
+        raise RuntimeError("chain_off must ascend from 0 to len(rows)")
+    carry = torch.full((len(co) - 1,), init if warm else float("nan"), dtype=torch.float64, device=dev)
+    sd = int(lib().jxg_lmm_series_doubles(p, lo_b, hi_b)) if tables is not None else 0
+    if sd == 0:
+        # no series form (wide bounds, many covariates): the chains that touch this block, states carried across blocks
+        def scan(grot, r0, nr):
+            c0, loc_t = _chain_segments(co, r0, r0 + nr, dev)
+            check(lib().jxg_lmm_scan_chain(_ptr(grot), nr, n, s_p, x_p, y_p, p, lo_b, hi_b, tol, max_iter, _ptr(loc_t),
+                                           len(loc_t) - 1, carry[c0:].data_ptr(), with_plrt, nullml_v, out[r0:].data_ptr(),
+                                           ev_p(r0), _stream()))
+        return _Scanner(stage, scan)
+    cap = SERIES_CAP_BYTES // (8 * (sd + 1 + out.shape[1]))
+    sb_rows, sb0 = min(mk, max(br, cap // br * br)), 0     # rows per super-block; first row of the open one
+    scoef = torch.empty((sb_rows, sd), dtype=torch.float64, device=dev)
+    sssq = torch.empty(sb_rows, dtype=torch.float64, device=dev)
+
+    def scan(grot, r0, nr):
+        # the series of this block behind those of the open super-block; when it is full or the rows end, its Brent
+        # searches: one launch over the chains that touch it
+        nonlocal sb0
+        check(lib().jxg_lmm_series_coef_tab(_ptr(grot), nr, n, x_p, p, lo_b, hi_b, _ptr(tables), scoef[r0 - sb0:].data_ptr(),
+                                            sssq[r0 - sb0:].data_ptr(), _stream()))
+        if r0 + nr - sb0 >= sb_rows or r0 + nr >= mk:
+            c0, loc_t = _chain_segments(co, sb0, r0 + nr, dev)
+            check(lib().jxg_lmm_series_brent_tab(r0 + nr - sb0, n, s_p, x_p, p, lo_b, hi_b, _ptr(tables), tol, max_iter, 0, 0.0,
+                                                 _ptr(scoef), _ptr(sssq), _ptr(loc_t), len(loc_t) - 1, carry[c0:].data_ptr(),
+                                                 with_plrt, nullml_v, out[sb0:].data_ptr(), ev_p(sb0), _stream()))
+            sb0 = r0 + nr
+    return _Scanner(stage, scan, whole_table=True)
+
+
+def _lmm2_scan(stage, model, out, brent, max_iter, tol, nullml):
+    """'lmm2': REML Wald + ML likelihood ratio against the null ML."""
+    lo_b, hi_b, warm, init = brent
+
+    def scan(grot, r0, nr):
+        check(lib().jxg_lmm2_scan(_ptr(grot), nr, model.n, _ptr(model.S), _ptr(model.xcov), _ptr(model.y), model.p, lo_b, hi_b,
+                                  float(tol), int(max_iter), warm, init, float(nullml), out[r0:].data_ptr(), _stream()))
+    return _Scanner(stage, scan)
+
+
+def _fixed_lambda_scan(stage, p, out, w, py, wx, a_chol, ypy, df, score, with_plrt=0, nullml=0.0, log_det_v=0.0):
+    """'fvlmm' / 'splmm' over a rotation stage of either basis.  Where the stage runs the fp16 kernel and `_fused_fixed_lambda`
+    allows it `jxg_fvlmm_finish_dev` finishes the fused sums; else `jxg_fvlmm_scan_dev` / `jxg_splmm_exact_scan_dev` read G~.
+    score: the SparseLMM exact scan -- score-form test with the null sigma2 = yPy / (n - p) (src/stats/splmm.rs:2567-2880)."""
+    n = stage.n
+    a_dev = torch.from_numpy(np.ascontiguousarray(a_chol, dtype=np.float64)).to(out.device)
+    if _fused_fixed_lambda(p) and not stage.int8:
+        def finish(sums, r0, nr):
+            check(lib().jxg_fvlmm_finish_dev(_ptr(sums), stage.tiles, p + 2, nr, n, p, _ptr(a_dev), ypy, df, with_plrt, nullml,
+                                             log_det_v, 1 if score else 0, out[r0:].data_ptr(), _stream()))
+        return _Scanner(stage, finish, fused=(w, py, wx, p))
+
+    def scan(grot, r0, nr):
+        if score:
+            check(lib().jxg_splmm_exact_scan_dev(_ptr(grot), nr, n, p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev), ypy, df,
+                                                 out[r0:].data_ptr(), _stream()))
+        else:
+            check(lib().jxg_fvlmm_scan_dev(_ptr(grot), nr, n, p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev), ypy, df, with_plrt,
+                                           nullml, log_det_v, out[r0:].data_ptr(), _stream()))
+    return _Scanner(stage, scan)
+
+
+def _splmm_scan(stage, p, out, fv_state):
+    # null state on the K + lambda I scale, formed in f64 by the caller without the 1e-6 ridge jxg_fvlmm_prepare puts
+    # on X'WX (fvlmm.rs): at the large lambda of a trait without polygenic signal that ridge is a 1e-4 relative error
+    w, py, wx, a_chol, ypy = fv_state
+    return _fixed_lambda_scan(stage, p, out, w, py, wx, a_chol, ypy, stage.n - p, True)
+
+
+def _run_blocks(scanner, out, br, nbuf=1, times: StageTimes = None, on_block=None, progress=None, progress_every=0):
+    """The block loop of the packed scans: rotate block b into one of `nbuf` buffers, scan it; stage times from events,
+    `on_block` on a copy stream one block behind, `progress`.  Only launches, no allocation and no host sync per block (the
+    chain forms upload the offsets of the chains that touch a block or super-block: `_chain_segments`)."""
+    stage, scan, whole_table, fused = scanner
+    mk = int(out.shape[0])
+    rotate = stage.rotate if fused is None else (lambda buf, r0, nr: stage.fused_sums(buf, r0, nr, *fused))
+    shape, dtype = ((br, stage.n), torch.float32) if fused is None else ((stage.tiles, br, fused[3] + 2), torch.float64)
+    bufs = [torch.empty(shape, dtype=dtype, device=out.device) for _ in range(nbuf)]
+    # per block the events around its rotation (0, 1) and around its scan (2, 3); only where stage times are asked for
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range((mk + br - 1) // br if times is not None else 0)]
+    pending = None          # (i0, i1, event recorded behind the block's scan)
+    copy_stream = torch.cuda.Stream(device=out.device) if on_block is not None else None
+    step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
+
+    def hand_over(item):
+        i0, i1, ev = item
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(ev)
+            host = out[i0:i1].to("cpu", non_blocking=False)
+        on_block(i0, host.numpy())
+
+    for bi, r0 in enumerate(range(0, mk, br)):
+        nr = min(br, mk - r0)
+        buf = bufs[bi % nbuf]
+        if ev:
+            ev[bi][0].record()
+        rotate(buf, r0, nr)
+        if ev:
+            ev[bi][1].record()
+            ev[bi][2].record()
+        scan(buf, r0, nr)
+        if ev:
+            ev[bi][3].record()
+        if on_block is not None and not whole_table:
+            done = torch.cuda.Event()
+            done.record()
+            if pending is not None:
+                hand_over(pending)       # the previous block, while this one runs
+            pending = (r0, r0 + nr, done)
+        if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
+            last_tick = r0 + nr
+            progress(r0 + nr, mk)
+    if whole_table and on_block is not None:
+        done = torch.cuda.Event()
+        done.record()
+        pending = (0, mk, done)
+    if pending is not None:
+        hand_over(pending)
+    if times is not None:
+        torch.cuda.synchronize()
+        times.add("rotate", sum(e[0].elapsed_time(e[1]) for e in ev) * 1e-3)
+        times.add("scan", sum(e[2].elapsed_time(e[3]) for e in ev) * 1e-3)
+
+
+def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndarray, mode="lmm", low=None,
+              high=None, max_iter=30, tol=1e-2, init_log10_lbd=None, block_rows=None, return_evals=False,
+              times: StageTimes = None, nullml=None, fv_state=None, on_block=None, chain_off=None, progress=None,
+              progress_every=0):
+    """Rotate + scan the given SNP rows. mode: 'lmm' (exact per-SNP REML), 'fvlmm' (fixed lambda) or 'lmm2' (REML Wald +
+    ML likelihood ratio, needs `nullml`).  Returns a (len(rows), 3) f64 device tensor [beta, se, p] -- 4 columns
+    [.., plrt] when `nullml` is given, 6 columns [beta, se, pwald, lambda, ml, plrt] for 'lmm2' -- (and the per-SNP
+    Brent evaluation counts).
+    block_rows: rows per rotation block; None = 8192, or 32768 for the exact scan beyond the LDS-resident limit.
+    chain_off ('lmm' only): offsets into `rows` (int64, 0 ... len(rows), ascending; `stats.warm_chain_offsets`) of the
+    reference's warm-start chains (src/stats/lmm.rs:134-161): inside a chain every SNP's Brent starts from the optimum of the
+    valid SNP before it, the first one from `init_log10_lbd` or the interval midpoint.  The rotation and the per-SNP series stay
+    parallel over all SNPs; the Brent searches run one wave per chain -- where the series form exists in ONE launch per
+    super-block (the series of at most SERIES_CAP_BYTES / (8 (series + 1 + columns)) rows, whole blocks, at least one; a chain cut
+    by a super-block continues from its carried state; `on_block` then receives the whole table at the end), block by block with
+    carried states otherwise.
+    progress(done, total): called after a block when `done` has advanced by `progress_every` rows (default: one block) since the
+    last call, and after the last block; an exception raised there ends the scan."""
+    dev, n = panel.device, model.n
+    if panel.n != n:
+        raise RuntimeError(f"selected sample count {panel.n} != model n {n}")
+    mk = len(rows)
+    with_plrt = 1 if nullml is not None else 0
+    if mode == "lmm2" and nullml is None:
+        raise RuntimeError("lmm2 needs the null ML (nullml)")
+    out = torch.empty((mk, 6 if mode == "lmm2" else (4 if with_plrt else 3)), dtype=torch.float64, device=dev)
+    evals = torch.zeros(mk, dtype=torch.int32, device=dev) if return_evals else None
+    if mk == 0:
+        return (out, evals) if return_evals else out
+    if block_rows is None:
+        # beyond the LDS-resident limit the exact scan runs its tiled form: one workgroup per CU walks a queue of SNPs in
+        # lock step over LDS tiles of (s, X~, y~); longer blocks keep every wave's queue deep (8 SNPs per wave)
+        block_rows = 32768 if mode == "lmm" and (8 * n * (2 + model.p) > 156 * 1024 or model.p + 1 > 4) else 8192
+    br = int(min(block_rows, mk))
+    stage = DenseRotation(panel, model, rows, lut, br, fixed_lambda=mode in ("fvlmm", "splmm"))
+    if mode in ("lmm", "lmm2"):     # (low, high, warm, init) of the Brent searches
+        brent = (*(model.null.bounds if low is None else (float(low), float(high))),
+                 int(init_log10_lbd is not None), float(init_log10_lbd or 0.0))
+    if mode == "lmm2":
+        scanner = _lmm2_scan(stage, model, out, brent, max_iter, tol, nullml)
+    elif mode == "lmm":
+        scanner = _exact_scan(stage, model, out, evals, br, brent, max_iter, tol, nullml, chain_off)
+    elif mode == "splmm":
+        if fv_state is None:
+            raise RuntimeError("the SparseLMM exact scan needs its null state (fv_state = w, py, wx, a_chol, ypy)")
+        scanner = _splmm_scan(stage, model.p, out, fv_state)
+    else:
+        lbd, w, py, wx, a_chol, ypy, log_det_v, df = model.fv_cache(init_log10_lbd)
+        scanner = _fixed_lambda_scan(stage, model.p, out, w, py, wx, a_chol, ypy, df, False, with_plrt,
+                                     float(nullml) if nullml is not None else 0.0, log_det_v)
+    _run_blocks(scanner, out, br, 2 if mk > br else 1, times, on_block, progress, progress_every)
+    return (out, evals) if return_evals else out
+
+
 def scan_rows_splmm_blocks(rot: BlockRotation, p: int, rows: np.ndarray, lut: np.ndarray, fv_state, block_rows=8192):
     """SparseLMM exact scan (`jxg_splmm_exact_scan_dev`, src/stats/splmm.rs:2567-2880) over rows rotated by a block-diagonal
     eigenbasis: per block of SNP rows one rotation launch per diagonal block, then the score-form scan over the full
-    rotated rows.  Returns (len(rows), 3) f64 [beta, se, p] on the device."""
-    dev = rot.device
-    n, mk = rot.n, len(rows)
-    out = torch.empty((mk, 3), dtype=torch.float64, device=dev)
-    if mk == 0:
-        return out
-    rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-    lut_t = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32)).to(dev)
-    lut16 = torch.empty((mk, 16), dtype=torch.uint8, device=dev)
-    check(lib().jxg_lut_split(_ptr(lut_t), mk, _ptr(lut16), _stream()))      # general rows: hi / lo split of every LUT
-    w, py, wx, a_chol, ypy = fv_state
-    a_dev = torch.from_numpy(np.ascontiguousarray(a_chol, dtype=np.float64)).to(dev)
-    br = int(min(block_rows, mk))
-    if _fused_fixed_lambda(p):
-        # every column tile of every diagonal block writes its share of the three weighted sums; G~ is never written
-        tiles = int(sum(panel.nt for _o, _nb, _h, _l, panel in rot.parts))
-        sums = torch.empty((tiles, br, p + 2), dtype=torch.float64, device=dev)
-        for r0 in range(0, mk, br):
-            nr = min(br, mk - r0)
-            t0 = 0
-            for off, nb, hi, lo, panel in rot.parts:
-                check(lib().jxg_rotate_packed16x_fused(_ptr(panel.p32), panel.m, nb, rows_t[r0:].data_ptr(), nr,
-                                                       lut16[r0:].data_ptr(), None, None, _ptr(hi), _ptr(lo), SCALE_EXP,
-                                                       w[off:].data_ptr(), py[off:].data_ptr(), wx[off:].data_ptr(), p,
-                                                       _ptr(sums), p + 2, t0, _stream()))
-                t0 += panel.nt
-            check(lib().jxg_fvlmm_finish_dev(_ptr(sums), tiles, p + 2, nr, n, p, _ptr(a_dev), ypy, n - p, 0, 0.0, 0.0, 1,
-                                             out[r0:].data_ptr(), _stream()))
-        return out
-    grot = torch.empty((br, n), dtype=torch.float32, device=dev)
-    for r0 in range(0, mk, br):
-        nr = min(br, mk - r0)
-        for off, nb, hi, lo, panel in rot.parts:
-            check(lib().jxg_rotate_packed16x_ld(_ptr(panel.p32), panel.m, nb, rows_t[r0:].data_ptr(), nr,
-                                                lut16[r0:].data_ptr(), None, None, _ptr(hi), _ptr(lo), SCALE_EXP,
-                                                grot[:, off:].data_ptr(), n, _stream()))
-        check(lib().jxg_splmm_exact_scan_dev(_ptr(grot), nr, n, p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev), ypy, n - p,
-                                             out[r0:].data_ptr(), _stream()))
+    rotated rows (fused: the finish of their sums).  Returns (len(rows), 3) f64 [beta, se, p] on the device."""
+    out = torch.empty((len(rows), 3), dtype=torch.float64, device=rot.device)
+    if len(rows):
+        _run_blocks(_splmm_scan(BlockDiagRotation(rot, rows, lut), p, out, fv_state), out, int(min(block_rows, len(rows))))
     return out
 
 
@@ -915,31 +957,15 @@ def scan_rows_splmm_factor(rows_f32, m: int, n: int, p: int, csr, diag: np.ndarr
 def rotate_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndarray) -> torch.Tensor:
     """G~ = G U for a (small) list of SNP rows, written out: (len(rows), n) f32 on the device (the fp16 hi / lo rotation of
     `scan_rows` without a scan behind it; used for the sampled markers of the SparseLMM gamma estimate)."""
-    dev, n, mk = panel.device, model.n, len(rows)
-    rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-    lut_t = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32)).to(dev)
-    hi, lo, usum = model.planes()
-    lut16 = torch.empty((mk, 16), dtype=torch.uint8, device=dev)
-    rowoff = torch.empty(mk, dtype=torch.float32, device=dev)
-    check(lib().jxg_lut_split_rows(_ptr(panel.p32), panel.m, n, _ptr(rows_t), _ptr(lut_t), mk, _ptr(lut16), _ptr(rowoff),
-                                   _stream()))
-    grot = torch.empty((mk, n), dtype=torch.float32, device=dev)
-    check(lib().jxg_rotate_packed16x(_ptr(panel.p32), panel.m, n, _ptr(rows_t), mk, _ptr(lut16), _ptr(rowoff), _ptr(usum),
-                                     _ptr(hi), _ptr(lo), SCALE_EXP, _ptr(grot), _stream()))
+    grot = torch.empty((len(rows), model.n), dtype=torch.float32, device=panel.device)
+    DenseRotation(panel, model, rows, lut, len(rows), int8=False).rotate(grot, 0, len(rows))
     return grot
 
 
 def rotate_rows_blocks(rot: BlockRotation, rows: np.ndarray, lut: np.ndarray) -> torch.Tensor:
     """`rotate_rows` for a block-diagonal eigenbasis: every diagonal block writes its columns of the rotated rows."""
-    dev, n, mk = rot.device, rot.n, len(rows)
-    rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
-    lut_t = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.float32)).to(dev)
-    lut16 = torch.empty((mk, 16), dtype=torch.uint8, device=dev)
-    check(lib().jxg_lut_split(_ptr(lut_t), mk, _ptr(lut16), _stream()))
-    grot = torch.empty((mk, n), dtype=torch.float32, device=dev)
-    for off, nb, hi, lo, panel in rot.parts:
-        check(lib().jxg_rotate_packed16x_ld(_ptr(panel.p32), panel.m, nb, _ptr(rows_t), mk, _ptr(lut16), None, None, _ptr(hi),
-                                            _ptr(lo), SCALE_EXP, grot[:, off:].data_ptr(), n, _stream()))
+    grot = torch.empty((len(rows), rot.n), dtype=torch.float32, device=rot.device)
+    BlockDiagRotation(rot, rows, lut).rotate(grot, 0, len(rows))
     return grot
 
 
@@ -1126,31 +1152,22 @@ def run_trait(packed: torch.Tensor, n_samples: int, k: torch.Tensor, keep_idx, y
             res.model_tag, res.null_lrt = "lm", lrt
             return res
     on_block = on_rows(keep, af[rows], miss[rows], 6 if mode == "lmm2" else 3, mode) if on_rows is not None else None
-    if mode == "lmm":
-        init = math.log10(model.null.lbd) if (warm_start and model.null.lbd > 0) else None
-        if init is not None:
-            init = min(max(init, model.null.bounds[0]), model.null.bounds[1])
-        out = scan_rows(panel, model, rows, lut, "lmm", max_iter=max_iter, tol=tol, init_log10_lbd=init, on_block=on_block,
-                        chain_off=chain_off)
-    elif mode == "lmm2":
-        # null ML by Brent on -ml_loglike, seeded with the REML optimum (src/stats/lmm.rs:2902-2921; the workflow passes
-        # bounds, max_iter = 30, tol = 1e-2 and init_log10_lbd_reml = log10 lambda0: workflow_model_stream.py:1499-1590)
-        o2 = torch.empty(2, dtype=torch.float64, device=packed.device)
-        lo_b, hi_b = model.null.bounds
-        init = min(max(math.log10(model.null.lbd), lo_b), hi_b) if model.null.lbd > 0 else None
-        check(lib().jxg_lmm2_null_ml(_ptr(model.S), _ptr(model.xcov), _ptr(model.y), n, model.p, lo_b, hi_b, int(max_iter),
-                                     float(tol), 1 if init is not None else 0, float(init or 0.0), o2.data_ptr(),
-                                     _stream()))
-        ml0 = float(o2.cpu().numpy()[1])
-        if not math.isfinite(ml0):
-            raise RuntimeError("failed to optimize null ML for LMM2 unified scan")
-        out = scan_rows(panel, model, rows, lut, "lmm2", max_iter=max_iter, tol=tol, init_log10_lbd=init, nullml=ml0,
-                        on_block=on_block)
-    else:
-        out = scan_rows(panel, model, rows, lut, "fvlmm", on_block=on_block)
+    out = _scan_trait(panel, model, rows, lut, mode, max_iter, tol, warm_start, chain_off, on_block)
     res = GwasResult(keep, af[rows], miss[rows], out.cpu().numpy(), model.null, 0, {})
     res.model_tag, res.null_lrt = mode, lrt
     return res
+
+
+def _scan_trait(panel, model, rows, lut, mode, max_iter, tol, warm_start, chain_off, on_block=None):
+    """One trait's scan with the seeds of its route: 'lmm' from log10 lambda0 when `warm_start`, 'lmm2' always, with the null ML."""
+    if mode == "lmm":
+        return scan_rows(panel, model, rows, lut, "lmm", max_iter=max_iter, tol=tol, on_block=on_block, chain_off=chain_off,
+                         init_log10_lbd=model.warm_seed() if warm_start else None)
+    if mode == "lmm2":
+        init, ml0 = model.null_ml(max_iter, tol)
+        return scan_rows(panel, model, rows, lut, "lmm2", max_iter=max_iter, tol=tol, init_log10_lbd=init, nullml=ml0,
+                         on_block=on_block)
+    return scan_rows(panel, model, rows, lut, "fvlmm", on_block=on_block)
 
 
 def _run_trait_ranks(panel, model, counts, keep, af, miss, rows, y, x, mode, max_iter, tol, warm_start, on_rows, force_model,
@@ -1181,24 +1198,7 @@ def _run_trait_ranks(panel, model, counts, keep, af, miss, rows, y, x, mode, max
         out = scan_rows_lm(panel, mine, af[mine], x, y)[:, :3].contiguous()
     else:
         lut = st.scan_lut_from_counts(af[mine], np.zeros(len(mine), dtype=bool), counts[mine], n)
-        init, nullml = None, None
-        lo_b, hi_b = model.null.bounds
-        if mode == "lmm" and warm_start and model.null.lbd > 0:
-            init = min(max(math.log10(model.null.lbd), lo_b), hi_b)
-        if mode == "lmm2":
-            o2 = torch.empty(2, dtype=torch.float64, device=panel.device)
-            init = min(max(math.log10(model.null.lbd), lo_b), hi_b) if model.null.lbd > 0 else None
-            check(lib().jxg_lmm2_null_ml(_ptr(model.S), _ptr(model.xcov), _ptr(model.y), n, model.p, lo_b, hi_b, int(max_iter),
-                                         float(tol), 1 if init is not None else 0, float(init or 0.0), o2.data_ptr(),
-                                         _stream()))
-            nullml = float(o2.cpu().numpy()[1])
-            if not math.isfinite(nullml):
-                raise RuntimeError("failed to optimize null ML for LMM2 unified scan")
-        if mode in ("lmm", "lmm2"):
-            out = scan_rows(panel, model, mine, lut, mode, max_iter=max_iter, tol=tol, init_log10_lbd=init, nullml=nullml,
-                            chain_off=my_chain if (mode == "lmm" and len(mine)) else None)
-        else:
-            out = scan_rows(panel, model, mine, lut, "fvlmm")
+        out = _scan_trait(panel, model, mine, lut, mode, max_iter, tol, warm_start, my_chain if len(mine) else None)
     out = _allgather_rows(out)
     keep_all, af_k, miss_k = keep, af[rows], miss_col
     if payload_sharded:       # the QC columns are per shard too: concatenate them in rank (= BED) order
@@ -1256,8 +1256,7 @@ def run_gwas(packed: torch.Tensor, n_samples: int, y: np.ndarray, covar: np.ndar
         if warm_chain is not None:       # the reference CLI's scan: chains over chunks of the file's rows, seeded with lambda0
             chain_off = st.warm_chain_offsets(st.warm_chain_blocks_bed(mine, panel.m, int(warm_chain[0])), len(mine),
                                               int(warm_chain[1]))
-            if model.null.lbd > 0:
-                init = min(max(math.log10(model.null.lbd), model.null.bounds[0]), model.null.bounds[1])
+            init = model.warm_seed()
         out = scan_rows(panel, model, mine, lut, "lmm", max_iter=max_iter, tol=tol, init_log10_lbd=init,
                         times=tm if timing else None, chain_off=chain_off)
     else:

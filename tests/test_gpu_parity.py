@@ -1195,6 +1195,14 @@ def _full_size_properties(oracle, oracle_c, n, m, missing, scan_cap, f32_consume
     fa = pipeline.scan_rows(panel, model, rows, lut, "fvlmm", block_rows=8192).cpu().numpy()
     fb = pipeline.scan_rows(panel, model, rows, lut, "fvlmm", block_rows=3000).cpu().numpy()
     assert np.array_equal(fa, fb)
+    # the SparseLMM exact scan behind the same rotation stage (null state at lambda0 on the model's own spectrum): same bits
+    from types import SimpleNamespace
+    from janusx_amd import janusx as jxrs
+    sp_state = jxrs._splmm_exact_null_state(SimpleNamespace(s=model.S.cpu().numpy(), xr=model.xcov.cpu().numpy(),
+                                                            yr=model.y.cpu().numpy(), s_dev=model.S), model.null.lbd)
+    sa = pipeline.scan_rows(panel, model, rows, lut, "splmm", fv_state=sp_state, block_rows=8192).cpu().numpy()
+    sb = pipeline.scan_rows(panel, model, rows, lut, "splmm", fv_state=sp_state, block_rows=100).cpu().numpy()
+    assert np.isfinite(sa).any() and sa.tobytes() == sb.tobytes(), "chunked SparseLMM exact scan differs from unchunked scan"
     # sample of SNPs against the oracle, given the same spectral inputs (S, Dh, X~, y~ from the GPU)
     pick = np.random.default_rng(0).choice(len(rows), 150, replace=False)
     pk = packed[torch.from_numpy(rows[pick]).to(dev)].cpu().numpy()
@@ -3113,6 +3121,18 @@ def test_splmm_block_route_matches_the_dense_route(oracle, tmp_path, monkeypatch
     assert np.max(np.abs(got[ok, 0] - ref[ok, 0]) / scale) < TOL and np.max(np.abs(got[ok, 1] - ref[ok, 1]) / ref[ok, 1]) < TOL
     lp = np.abs(np.log(np.maximum(got[ok, 2], 1e-300)) - np.log(np.maximum(ref[ok, 2], 1e-300)))
     assert np.max(lp / np.maximum(1.0, np.abs(np.log(np.maximum(ref[ok, 2], 1e-300))))) < 10 * TOL
+    # the blocking of the SNP rows changes no bit: blocks of 100 rows against the default (one block), with the fused sums and
+    # with G~ written out (JXGPU_FVLMM_FUSED=0)
+    from janusx_amd import pipeline
+    whole = pipeline.scan_rows_splmm_blocks
+    for fused in ("1", "0"):
+        monkeypatch.setenv("JXGPU_FVLMM_FUSED", fused)
+        one, _, _ = jxrs.splmm_exact_scan_from_jxgrm(path, ys, packed, n, maf_all, flip, xc, sub, rows)
+        with monkeypatch.context() as mp:
+            mp.setattr(pipeline, "scan_rows_splmm_blocks", lambda *a, **kw: whole(*a, **{**kw, "block_rows": 100}))
+            cut, _, _ = jxrs.splmm_exact_scan_from_jxgrm(path, ys, packed, n, maf_all, flip, xc, sub, rows)
+        assert np.array_equal(np.isnan(one[:, 0]), bad) and cut.tobytes() == one.tobytes(), fused
+    monkeypatch.delenv("JXGPU_FVLMM_FUSED")
     # blocks of two samples: many blocks, single-sample blocks among them
     monkeypatch.setenv("JXGPU_SPLMM_BLOCK", "2")
     got_b2, l_b2, _ = jxrs.splmm_exact_scan_from_jxgrm(path, ys, packed, n, maf_all, flip, xc, sub, rows[:64])
