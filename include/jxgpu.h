@@ -750,6 +750,33 @@ int jxg_ld_band_mask_p32(const uint8_t *d_p32, int64_t m_total, int n, const int
 int jxg_ld_sums_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int i0, int i1, int j0,
                     int j1, int32_t *d_sums, void *stream);
 
+/* ---- site / sample statistics and LD scores (`jx gstats`; src/stats/gstats.rs, python/janusx/script/gstats.py).
+ *   jx_ldsc_window_bounds : host, no GPU call.  `build_sorted_chrom_groups` (src/stats/gstats.rs:873-896) and `compute_window_bounds`
+ *                           (:898-953): all rows of a chromosome code form one group (groups by first appearance of the code),
+ *                           stably sorted by position, for a cM window by cM and then position; order[p] = file row, groups
+ *                           chrom_off[0 .. *n_chrom] (m + 1 slots), and the two-sided window [start[p], end[p]) of position p in
+ *                           positions of that order.  kind 0: w_int variants to either side; 1: w_int base pairs; 2: w_cm cM
+ *                           (compared against w_cm + 1e-12).  A NaN cM value is refused (the reference sorts with it).
+ *   jxg_ld_score_p32      : LD scores (`compute_ldscore_core`, :1002-1171; pair values of :956-1000, 1063-1100) of the positions
+ *                           [r0, r1) of a row list, r0 a multiple of 32: d_score[i] = d_self[i] + sum over d_start[i] <= j <
+ *                           d_end[i], j != i of r^2(i, j) clamped to [0, 1], from the exact integer pair sums and the per-position
+ *                           d_mean, d_std, d_hasmiss as in jxg_ld_band_mask_p32, every pair evaluated from i's side.  d_part:
+ *                           (r1 - r0) * npb f64 of scratch, npb >= the number of 32-row blocks of the row list between the one
+ *                           that holds the smallest start and the one that holds the largest end of any 32-row block of [r0, r1).
+ *                           d_self, d_score are indexed by position like d_mean.
+ *   jxg_sample_counts_p32 : per-sample counts over the SNP axis (`accumulate_individual_row_counts`, :180-220): d_counts (2, n)
+ *                           int32 = the number of the m rows of the image with code 01 (missing) and with code 10 (het) at
+ *                           each of the n samples; pad samples of the last tile are not counted.  m <= 2^31 - 1.
+ *   jxg_sample_counts_chunk: SNP rows one workgroup of that kernel walks (for tests and sizing). */
+int jx_ldsc_window_bounds(const int32_t *chrom_codes, const int64_t *positions, const double *cm_positions, int64_t m, int kind,
+                          int64_t w_int, double w_cm, int64_t *order, int64_t *chrom_off, int64_t *n_chrom, int64_t *start,
+                          int64_t *end);
+int jxg_ld_score_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int r0, int r1,
+                     const int32_t *d_start, const int32_t *d_end, const double *d_mean, const double *d_std,
+                     const uint8_t *d_hasmiss, const double *d_self, int npb, double *d_part, double *d_score, void *stream);
+int jxg_sample_counts_p32(const uint8_t *d_p32, int64_t m, int n, int32_t *d_counts, void *stream);
+int jxg_sample_counts_chunk(void);
+
 #ifdef __cplusplus
 }
 #endif

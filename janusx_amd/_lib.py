@@ -162,6 +162,10 @@ SIGNATURES = {
     "jx_ld_prune_greedy": [c_p, c_l, c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_p, c_p],
     "jxg_ld_band_mask_p32": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_p],
     "jxg_ld_sums_p32": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
+    "jx_ldsc_window_bounds": [c_p, c_p, c_p, c_l, c_i, c_l, c_d, c_p, c_p, c_p, c_p, c_p],
+    "jxg_ld_score_p32": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p],
+    "jxg_sample_counts_p32": [c_p, c_l, c_i, c_p, c_p],
+    "jxg_sample_counts_chunk": [],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

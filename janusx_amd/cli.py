@@ -10,12 +10,16 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
                                  [-solver adam-em|adam|auto] [-max-iter 500] [-check 5] [-tol 1e-5] [-snps-only]  (fastpop: same)
   python -m janusx_amd gformat -bfile PREFIX -prune WINDOW STEP R2 [-o OUT | -o DIR/ -prefix NAME]   (LD pruning; WINDOW: 50, 500kb, 100bp)
+  python -m janusx_amd gstats -bfile PREFIX [-freq] [-miss] [-het] [-ldsc [WINDOW]] [-o OUT | -o DIR/ -prefix NAME]
+                                 (site / sample QC tables and LD scores; WINDOW: 100, 100kb, 0.1mb, 100000b, 10cm; bare -ldsc: 100kb)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
 
 Outputs: `{out}.{trait}.lmm.tsv` / `.lmm2.tsv` / `.fvlmm.tsv` / `.splmm2.tsv` (`gwas -splmm-exact [cutoff]`, exact SparseLMM scan) / `.splmm.tsv` (`gwas -splmm [cutoff]`, GRAMMAR-gamma SparseLMM scan); `{out}.cGRM.npy` (method 1) or `.sGRM.npy` (method 2) + `.npy.id`; `{out}.spgrm` + `.spgrm.id` with `grm -sparse [cutoff]`;
-`{out}.{trait}.gs.GBLUP.tsv` (sample, observed, predicted, fold) for `gs`; `{out}.eigenvec` + `{out}.eigenval` for `pca`.
+`{out}.{trait}.gs.GBLUP.tsv` (sample, observed, predicted, fold) for `gs`; `{out}.eigenvec` + `{out}.eigenval` for `pca`;
+`{out}.freq` / `.lmiss` / `.lhet` (chr, pos, value), `{out}.imiss` / `.ihet` (fid, iid, value) and `{out}.{n_samples}.{window}.ldsc`
+(chr, pos, M, ldsc) for `gstats` (python/janusx/script/gstats.py; its PDFs and `.gstats.log` are not written).
 Only PLINK BED input, the additive model, the -lmm / -fvlmm scans and the GBLUP branch of `-BLUP`
 (python/janusx/gs/blup.py:72-163 routes n <= BLUP_SMALL_N there; `gblup_reml_npy_grm` call of
 python/janusx/gs/workflow.py:9122) are built; VCF/HMP readers, PCs (-q), plots, the history DB, the
@@ -968,6 +972,123 @@ def cmd_gformat(args):
     return 0
 
 
+def _parse_ldsc_window(text):
+    """WINDOW of `jx gstats -ldsc` -> (kind, value, label): `_parse_ldsc_window` of python/janusx/script/gstats.py:100-138 with its
+    grammar, labels and messages.  A bare number (or `snp` / `snps`) counts variants, `b` / `bp` / `kb` / `mb` are base pairs, `cm`
+    genetic distance; nothing given means 100kb."""
+    import re
+    raw = "100kb" if text is None or str(text).strip() == "" else str(text).strip().lower()
+    compact = raw.replace(" ", "")
+    mt = re.fullmatch(r"([0-9]*\.?[0-9]+)([a-z]*)", compact)
+    if mt is None:
+        raise ValueError(f"Invalid -ldsc window: {text!r}. Use forms like 100, 100kb, 0.1mb, 100000b, or 10cm.")
+    value, unit = float(mt.group(1)), str(mt.group(2) or "")
+    if not math.isfinite(value) or value <= 0.0:
+        raise ValueError(f"-ldsc window must be > 0, got {text!r}.")
+    if unit in ("", "snp", "snps"):
+        if not value.is_integer():
+            raise ValueError(f"SNP-count LD-score window must be an integer, got {text!r}.")
+        v = int(round(value))
+        return "variants", float(v), f"{v}snp"
+    if unit in ("b", "bp"):
+        bp = int(round(value))
+        return "bp", float(bp), f"{bp}b"
+    if unit == "kb":
+        return "bp", float(int(round(value * 1000.0))), compact
+    if unit == "mb":
+        return "bp", float(int(round(value * 1_000_000.0))), compact
+    if unit == "cm":
+        return "cm", float(value), compact
+    raise ValueError(f"Unsupported -ldsc unit in {text!r}. Use forms like 100, 100kb, 0.1mb, 100000b, or 10cm.")
+
+
+def _gstats_write_tables(src_path, min_cols, cols, out, tables, header):
+    """One text table per (suffix, name, values) of `tables`: `header` and the name, then per non-blank line of `src_path` its
+    columns `cols` copied as text and the value as `%.6f` (python/janusx/script/gstats.py:183-304)."""
+    kind = "BIM" if src_path.endswith(".bim") else "FAM"
+    expected = len(tables[0][2])
+    with contextlib.ExitStack() as stack:
+        outs = []
+        for suffix, name, values in tables:
+            fh = stack.enter_context(open(f"{out}.{suffix}", "w", encoding="utf-8"))
+            fh.write(f"{header}\t{name}\n")
+            outs.append((fh, values))
+        row = 0
+        with open(src_path, encoding="utf-8") as src:
+            for line_no, line in enumerate(src, 1):
+                if not line.strip():
+                    continue
+                toks = line.split()
+                if len(toks) < min_cols:
+                    raise SystemExit(f"gstats: Malformed {kind} file: {src_path}:{line_no}")
+                if row >= expected:
+                    raise SystemExit(f"gstats: {src_path} has more rows than the statistics ({row + 1} > {expected})")
+                lead = "\t".join(toks[c].strip() for c in cols)
+                for fh, values in outs:
+                    fh.write(f"{lead}\t{float(values[row]):.6f}\n")
+                row += 1
+        if row != expected:
+            raise SystemExit(f"gstats: {src_path} has {row} rows, the statistics {expected}")
+    return [f"{out}.{suffix}" for suffix, _n, _v in tables]
+
+
+def cmd_gstats(args):
+    """`jx gstats -bfile PREFIX [-freq] [-miss] [-het] [-ldsc [WINDOW]]` (python/janusx/script/gstats.py:545-793): site MAF /
+    missing / het tables, sample missing / het tables and windowed LD scores, with the reference's file names and text.  Its PDFs
+    and its `.gstats.log` are not written (plots are out of scope on this build); non-BED input is refused."""
+    for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"gstats: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    if not args.bfile:
+        raise SystemExit("gstats needs -bfile PREFIX")
+    if not (args.freq or args.miss or args.het or args.ldsc is not None):
+        raise SystemExit("gstats: select at least one statistic: -freq / -miss / -het / -ldsc")
+    try:
+        spec = _parse_ldsc_window(args.ldsc) if args.ldsc is not None else None
+    except ValueError as e:
+        raise SystemExit(f"gstats: {e}") from None
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    from . import janusx as jxrs
+    src = jxrs._bed_prefix(args.bfile)
+    out = _resolve_out(args, src)
+    t0 = time.perf_counter()
+    outputs = []
+    try:
+        if args.freq or args.miss or args.het:
+            if args.freq and not args.miss and not args.het:
+                maf, lmiss, lhet, _n = jxrs.gstats_bed_site_stats(src)
+                imiss = ihet = None
+            else:
+                maf, lmiss, lhet, imiss, ihet, _n, _m = jxrs.gstats_bed_joint_stats(
+                    src, site_maf=bool(args.freq), site_miss=bool(args.miss), site_het=bool(args.het),
+                    individual_miss=bool(args.miss), individual_het=bool(args.het))
+            site = [t for t, on in ((("freq", "freq", maf), args.freq), (("lmiss", "miss", lmiss), args.miss),
+                                    (("lhet", "het", lhet), args.het)) if on]
+            outputs += _gstats_write_tables(f"{src}.bim", 4, (0, 3), out, site, "chr\tpos")
+            sample = [t for t, on in ((("imiss", "miss", imiss), args.miss), (("ihet", "het", ihet), args.het)) if on]
+            if sample:
+                outputs += _gstats_write_tables(f"{src}.fam", 2, (0, 1), out, sample, "fid\tiid")
+        if spec is not None:
+            kind, value, label = spec
+            m_counts, ldsc, n = jxrs.gstats_bed_ldscore(src, kind, value)
+            path = f"{out}.{int(n)}.{label}.ldsc"
+            with open(f"{src}.bim", encoding="utf-8") as fh:
+                sites = [(t[0].strip(), int(t[3])) for t in (ln.split() for ln in fh) if t]
+            with open(path, "w", encoding="utf-8") as fh:
+                fh.write("chr\tpos\tM\tldsc\n")
+                fh.writelines(f"{c}\t{p}\t{int(k)}\t{float(v):.6f}\n" for (c, p), k, v in zip(sites, m_counts, ldsc))
+            outputs.append(path)
+    except RuntimeError as e:
+        raise SystemExit(f"gstats: {e}") from None
+    print(f"gstats: finished in {time.perf_counter() - t0:.2f} s (the reference's PDF plots and .gstats.log are not written on this "
+          "build)")
+    for path in outputs:
+        print(f"  {path}")
+    return 0
+
+
 def cmd_pca(args):
     """`jx pca` (python/janusx/script/pca.py:1134-1265): -bfile -> method-1 GRM with QC and its eigendecomposition, or with -rsvd
     the randomized SVD of the genotypes (`admx_rsvd_stream_sample`); -k -> eigendecomposition of a GRM file."""
@@ -1345,6 +1466,19 @@ def main(argv=None):
         f.add_argument(f"-{flag}", f"--{flag}", dest=flag.replace("-", "_"), action="store_true", default=False,
                        help=argparse.SUPPRESS)
     f.set_defaults(func=cmd_gformat)
+    g = sub.add_parser("gstats")
+    g.add_argument("-bfile", "--bfile", default=None)
+    g.add_argument("-freq", "--freq", action="store_true", default=False, help="site MAF table {out}.freq")
+    g.add_argument("-miss", "--miss", action="store_true", default=False, help="missing-rate tables {out}.imiss / {out}.lmiss")
+    g.add_argument("-het", "--het", action="store_true", default=False, help="heterozygosity tables {out}.ihet / {out}.lhet")
+    g.add_argument("-ldsc", "--ldsc", nargs="?", const="100kb", default=None, metavar="WINDOW",
+                   help="LD scores {out}.{N}.{window}.ldsc; WINDOW: SNP count (100), 100kb / 0.1mb / 100000b, or 10cm; default 100kb")
+    g.add_argument("-o", "--out", default=None)
+    g.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
+    g.add_argument("-t", "--thread", "--threads", dest="thread", type=int, default=0, help="accepted for compatibility; unused")
+    for flag in ("vcf", "hmp", "file"):
+        g.add_argument(f"-{flag}", f"--{flag}", dest=flag, default=None, help=argparse.SUPPRESS)
+    g.set_defaults(func=cmd_gstats)
     args = ap.parse_args(argv)
     return args.func(args)
 

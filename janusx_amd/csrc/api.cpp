@@ -1221,6 +1221,98 @@ extern "C" int jx_ld_window_ends(const int32_t *chrom_codes, const int64_t *posi
     return 0;
 }
 
+// ---- LD scores, host half (`jx gstats -ldsc`; src/stats/gstats.rs:873-953): chromosome groups, their sort and the two-sided
+// windows.  No GPU call.  All rows of a code form one group wherever they lie in the file (groups by first appearance of the
+// code; the reference's order of groups is that of a hash map and decides nothing).  A group is stably sorted by position, for a
+// cM window by cM and then by position (`build_sorted_chrom_groups`, :873-896), and `compute_window_bounds` (:898-953) runs on it:
+// kind 0 = variants (w_int rows to either side), 1 = base pairs (w_int), 2 = cM (w_cm).  order[p] = file row, chrom_off[0 .. *n_chrom]
+// bounds the groups, and row order[p] adds the rows order[start[p] .. end[p]) (positions of the order, its own among them).
+extern "C" int jx_ldsc_window_bounds(const int32_t *chrom_codes, const int64_t *positions, const double *cm_positions, int64_t m,
+                                     int kind, int64_t w_int, double w_cm, int64_t *order, int64_t *chrom_off, int64_t *n_chrom,
+                                     int64_t *start, int64_t *end) {
+    if (m < 0) return fail("jx_ldsc_window_bounds: m must be >= 0");
+    if (kind < 0 || kind > 2) return fail("jx_ldsc_window_bounds: kind must be 0 (variants), 1 (bp) or 2 (cM)");
+    if (kind != 2 && w_int <= 0) return fail("jx_ldsc_window_bounds: the window must be > 0");
+    if (kind == 2 && !(std::isfinite(w_cm) && w_cm > 0.0)) return fail("jx_ldsc_window_bounds: the cM window must be finite and > 0");
+    if (kind == 2) {
+        if (!cm_positions) return fail("jx_ldsc_window_bounds: a cM window needs cM positions");
+        for (int64_t i = 0; i < m; ++i)
+            if (std::isnan(cm_positions[i]))
+                return fail("cM value of row " + std::to_string(i) + " is NaN: a cM window needs an ordered cM column");
+    }
+    std::vector<int64_t> group((size_t)m), count;
+    {
+        std::vector<std::pair<int32_t, int64_t>> seen;        // sorted (code, group)
+        for (int64_t i = 0; i < m; ++i) {
+            const int32_t c = chrom_codes[i];
+            auto it = std::lower_bound(seen.begin(), seen.end(), std::make_pair(c, (int64_t)-1));
+            if (it == seen.end() || it->first != c) {
+                it = seen.insert(it, std::make_pair(c, (int64_t)count.size()));
+                count.push_back(0);
+            }
+            group[(size_t)i] = it->second;
+            ++count[(size_t)it->second];
+        }
+    }
+    const int64_t ng = (int64_t)count.size();
+    *n_chrom = ng;
+    chrom_off[0] = 0;
+    for (int64_t g = 0; g < ng; ++g) chrom_off[g + 1] = chrom_off[g] + count[(size_t)g];
+    {
+        std::vector<int64_t> fill(chrom_off, chrom_off + ng);
+        for (int64_t i = 0; i < m; ++i) order[fill[(size_t)group[(size_t)i]]++] = i;
+    }
+    auto sat_sub = [](int64_t a, int64_t b) {
+        int64_t r;
+        return __builtin_sub_overflow(a, b, &r) ? (b > 0 ? INT64_MIN : INT64_MAX) : r;
+    };
+    for (int64_t g = 0; g < ng; ++g) {
+        const int64_t c0 = chrom_off[g], n = chrom_off[g + 1] - c0;
+        int64_t *grp = order + c0;
+        if (kind == 2)
+            std::stable_sort(grp, grp + n, [&](int64_t a, int64_t b) {
+                if (cm_positions[a] != cm_positions[b]) return cm_positions[a] < cm_positions[b];
+                return positions[a] < positions[b];
+            });
+        else
+            std::stable_sort(grp, grp + n, [&](int64_t a, int64_t b) { return positions[a] < positions[b]; });
+        int64_t *starts = start + c0, *ends = end + c0;
+        if (kind == 0) {
+            for (int64_t i = 0; i < n; ++i) {
+                starts[i] = i > w_int ? i - w_int : 0;
+                ends[i] = w_int >= n - i - 1 ? n : i + w_int + 1;   // min(n, i + w + 1) without overflow
+            }
+        } else if (kind == 1) {
+            const int64_t w = w_int;
+            int64_t left = 0, right = 0;
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t pos_i = positions[grp[i]];
+                while (left < i && sat_sub(pos_i, positions[grp[left]]) > w) ++left;
+                if (right < i) right = i;
+                while (right + 1 < n && sat_sub(positions[grp[right + 1]], pos_i) <= w) ++right;
+                starts[i] = left;
+                ends[i] = right + 1;
+            }
+        } else {
+            const double w = w_cm, eps = 1e-12;
+            int64_t left = 0, right = 0;
+            for (int64_t i = 0; i < n; ++i) {
+                const double cm_i = cm_positions[grp[i]];
+                while (left < i && (cm_i - cm_positions[grp[left]]) > w + eps) ++left;
+                if (right < i) right = i;
+                while (right + 1 < n && (cm_positions[grp[right + 1]] - cm_i) <= w + eps) ++right;
+                starts[i] = left;
+                ends[i] = right + 1;
+            }
+        }
+        for (int64_t i = 0; i < n; ++i) {                     // positions of the whole order
+            starts[i] += c0;
+            ends[i] += c0;
+        }
+    }
+    return 0;
+}
+
 // The strict greedy over the windows that start at the positions [ws0, ws1), from a band mask of the rows [r0, r1) in the
 // layout of `jxg_ld_band_mask_p32`: bit (lj - li - 1) of row li, wpr 32-bit words per row, set where the pair is in LD.
 // maf, first_unchecked and dropped are indexed by position; first_unchecked (start: p + 1) and dropped (start: 0) carry the

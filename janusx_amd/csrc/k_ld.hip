@@ -21,6 +21,14 @@
 //                one i: a wave ballot gives their bits, one lane per quarter ORs them into the row (integer OR: any order gives
 //                the same words).
 //     (b) sums   the six i32 sums of a rectangular block of pairs, for the LD-block matrix and for tests.
+//     (c) score  LD scores (`jx gstats -ldsc`: `compute_ldscore_core`, src/stats/gstats.rs:1002-1171): l_i = self_i + sum of r^2(i, j)
+//                over the two-sided window start[i] <= j < end[i], j != i.  The band is computed two-sided: block (i-block, j-block)
+//                serves the rows of the i-block only, because the clean formula rounds n mean_i mean_j and denom std_i std_j left to
+//                right from i's side and the reference evaluates every pair from the side of the row it adds to.  j-blocks are
+//                the 32-row blocks of the row list (absolute multiples of 32), from the one that holds the smallest start of
+//                the i-block to the one that holds its largest end; a wave adds its 32 x 32 values along j (in lane over its two
+//                j tiles, then over the 16 lanes of a quarter) and writes one f64 per (row, j-block); a second kernel adds the
+//                self term and the partials of a row in ascending j-block.
 #include "jx_common.h"
 
 namespace jx {
@@ -277,6 +285,94 @@ __global__ __launch_bounds__(LD_WAVES * 64) void ld_sums_kernel(const uint8_t *_
                 }
 }
 
+// r^2 of one pair as the LD score adds it (src/stats/gstats.rs:956-1000, 1063-1100): clamped to [0, 1]; 0 where the clean formula
+// has no positive denominator or a non-finite covariance (a finite covariance cannot give a non-finite square here: the square
+// stays below 1e40) and where the pairwise-complete formula has no value
+template <bool SIX>
+__device__ __forceinline__ double ld_score_pair(const ld_i32x4 (&acc)[SIX ? 6 : 1][LD_U][LD_U], int a, int b, int r, bool clean, double nf,
+                                                double denom, double mean_i, double mean_j, double sd_i, double sd_j) {
+    double r2;
+    if (!SIX || clean)
+        r2 = ld_r2_clean(ld_elem(acc[0][a][b], r), nf, denom, mean_i, mean_j, sd_i, sd_j);
+    else
+        r2 = ld_r2_pairwise(ld_elem(acc[0][a][b], r), ld_elem(acc[SIX ? 1 : 0][a][b], r), ld_elem(acc[SIX ? 2 : 0][a][b], r),
+                            ld_elem(acc[SIX ? 3 : 0][a][b], r), ld_elem(acc[SIX ? 4 : 0][a][b], r), ld_elem(acc[SIX ? 5 : 0][a][b], r));
+    if (!isfinite(r2)) return 0.0;
+    return r2 < 0.0 ? 0.0 : (r2 > 1.0 ? 1.0 : r2);
+}
+
+// grid (x: ceil(npb / LD_WAVES), y: i-blocks of [r0, r1), r0 a multiple of LD_B); wave = the i-block against the x-th j-block of
+// its reach.  part ((r1 - r0) rows of npb f64, zeroed by the caller): part[i - r0][x] = sum over the j of that block inside row
+// i's window.  One launch per form, as for the mask.  Two waves per SIMD are asked for: the six form then keeps its 96 accumulators
+// in 156 VGPRs without scratch (left alone the compiler takes 266 registers: one wave per SIMD).
+template <bool SIX>
+__global__ __launch_bounds__(LD_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2))) void ld_score_kernel(
+    const uint8_t *__restrict__ p32, int64_t m_total, int ntiles, int n, const int32_t *__restrict__ rows, int nrows, int r0, int r1,
+    const int32_t *__restrict__ start, const int32_t *__restrict__ end, const double *__restrict__ mean, const double *__restrict__ sd,
+    const uint8_t *__restrict__ hasmiss, int npb, double *__restrict__ part) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, s = lane & 15, kq = lane >> 4;
+    const int x = blockIdx.x * LD_WAVES + wave;
+    const int64_t i0l = (int64_t)r0 + (int64_t)blockIdx.y * LD_B;
+    if (x >= npb || i0l >= r1) return;
+    const int i0 = (int)i0l;
+    // reach of the i-block: the j-blocks that hold the smallest start and the largest end of its rows
+    int lo = nrows, hi = 0, miss = 0;
+    if (lane < LD_B && i0 + lane < r1) {
+        lo = start[i0 + lane];
+        hi = end[i0 + lane];
+        miss = hasmiss[i0 + lane];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int l = __shfl_xor(lo, off, 64), h = __shfl_xor(hi, off, 64);
+        lo = l < lo ? l : lo;
+        hi = h > hi ? h : hi;
+    }
+    lo = lo < 0 ? 0 : lo;                                     // never outside the row list
+    hi = hi > nrows ? nrows : hi;
+    if (hi <= lo) return;
+    const int jb0 = lo / LD_B, jb1 = (hi - 1) / LD_B;
+    if (x > jb1 - jb0) return;                                // wave-uniform: its partials stay zero
+    const int j0 = (jb0 + x) * LD_B;                          // <= hi - 1 < nrows
+    if (lane < LD_B && j0 + lane < nrows) miss |= hasmiss[j0 + lane];
+    if ((__ballot(miss != 0) != 0ull) != SIX) return;         // wave-uniform
+    ld_i32x4 acc[SIX ? 6 : 1][LD_U][LD_U];
+    ld_main<SIX>(p32, m_total * 32, ntiles, rows, nrows, i0, j0, acc);
+    const double nf = (double)n, denom = (double)(n - 1 > 1 ? n - 1 : 1);
+#pragma unroll
+    for (int a = 0; a < LD_U; ++a) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = i0 + 16 * a + 4 * kq + r;
+            const bool iin = i < r1;
+            const int si = iin ? start[i] : 0, ei = iin ? end[i] : 0;
+            const double mean_i = iin ? mean[i] : 0.0, sd_i = iin ? sd[i] : 0.0;
+            const bool hm_i = iin ? hasmiss[i] != 0 : true;
+            double sum = 0.0;
+#pragma unroll
+            for (int b = 0; b < LD_U; ++b) {                  // in lane over the j tiles
+                const int j = j0 + 16 * b + s;
+                if (iin && j < nrows && j >= si && j < ei && j != i)
+                    sum += ld_score_pair<SIX>(acc, a, b, r, !hm_i && !hasmiss[j], nf, denom, mean_i, mean[j], sd_i, sd[j]);
+            }
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) sum += __shfl_xor(sum, off, 64);   // the 16 lanes of a quarter: one row i
+            if (s == 0 && iin) part[(int64_t)(i - r0) * npb + x] = sum;
+        }
+    }
+}
+
+// score[i] = self[i] + part[i - r0][0] + part[i - r0][1] + ... in that order, for the positions [r0, r1)
+__global__ __launch_bounds__(256) void ld_score_reduce_kernel(const double *__restrict__ part, const double *__restrict__ self, int r0,
+                                                              int r1, int npb, double *__restrict__ score) {
+    const int64_t i = (int64_t)r0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r1) return;
+    const double *p = part + (i - r0) * npb;
+    double sum = self[i];
+    for (int x = 0; x < npb; ++x) sum += p[x];
+    score[i] = sum;
+}
+
 static int ld_check(const char *who, int64_t m_total, int n, int nrows) {
     if (n <= 0) return fail(std::string(who) + ": n must be > 0");
     if (n > LD_MAX_N) return fail(std::string(who) + ": at most 16 777 216 samples (exact i32 sums and exact f64 products of them)");
@@ -320,6 +416,30 @@ extern "C" int jxg_ld_sums_p32(const uint8_t *d_p32, int64_t m_total, int n, con
     if (grid.y > 65535u) return fail("jxg_ld_sums_p32: at most 2 097 120 rows per block");
     hipLaunchKernelGGL(ld_sums_kernel, grid, block, 0, (hipStream_t)stream, d_p32, m_total, num_tiles(n), d_rows, nrows, i0, i1, j0, j1,
                        d_sums);
+    JX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int jxg_ld_score_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int r0, int r1,
+                                const int32_t *d_start, const int32_t *d_end, const double *d_mean, const double *d_std,
+                                const uint8_t *d_hasmiss, const double *d_self, int npb, double *d_part, double *d_score,
+                                void *stream) {
+    if (ld_check("jxg_ld_score_p32", m_total, n, nrows)) return 1;
+    if (r0 < 0 || r1 < r0 || r1 > nrows) return fail("jxg_ld_score_p32: row range outside the row list");
+    if (r0 % LD_B) return fail("jxg_ld_score_p32: a row range starts at a multiple of 32 of the row list");
+    if (npb < 1 || npb > (1 << 26)) return fail("jxg_ld_score_p32: partials per row must be in [1, 2^26]");
+    if (r1 == r0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    JX_HIP(hipMemsetAsync(d_part, 0, sizeof(double) * (size_t)(r1 - r0) * (size_t)npb, st));
+    const dim3 grid((npb + LD_WAVES - 1) / LD_WAVES, (r1 - r0 + LD_B - 1) / LD_B), block(LD_WAVES * 64);
+    if (grid.y > 65535u) return fail("jxg_ld_score_p32: at most 2 097 120 rows per range");
+    hipLaunchKernelGGL(ld_score_kernel<false>, grid, block, 0, st, d_p32, m_total, num_tiles(n), n, d_rows, nrows, r0, r1, d_start,
+                       d_end, d_mean, d_std, d_hasmiss, npb, d_part);
+    JX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ld_score_kernel<true>, grid, block, 0, st, d_p32, m_total, num_tiles(n), n, d_rows, nrows, r0, r1, d_start,
+                       d_end, d_mean, d_std, d_hasmiss, npb, d_part);
+    JX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ld_score_reduce_kernel, dim3((r1 - r0 + 255) / 256), dim3(256), 0, st, d_part, d_self, r0, r1, npb, d_score);
     JX_LAUNCH_CHECK();
     return 0;
 }

@@ -5372,3 +5372,298 @@ def bed_ldblock_r2_rust(bfile, chrom_ranges, start_bp, end_bp, selected_chrom=No
         raise RuntimeError(f"{path}: size {os.path.getsize(path)} != 3 + {total}*{bps}")
     rows = np.ascontiguousarray(np.memmap(path, dtype=np.uint8, mode="r", offset=3, shape=(total, bps))[np.asarray(idx)])
     return ld_r2_matrix_packed(rows, n), chrom, pos
+
+
+# ---- site / sample statistics and LD scores (`jx gstats`; src/stats/gstats.rs; csrc/k_gstats.hip, csrc/k_ld.hip) --------------------
+
+LDSC_PARTIAL_BUDGET_BYTES = 256 << 20   # device partial sums (one f64 per row and 32-row block of partners) of one row range
+_LDSC_KINDS = {"variant": 0, "variants": 0, "snp": 0, "snps": 0, "bp": 1, "b": 1, "kb": 1, "mb": 1, "cm": 2, "genetic": 2}
+
+
+def _rust_f64(v):
+    """A float as Rust's `{}` prints it (the reference's error texts)."""
+    import math
+    v = float(v)
+    if math.isnan(v):
+        return "NaN"
+    if math.isinf(v):
+        return "inf" if v > 0 else "-inf"
+    return str(int(v)) if v == math.floor(v) and abs(v) < 1e16 else repr(v)
+
+
+def _ldsc_parse_window(kind, value):
+    """`parse_ldsc_window`, src/stats/gstats.rs:824-863 -> (0 variants | 1 bp | 2 cM, integer window, cM window)."""
+    import math
+    value = float(value)
+    if not (math.isfinite(value) and value > 0.0):
+        raise RuntimeError(f"window_value must be finite and > 0, got {_rust_f64(value)}")
+    code = _LDSC_KINDS.get(str(kind).strip().lower())
+    if code is None:
+        raise RuntimeError(f"window_kind must be one of: variants, bp, cm; got '{kind}'")
+    if code == 2:
+        return 2, 0, value
+    rounded = math.floor(value + 0.5)                         # f64::round of a positive value
+    w = int(min(rounded, 2.0 ** 63 - 1024.0))                 # `as i64` saturates
+    if code == 0:
+        if abs(rounded - value) > 1e-9:
+            raise RuntimeError(f"variant-count LD-score window must be an integer, got {_rust_f64(value)}")
+        if w <= 0:
+            raise RuntimeError(f"variant-count LD-score window must be > 0, got {w}")
+    else:
+        if abs(rounded - value) > 1e-6:
+            raise RuntimeError(f"bp LD-score window must resolve to an integer, got {_rust_f64(value)}")
+        if w <= 0:
+            raise RuntimeError(f"bp LD-score window must be > 0, got {w}")
+    return code, w, 0.0
+
+
+def _ldsc_window_bounds(chrom_codes, positions, cm_positions, kind, w_int, w_cm):
+    """`jx_ldsc_window_bounds` (host, no device): the chromosome-grouped, sorted order of the rows, the group offsets and the
+    two-sided window [start, end) per position of that order."""
+    cc, ps = _c(chrom_codes, np.int32).ravel(), _c(positions, np.int64).ravel()
+    cm = None if cm_positions is None else _c(cm_positions, np.float64).ravel()
+    m = int(cc.shape[0])
+    order, off, ng = np.zeros(m, dtype=np.int64), np.zeros(m + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    start, end = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+    check(lib().jx_ldsc_window_bounds(_p(cc), _p(ps), _p(cm), m, int(kind), int(w_int), float(w_cm), _p(order), _p(off), _p(ng),
+                                      _p(start), _p(end)))
+    return order, off[:int(ng[0]) + 1].copy(), start, end
+
+
+def _ldsc_ranges(start, end, budget_bytes):
+    """Row ranges [(r0, r1, npb)] of the row list whose partial sums stay under `budget_bytes`: r0 a multiple of 32, so that the
+    32-row blocks of a row and of its partners, and hence the rounding of its score, do not depend on the budget; npb = the most
+    32-row blocks of partners any 32-row block of the range reaches; at most 65 535 blocks per range (the grid)."""
+    m = int(start.shape[0])
+    edges = np.arange(0, m, 32)
+    reach = (np.maximum.reduceat(end, edges) - 1) // 32 - np.minimum.reduceat(start, edges) // 32 + 1
+    budget, out, a, nblk = int(budget_bytes), [], 0, int(edges.shape[0])
+    while a < nblk:
+        npb = int(reach[a])
+        if 32 * npb * 8 > budget:
+            raise RuntimeError(f"LD score: a partial-sum budget of {budget} bytes is below the {32 * npb * 8} bytes one block of 32 "
+                               f"rows needs ({npb} blocks of partners); use a smaller window or a larger budget")
+        b = a + 1
+        while b < nblk and b - a < 65535:
+            top = max(npb, int(reach[b]))
+            if (b + 1 - a) * 32 * top * 8 > budget:
+                break
+            npb, b = top, b + 1
+        out.append((32 * a, min(32 * b, m), npb))
+        a = b
+    return out
+
+
+def ldscore_packed(packed, n_samples, chrom_codes, positions, cm_positions=None, window_kind="bp", window_value=100000,
+                   partial_budget_bytes=None, timings=None):
+    """LD scores of a packed payload (m, ceil(n / 4)) (extension: `compute_ldscore_core`, src/stats/gstats.rs:1002-1171, for a panel
+    in memory) -> (M int64 (m), ldsc f64 (m)): per row the size of its two-sided window among the rows of its chromosome code
+    (`window_kind` / `window_value` as `gstats_bed_ldscore`; `cm_positions` for a cM window) and l_i = self term + the sum of the
+    clamped r^2 with the other rows of the window.  The windows come from the host (`jx_ldsc_window_bounds`), the pair values and
+    their sums from the device (`jxg_ld_score_p32`: exact integer pair sums, r^2 in f64 in the reference's operation order from
+    the side of the row the score belongs to), range by range so that the device partials stay under `partial_budget_bytes`
+    (default `LDSC_PARTIAL_BUDGET_BYTES`); the scores do not depend on the budget.  `packed` may be a torch CUDA uint8 tensor;
+    `timings`: a dict that receives `bounds_s`, `score_s` (launches and the copy of the scores) and `ranges`."""
+    kind, w_int, w_cm = _ldsc_parse_window(window_kind, window_value)
+    shape = tuple(packed.shape) if hasattr(packed, "shape") else np.asarray(packed).shape
+    if len(shape) != 2:
+        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
+    n, m = int(n_samples), int(shape[0])
+    if n <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    if int(shape[1]) != (n + 3) // 4:
+        raise RuntimeError(f"packed second dimension mismatch: got {int(shape[1])}, expected {(n + 3) // 4} for n_samples={n}")
+    cc, ps = np.asarray(chrom_codes).ravel(), np.asarray(positions).ravel()
+    if int(cc.shape[0]) != m:
+        raise RuntimeError(f"chrom_codes length mismatch: got {int(cc.shape[0])}, expected {m}")
+    if int(ps.shape[0]) != m:
+        raise RuntimeError(f"positions length mismatch: got {int(ps.shape[0])}, expected {m}")
+    if cm_positions is None and kind == 2:
+        raise RuntimeError("a cM LD-score window needs cm_positions")
+    if cm_positions is not None and int(np.asarray(cm_positions).size) != m:
+        raise RuntimeError(f"cm_positions length mismatch: got {int(np.asarray(cm_positions).size)}, expected {m}")
+    if m >= 1 << 31:
+        raise RuntimeError("at most 2^31 - 1 rows")
+    if m == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)
+    t0 = time.perf_counter()
+    order, _off, start, end = _ldsc_window_bounds(cc, ps, cm_positions, kind, w_int, w_cm)
+    t_bounds = time.perf_counter() - t0
+    ranges = _ldsc_ranges(start, end, LDSC_PARTIAL_BUDGET_BYTES if partial_budget_bytes is None else int(partial_budget_bytes))
+    import torch
+    from .pipeline import _ptr, _stream
+    panel = _panel(packed, n)
+    counts = panel.counts().astype(np.int64)
+    mean, std, maf, hasmiss = _ld_row_stats(counts, n)
+    self_term = (((n - counts[:, 0]) > 1) & (maf > 0.0)).astype(np.float64)     # src/stats/gstats.rs:1054-1058
+    dev = panel.device
+    identity = bool(np.array_equal(order, np.arange(m)))
+    rows_t = None if identity else torch.from_numpy(order.astype(np.int32)).to(dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    mean_t, std_t, miss_t, self_t = up(mean[order]), up(std[order]), up(hasmiss[order].astype(np.uint8)), up(self_term[order])
+    start_t, end_t = up(start.astype(np.int32)), up(end.astype(np.int32))
+    part_t = torch.empty(max((r1 - r0) * npb for r0, r1, npb in ranges), dtype=torch.float64, device=dev)
+    score_t = torch.empty(m, dtype=torch.float64, device=dev)
+    t0 = time.perf_counter()
+    for r0, r1, npb in ranges:
+        check(lib().jxg_ld_score_p32(_ptr(panel.p32), m, n, _ptr(rows_t), m, r0, r1, _ptr(start_t), _ptr(end_t), _ptr(mean_t),
+                                     _ptr(std_t), _ptr(miss_t), _ptr(self_t), npb, _ptr(part_t), _ptr(score_t), _stream()))
+    score = score_t.cpu().numpy()
+    if timings is not None:
+        timings.update(bounds_s=t_bounds, score_s=time.perf_counter() - t0, ranges=len(ranges))
+    m_counts, ldsc = np.empty(m, dtype=np.int64), np.empty(m, dtype=np.float64)
+    m_counts[order] = end - start
+    ldsc[order] = score
+    return m_counts, ldsc
+
+
+def _gstats_site_rates(counts, n):
+    """`packed_site_rates`, src/stats/gstats.rs:158-177, in f32 from the integer row counts (missing, het, hom_alt) -> (maf, miss,
+    het) f32.  numpy's float32 elementwise operations are the IEEE ones the reference's are, in its order."""
+    c = np.asarray(counts, dtype=np.int64)
+    missing, het_count, hom_alt = c[:, 0], c[:, 1], c[:, 2]
+    non_missing = np.maximum(int(n) - missing, 0)
+    called = non_missing > 0
+    miss_rate = missing.astype(np.float32) / np.float32(n)
+    nm32 = np.where(called, non_missing, 1).astype(np.float32)
+    p_alt = (het_count + 2 * hom_alt).astype(np.float32) / (np.float32(2.0) * nm32)
+    maf = np.minimum(p_alt, np.float32(1.0) - p_alt)
+    het = het_count.astype(np.float32) / nm32
+    zero = np.float32(0.0)
+    return np.where(called, maf, zero).astype(np.float32), miss_rate.astype(np.float32), np.where(called, het, zero).astype(np.float32)
+
+
+def _gstats_sample_rates(sample_counts, n_snps):
+    """`finalize_individual_rates`, src/stats/gstats.rs:222-245, in f32 from the per-sample counts (2, n) (missing, het) -> (miss,
+    het) f32."""
+    c = np.asarray(sample_counts, dtype=np.int64)
+    miss_ct, het_ct = c[0], c[1]
+    nonmiss = int(n_snps) - miss_ct
+    miss = miss_ct.astype(np.float32) / np.float32(n_snps)
+    het = np.where(nonmiss > 0, het_ct.astype(np.float32) / np.where(nonmiss > 0, nonmiss, 1).astype(np.float32), np.float32(0.0))
+    return miss.astype(np.float32), het.astype(np.float32)
+
+
+def _sample_counts(panel):
+    """(2, n) int32: per sample the number of rows of a panel with a missing call and with a het call (`jxg_sample_counts_p32`)."""
+    import torch
+    from .pipeline import _ptr, _stream
+    out = torch.empty((2, panel.n), dtype=torch.int32, device=panel.device)
+    check(lib().jxg_sample_counts_p32(_ptr(panel.p32), panel.m, panel.n, _ptr(out), _stream()))
+    return out.cpu().numpy()
+
+
+def sample_counts_packed(packed, n_samples):
+    """Per-sample (missing, het) row counts (2, n) int32 of a packed payload (m, ceil(n / 4)), host array or torch CUDA tensor
+    (extension: the integer half of `gstats_bed_individual_stats`)."""
+    return _sample_counts(_panel(packed, n_samples))
+
+
+def _gstats_open_bed(prefix):
+    """`open_bed_mmap`, src/stats/gstats.rs:123-156 -> (payload (m, bps) uint8 memmap, n_samples, m)."""
+    from .bed import read_fam_ids
+    try:
+        n = len(read_fam_ids(prefix))
+    except OSError as e:
+        raise RuntimeError(f"{prefix}.fam: {e}") from None
+    if n == 0:
+        raise RuntimeError("no samples found in PLINK input")
+    path = f"{prefix}.bed"
+    try:
+        size = os.path.getsize(path)
+        with open(path, "rb") as fh:
+            head = fh.read(3)
+    except OSError as e:
+        raise RuntimeError(f"{path}: {e}") from None
+    if size < 3:
+        raise RuntimeError(f"{path}: BED too small")
+    if head != bytes([0x6C, 0x1B, 0x01]):
+        raise RuntimeError(f"{path}: unsupported BED header (expect SNP-major 0x6C 0x1B 0x01)")
+    bps, data_len = (n + 3) // 4, size - 3
+    if data_len % bps != 0:
+        raise RuntimeError(f"{path}: invalid payload length data_len={data_len}, bytes_per_snp={bps}")
+    m = data_len // bps
+    if m == 0:
+        raise RuntimeError(f"{path}: no variant rows found")
+    return np.memmap(path, dtype=np.uint8, mode="r", offset=3, shape=(m, bps)), n, m
+
+
+def _gstats_bim_ldsc_meta(prefix):
+    """`parse_bim_ldsc_meta`, src/stats/gstats.rs:785-822 -> (chromosome codes int32 by first appearance of the normalised token,
+    positions int64, cM f64)."""
+    path = f"{prefix}.bim"
+    codes, cc, ps, cm = {}, [], [], []
+    try:
+        fh = open(path)
+    except OSError as e:
+        raise RuntimeError(f"{path}: {e}") from None
+    with fh:
+        for line_no, line in enumerate(fh, 1):
+            toks = line.split()
+            if len(toks) < 4:
+                raise RuntimeError(f"{path}:{line_no}: malformed BIM row, expect at least 4 columns")
+            try:
+                if "_" in toks[2]:
+                    raise ValueError
+                cm.append(float(toks[2]))
+            except ValueError:
+                raise RuntimeError(f"{path}:{line_no}: invalid cM value '{toks[2]}': invalid float literal") from None
+            try:
+                if "_" in toks[3]:
+                    raise ValueError
+                bp = int(toks[3])
+            except ValueError:
+                raise RuntimeError(f"{path}:{line_no}: invalid BP value '{toks[3]}': invalid digit found in string") from None
+            if not -(1 << 63) <= bp < (1 << 63):
+                raise RuntimeError(f"{path}:{line_no}: invalid BP value '{toks[3]}': number too {'large' if bp > 0 else 'small'} "
+                                   "to fit in target type")
+            ps.append(bp)
+            cc.append(codes.setdefault(_ld_chr_token(toks[0]), len(codes)))
+    if not cc:
+        raise RuntimeError(f"{path}: no variant rows found")
+    return np.asarray(cc, dtype=np.int32), np.asarray(ps, dtype=np.int64), np.asarray(cm, dtype=np.float64)
+
+
+def gstats_bed_site_stats(prefix, threads=0):
+    """src/stats/gstats.rs:1173-1199: per-site MAF, missing rate and het rate of a PLINK prefix -> (maf, miss, het f32 (m),
+    n_samples), the rates of `packed_site_rates` (:158-177) from the device's row counts.  `threads` is accepted and unused."""
+    payload, n, _m = _gstats_open_bed(_bed_prefix(prefix))
+    maf, miss, het = _gstats_site_rates(_panel(payload, n).counts(), n)
+    return maf, miss, het, n
+
+
+def gstats_bed_joint_stats(prefix, site_maf=True, site_miss=True, site_het=True, individual_miss=True, individual_het=True,
+                           threads=0):
+    """src/stats/gstats.rs:1201-1278: the requested site and sample tables of a PLINK prefix in one pass -> (maf, miss, het f32 (m),
+    sample miss, sample het f32 (n), n_samples, n_snps), None where not requested.  `threads` is accepted and unused."""
+    payload, n, m = _gstats_open_bed(_bed_prefix(prefix))
+    panel = _panel(payload, n)
+    maf, miss, het = _gstats_site_rates(panel.counts(), n)
+    imiss = ihet = None
+    if individual_miss or individual_het:
+        imiss, ihet = _gstats_sample_rates(_sample_counts(panel), m)
+    return (maf if site_maf else None, miss if site_miss else None, het if site_het else None, imiss if individual_miss else None,
+            ihet if individual_het else None, n, m)
+
+
+def gstats_bed_individual_stats(prefix, threads=0):
+    """src/stats/gstats.rs:1331-1357: per-sample missing rate and het rate over the SNPs of a PLINK prefix -> (miss, het f32 (n),
+    n_snps), `finalize_individual_rates` (:222-245) from the device's per-sample counts.  `threads` is accepted and unused."""
+    payload, n, m = _gstats_open_bed(_bed_prefix(prefix))
+    imiss, ihet = _gstats_sample_rates(_sample_counts(_panel(payload, n)), m)
+    return imiss, ihet, m
+
+
+def gstats_bed_ldscore(prefix, window_kind, window_value, threads=0):
+    """src/stats/gstats.rs:1359-1403: windowed LD scores of a PLINK prefix -> (M int64 (m), ldsc f64 (m), n_samples); window kinds
+    `variants` / `bp` / `cm` with their aliases (`parse_ldsc_window`, :824-863), chromosomes from the normalised `.bim` token,
+    positions and cM from the `.bim`.  A NaN cM value under a cM window is refused (the reference sorts with it).  `threads` is
+    accepted and unused."""
+    pfx = _bed_prefix(prefix)
+    _ldsc_parse_window(window_kind, window_value)
+    payload, n, m = _gstats_open_bed(pfx)
+    cc, ps, cm = _gstats_bim_ldsc_meta(pfx)
+    if int(cc.shape[0]) != m:
+        raise RuntimeError(f"BED/BIM row mismatch: bed={m}, bim={int(cc.shape[0])}")
+    m_counts, ldsc = ldscore_packed(payload, n, cc, ps, cm, window_kind, window_value)
+    return m_counts, ldsc, n
