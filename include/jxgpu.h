@@ -581,6 +581,18 @@ int jx_lm_residualize(const double *y, const double *x, const double *ixx, int n
 int jxg_lm_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const float *d_lut,
                     const double *d_xr, int q0, const double *d_ixx, double yy_r, double *d_work, double *d_out,
                     void *stream);
+/* `lm2_stream_bed_to_tsv` (src/stats/glm2.rs:142-325): the SNP-by-covariate interaction scan y ~ X + g + g o c_1 .. g o c_k on a
+ * resident P32 image.  d_lut (nrows, 4) f32 = additive value by 2-bit code.  d_w (tiles, nblk, 32, 64) f64 = the weight columns
+ * in the operand layout of the 16x16x4 f64 matrix instruction: element [tile][b][ks][lane] = column 16 b + (lane & 15) at sample
+ * 128 tile + 4 ks + (lane >> 4), zero beyond n; blocks [0, nblk_v) hold c_a Q_t and c_a r_y (column a (q_rank + 1) + t, t =
+ * q_rank for r_y, c_0 = 1) and are summed against v, blocks [nblk_v, nblk) hold c_a c_b (b <= a, column a (a + 1) / 2 + b) and
+ * are summed against v^2.  d_sums (nrows, 16 nblk) f64 receives the sums; d_out (nrows, 4 (1 + k) + 4) f64 = (beta, se, chisq,
+ * pwald) per coefficient, then chisq_int_joint, p_int_joint, chisq_joint, p_joint; d_flag (nrows) i32 = 1 where the Schur
+ * complement (or the interaction block of its inverse) met an exactly zero or non-finite pivot: such a row is NaN in d_out and
+ * is left to the caller's pseudo-inverse.  df = n - (q_base + 1 + k).  stage: 0 = both kernels, 1 = the sums, 2 = the algebra. */
+int jxg_lm2_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const float *d_lut,
+                     const double *d_w, int nblk, int nblk_v, int q_rank, int k, double rss0, int df, double *d_sums,
+                     double *d_out, int32_t *d_flag, int stage, void *stream);
 /* `lm_block_assoc_f32` (src/stats/glm.rs:4313-4497): the same LM formulas on an already decoded SNP-major f32 block
  * g (m, n) on the host; out (m, 4).  Row rules of that entry point (s must exceed 1e-12; a non-finite variance or standard
  * error voids the row, glm.rs:4457-4479). */

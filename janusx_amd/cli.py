@@ -3,7 +3,7 @@
 Flag names, defaults and output file names follow the reference (python/janusx/assoc/workflow.py:6599-7047,
 python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model_stream.py:989-994):
 
-  python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-lmm | -lmm2 | -fvlmm) [-k 1|2|GRM.npy] [-c COV.tsv]
+  python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-lm | -lm2 COVCOL | -lmm | -lmm2 | -fvlmm) [-k 1|2|GRM.npy] [-c COV.tsv]
                             [-maf 0.02] [-geno 0.05] [-het 1.0] [-o OUT] [-force-model]
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
@@ -16,7 +16,7 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
 
-Outputs: `{out}.{trait}.lmm.tsv` / `.lmm2.tsv` / `.fvlmm.tsv` / `.splmm2.tsv` (`gwas -splmm-exact [cutoff]`, exact SparseLMM scan) / `.splmm.tsv` (`gwas -splmm [cutoff]`, GRAMMAR-gamma SparseLMM scan); `{out}.cGRM.npy` (method 1) or `.sGRM.npy` (method 2) + `.npy.id`; `{out}.spgrm` + `.spgrm.id` with `grm -sparse [cutoff]`;
+Outputs: `{out}.{trait}.lm.tsv` (`gwas -lm`, plain linear model) / `.lm2.tsv` (`gwas -lm2 COVCOL`, SNP-by-covariate interaction scan over the 0-based columns COVCOL of the merged -c table: 0, 0:3, :2, 0,3) / `.lmm.tsv` / `.lmm2.tsv` / `.fvlmm.tsv` / `.splmm2.tsv` (`gwas -splmm-exact [cutoff]`, exact SparseLMM scan) / `.splmm.tsv` (`gwas -splmm [cutoff]`, GRAMMAR-gamma SparseLMM scan); `{out}.cGRM.npy` (method 1) or `.sGRM.npy` (method 2) + `.npy.id`; `{out}.spgrm` + `.spgrm.id` with `grm -sparse [cutoff]`;
 `{out}.{trait}.gs.GBLUP.tsv` (sample, observed, predicted, fold) for `gs`; `{out}.eigenvec` + `{out}.eigenval` for `pca`;
 `{out}.freq` / `.lmiss` / `.lhet` (chr, pos, value), `{out}.imiss` / `.ihet` (fid, iid, value) and `{out}.{n_samples}.{window}.ldsc`
 (chr, pos, M, ldsc) for `gstats` (python/janusx/script/gstats.py; its PDFs and `.gstats.log` are not written).
@@ -314,6 +314,92 @@ def _warm_start_mode(args):
     return "none" if env_truthy("JX_LMM_UNIFIED_NO_WARM_START") else "chain"
 
 
+def _parse_lm2_covariate_selector(value, label="-lm2/--lm2"):
+    """`_parse_lm2_covariate_selector` (python/janusx/assoc/workflow.py:497-553): 0-based column selectors `0`, `0:3` (both ends
+    included, descending allowed), `:2`, `0,3`; duplicates are dropped in first-seen order; a bare flag selects nothing."""
+    raw = str(value).strip() if value is not None else ""
+    if raw in ("", "__SELF__"):
+        return []
+    picks = []
+
+    def push(idx0):
+        if idx0 < 0:
+            raise ValueError(f"{label}: covariate column indices must be >= 0, got {idx0}.")
+        if idx0 not in picks:
+            picks.append(idx0)
+
+    def is_int(tok):
+        return tok.lstrip("+-").isdigit()
+
+    for token in [t.strip() for t in raw.split(",") if t.strip() != ""]:
+        if ":" in token:
+            left, right = (t.strip() for t in token.split(":", 1))
+            if left == "" and right == "":
+                raise ValueError(f"{label}: invalid empty covariate range '{token}'.")
+            if left != "" and not is_int(left):
+                raise ValueError(f"{label}: invalid covariate range start '{left}'.")
+            start = 0 if left == "" else int(left)
+            if right == "":
+                raise ValueError(f"{label}: open-ended covariate range '{token}' is not supported; provide an explicit end.")
+            if not is_int(right):
+                raise ValueError(f"{label}: invalid covariate range end '{right}'.")
+            end = int(right)
+            step = 1 if end >= start else -1
+            for idx in range(start, end + step, step):
+                push(idx)
+            continue
+        if not is_int(token):
+            raise ValueError(f"{label}: invalid covariate selector '{token}'. Use 0-based indices/ranges like 0, 0:3, :2, 0,3.")
+        push(int(token))
+    return picks
+
+
+def _resolve_lm2_covariate_indices(cov_all, selector_zero_based, label="-lm2/--lm2"):
+    """`_resolve_lm2_covariate_indices` (python/janusx/assoc/workflow.py:556-575): the selection against the merged -c table."""
+    arr = np.asarray(cov_all)
+    if arr.ndim != 2:
+        raise ValueError("LM2 requires a 2D merged covariate matrix.")
+    ncov = int(arr.shape[1])
+    if ncov <= 0:
+        raise ValueError("LM2 requires at least one covariate column from -c.")
+    bad = [int(i) for i in selector_zero_based if int(i) < 0 or int(i) >= ncov]
+    if bad:
+        raise ValueError(f"{label}: covariate column index out of range: {bad[0]}. valid=[0..{ncov - 1}]")
+    return np.asarray(selector_zero_based, dtype=np.int64)
+
+
+def _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, args, bim, out, name):
+    """`-lm` and `-lm2` of one trait on one panel of its samples: the QC of the other models (-maf, -geno, -het), the plain LM
+    scan (`pipeline.scan_rows_lm`, the table the LRT fallback of -lmm writes) and / or the interaction scan
+    (`pipeline.scan_rows_lm2`); `af` = ALT frequency, `miss` = the count of missing samples."""
+    from . import pipeline as pl
+    from . import stats as st
+    from .tsv import write_assoc_tsv_counts, write_lm2_tsv
+    n = len(keep_idx)
+    # a panel of its own, released on return: with -lmm / -lmm2 / -fvlmm in the same run `run_trait` re-tiles the payload once
+    # more for the same samples (one repack pass per trait; the two images are never resident together)
+    panel = pl.Panel(packed_t, n_fam, keep_idx)
+    counts = panel.counts()
+    keep, af, _miss = st.gwas_scan_row_stats(counts, n, args.maf, args.geno, args.het)
+    rows = np.nonzero(keep)[0]
+    meta = ([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows], [bim.snp[j] for j in rows], [bim.a0[j] for j in rows],
+            [bim.a1[j] for j in rows])
+    miss_cnt = counts[rows, 0]
+    if run_lm:
+        t1 = time.perf_counter()
+        path = f"{out}.{name}.lm.tsv"
+        stats = pl.scan_rows_lm(panel, rows, af[rows], x, y)
+        write_assoc_tsv_counts(path, *meta, af[rows], miss_cnt.astype(np.float32), stats[:, :3].cpu().numpy())
+        print(f"[{name}] -lm: n={n} snps={len(rows)} -> {path} ({time.perf_counter() - t1:.2f}s)")
+    if lm2_idx is not None:
+        t1 = time.perf_counter()
+        path = f"{out}.{name}.lm2.tsv"
+        stats = pl.scan_rows_lm2(panel, rows, af[rows], x, cov_rows[:, lm2_idx], y)
+        write_lm2_tsv(path, *meta, af[rows], miss_cnt, stats.cpu().numpy(), [int(i) for i in lm2_idx])
+        print(f"[{name}] -lm2: n={n} snps={len(rows)} interactions={','.join(str(int(i)) for i in lm2_idx)} -> {path} "
+              f"({time.perf_counter() - t1:.2f}s)")
+
+
 def cmd_gwas(args):
     import torch
     from . import janusx as jxrs
@@ -333,8 +419,13 @@ def cmd_gwas(args):
             raise SystemExit("-splmm and -splmm-exact in one run must use the same sparse-GRM cut-off")
     if args.splmm is None and sp_stems:
         args.splmm = float(args.splmm_exact)
-    if not (args.lmm or args.fvlmm or args.lmm2 or args.splmm is not None):
-        raise SystemExit("select at least one model: -lmm, -lmm2, -fvlmm, -splmm and/or -splmm-exact")
+    lm2_flag = getattr(args, "lm2", None)
+    if not (getattr(args, "lm", False) or lm2_flag is not None or args.lmm or args.fvlmm or args.lmm2 or args.splmm is not None):
+        raise SystemExit("select at least one model: -lm, -lm2, -lmm, -lmm2, -fvlmm, -splmm and/or -splmm-exact")
+    try:
+        lm2_sel = _parse_lm2_covariate_selector(lm2_flag)
+    except ValueError as e:
+        raise SystemExit(str(e))
     rank, world = _dist_setup()
     # the payload goes to HBM in windows (bed.stage_bed_payload: `mmap_window_mb` of the reference's BED routes); nothing
     # below holds a host copy of it
@@ -397,6 +488,25 @@ def cmd_gwas(args):
             cpos = {s: i for i, s in enumerate(cids)}
         else:
             args.cov = False
+    # -lm2 without -c, or without COVCOL, runs -lm instead (python/janusx/assoc/workflow.py:7969-8001); once, if -lm was given too
+    run_lm, lm2_idx = bool(getattr(args, "lm", False)), None
+    if lm2_flag is not None:
+        if not args.cov:
+            print("Warning: LM2 received no external covariates from -c; falling back to LM.")
+            run_lm = True
+        elif not lm2_sel:
+            print("Warning: LM2 received no explicit interaction columns; falling back to LM.")
+            run_lm = True
+        else:
+            from .lm2 import LM2_MAX_INTERACTIONS
+            try:
+                lm2_idx = _resolve_lm2_covariate_indices(cv, lm2_sel)
+            except ValueError as e:
+                raise SystemExit(str(e))
+            if len(lm2_idx) > LM2_MAX_INTERACTIONS:
+                raise SystemExit(f"-lm2/--lm2: at most {LM2_MAX_INTERACTIONS} interaction columns in this build, got {len(lm2_idx)}")
+    if (run_lm or lm2_idx is not None) and world > 1:
+        print("-lm / -lm2: computed on rank 0 alone")
     traits = _select_traits(names, args.ncol)
     out = _resolve_out(args, args.bfile)
     dev = packed_t.device
@@ -483,6 +593,9 @@ def cmd_gwas(args):
             x = np.concatenate([x, qmat[keep_idx]], axis=1)
         if args.cov:
             x = np.concatenate([x, np.array([cv[cpos[fam[j]]] for j in keep_idx])], axis=1)
+        if (run_lm or lm2_idx is not None) and rank == 0:
+            cov_rows = np.array([cv[cpos[fam[j]]] for j in keep_idx]) if lm2_idx is not None else None
+            _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, args, bim, out, name)
         for mode in (["lmm"] if args.lmm else []) + (["lmm2"] if args.lmm2 else []) + (["fvlmm"] if args.fvlmm else []):
             t1 = time.perf_counter()
             # rows are formatted and written block by block on a writer thread while the device scans the next block
@@ -1336,6 +1449,11 @@ def main(argv=None):
     g.add_argument("-bfile", "--bfile", required=True)
     g.add_argument("-p", "--pheno", required=True)
     g.add_argument("-n", "--n", dest="ncol", action="append", default=None)
+    g.add_argument("-lm", "--lm", action="store_true", default=False,
+                   help="plain linear model -> {out}.{trait}.lm.tsv")
+    g.add_argument("-lm2", "--lm2", nargs="?", const="__SELF__", default=None, metavar="COVCOL",
+                   help="linear model with SNP-by-covariate interaction terms over the selected columns of the merged -c table "
+                        "-> {out}.{trait}.lm2.tsv; 0-based selectors like 0, 0:3, :2, 0,3; without columns it runs -lm")
     g.add_argument("-lmm", "--lmm", action="store_true", default=False)
     g.add_argument("-lmm2", "--lmm2", action="store_true", default=False)
     g.add_argument("-fvlmm", "--fvlmm", action="store_true", default=False)

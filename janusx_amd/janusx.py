@@ -3176,6 +3176,175 @@ def lm_block_assoc_packed_to_tsv(y, x, ixx, packed, n_samples, row_flip, row_maf
     return rows, m
 
 
+def _lm_stream_checks(y, x, maf_threshold, max_missing_rate, genetic_model, het_threshold, chunk_size, mmap_window_mb):
+    """Leading argument checks shared by `lm_stream_bed_to_tsv` (src/stats/glm.rs:2385-2421) and `lm2_stream_bed_to_tsv`
+    (src/stats/glm2.rs:412-440), in the reference's order, before any device call.  -> (y, x)."""
+    if int(chunk_size) <= 0:
+        raise ValueError("chunk_size must be > 0")
+    if not (0.0 <= maf_threshold <= 0.5):
+        raise ValueError("maf_threshold must be within [0, 0.5]")
+    if not (0.0 <= max_missing_rate <= 1.0):
+        raise ValueError("max_missing_rate must be within [0, 1.0]")
+    if not (0.0 <= het_threshold <= 1.0):
+        raise ValueError("het_threshold must be within [0, 1.0]")
+    model = str(genetic_model).strip().lower()
+    if model not in ("add", "dom", "rec", "het"):
+        raise ValueError("genetic_model must be one of: add, dom, rec, het")
+    if model != "add":
+        raise RuntimeError(f"genetic_model '{model}' is outside this build's scope (additive model only)")
+    if mmap_window_mb is not None and int(mmap_window_mb) <= 0:
+        raise ValueError("mmap_window_mb must be > 0")
+    y = _c(y, np.float64).ravel()
+    x = _c(x, np.float64)
+    if x.ndim != 2 or x.shape[0] != y.shape[0]:
+        raise RuntimeError("X.n_rows must equal len(y)")
+    return y, x
+
+
+def _lm_prepared_meta(row_indices, row_flip, row_missing, row_maf):
+    """The prepared row metadata of the LM streaming routes (glm2.rs:487-510, 539-567): all four arrays or none, equal
+    lengths, `row_indices` ascending.  -> (row_indices i64, row_flip bool, row_missing f32, row_maf f32) or None."""
+    given = [a is not None for a in (row_indices, row_flip, row_missing, row_maf)]
+    if not any(given):
+        return None
+    if not all(given):
+        raise RuntimeError("prepared row metadata must provide all or none of: row_indices, row_flip, row_missing, row_maf")
+    ri = _c(row_indices, np.int64).ravel()
+    fl = np.asarray(row_flip).astype(bool).ravel()
+    mi = _c(row_missing, np.float32).ravel()
+    mf = _c(row_maf, np.float32).ravel()
+    if not (fl.shape[0] == mi.shape[0] == mf.shape[0] == ri.shape[0]):
+        raise RuntimeError(f"prepared row metadata length mismatch: row_indices={ri.shape[0]}, row_flip={fl.shape[0]}, "
+                           f"row_missing={mi.shape[0]}, row_maf={mf.shape[0]}")
+    if ri.size > 1 and np.any(np.diff(ri) < 0):
+        raise RuntimeError("prepared row_indices must be sorted in ascending BED order")
+    return ri, fl, mi, mf
+
+
+def _lm_stream_rows(prefix, n, sample_ids, meta, maf_threshold, max_missing_rate, snps_only, mmap_window_mb, packed,
+                    packed_n_samples):
+    """Payload, sample selection and kept rows of the two LM streaming routes: the panel over the selected samples, the
+    kept rows in BED order with their flip, allele frequency (f32) and missing count, the BIM columns and the number of rows
+    scanned.  Without prepared metadata the rows pass `lm2.row_filter` (src/stats/glm2.rs:634-717: no flip, no het filter);
+    prepared rows arrive filtered, their missing count is round(row_missing) (glm2.rs:568-577)."""
+    from . import bed as _bed
+    from . import lm2
+    bed_prefix = _bed_prefix(prefix)
+    fam = _bed.read_fam_ids(bed_prefix)
+    if sample_ids is None:
+        idx = None
+    else:
+        pos = {s: i for i, s in enumerate(fam)}
+        missing = [s for s in sample_ids if str(s) not in pos]
+        if missing:
+            raise RuntimeError(f"sample id not found in FAM: {missing[0]}")
+        idx = np.array([pos[str(s)] for s in sample_ids], dtype=np.int64)
+    n_sel = len(fam) if idx is None else int(idx.shape[0])
+    if n_sel != n:
+        raise RuntimeError(f"sample_ids length mismatch: selected n={n_sel} but len(y)={n}")
+    if packed is not None or int(packed_n_samples) > 0:
+        if packed is None or int(packed_n_samples) <= 0:
+            raise RuntimeError("the staged payload needs both `packed` and `packed_n_samples` > 0")
+        if int(packed_n_samples) != len(fam):
+            raise RuntimeError(f"packed_n_samples {int(packed_n_samples)} != {len(fam)} samples of {bed_prefix}.fam")
+        pk = packed
+        bim = _bed.read_bim(bed_prefix)
+    else:
+        pk, _n_full, bim = _bed.stage_bed_payload(bed_prefix, mmap_window_mb)
+    panel = _panel(pk, len(fam), idx)
+    if panel.m != len(bim.snp):
+        raise RuntimeError(f"payload has {panel.m} SNP rows, {bed_prefix}.bim lists {len(bim.snp)}")
+    if meta is None:
+        keep, af, miss = lm2.row_filter(panel.counts(), n, maf_threshold, max_missing_rate)
+        rows = np.nonzero(keep)[0].astype(np.int64)
+        flip, af, miss, total = np.zeros(len(rows), dtype=bool), af[rows], miss[rows].astype(np.int64), panel.m
+    else:
+        rows, flip, mi, af = meta
+        if rows.size and (rows.min() < 0 or rows.max() >= panel.m):
+            raise RuntimeError(f"row_indices out of range for n_snps={panel.m}")
+        with np.errstate(invalid="ignore"):
+            miss = np.where(np.isfinite(mi) & (mi >= 0), np.floor(np.abs(mi.astype(np.float64)) + 0.5), 0).astype(np.int64)
+        total = int(rows.shape[0])
+    if snps_only:
+        ok = _bed.snps_only_mask(bim)[rows]
+        rows, flip, af, miss = rows[ok], flip[ok], af[ok], miss[ok]
+    cols = ([bim.chrom[j] for j in rows], [int(bim.pos[j]) for j in rows], [bim.snp[j] for j in rows],
+            [bim.a0[j] for j in rows], [bim.a1[j] for j in rows])
+    return panel, rows, flip, af, miss, cols, total
+
+
+def lm_stream_bed_to_tsv(prefix, y, x, ixx, out_tsv, sample_ids=None, row_indices=None, row_flip=None, row_missing=None,
+                         row_maf=None, maf_threshold=0.0, max_missing_rate=1.0, genetic_model="add", het_threshold=0.02,
+                         snps_only=False, chunk_size=10000, threads=0, progress_callback=None, progress_every=0,
+                         mmap_window_mb=None, packed=None, packed_n_samples=0):
+    """src/stats/glm.rs:2339 ff.: the plain LM scan of a PLINK prefix with its own row filter, written as the 11-column LM
+    table (`miss` = the count of missing samples) -> (rows written, rows scanned).  `x` (n, q0) carries the intercept; `ixx` =
+    (X'X)^-1 or None.  The arithmetic is that of `lm_block_assoc_packed` (`pipeline.scan_rows_lm`).  `packed` /
+    `packed_n_samples`: an already staged payload of the prefix (host array or device tensor) instead of reading the .bed."""
+    from . import pipeline as pl
+    from .tsv import write_assoc_tsv_counts
+    y, x = _lm_stream_checks(y, x, maf_threshold, max_missing_rate, genetic_model, het_threshold, chunk_size, mmap_window_mb)
+    n, q0 = int(y.shape[0]), int(x.shape[1])
+    if n <= q0 + 1:
+        raise RuntimeError(f"n too small: require n > q0+1, got n={n}, q0={q0}")
+    if ixx is not None:
+        ixx = _c(ixx, np.float64)
+        if ixx.shape != (q0, q0):
+            raise RuntimeError("ixx must be (q0,q0)")
+    meta = _lm_prepared_meta(row_indices, row_flip, row_missing, row_maf)
+    panel, rows, flip, af, miss, cols, total = _lm_stream_rows(prefix, n, sample_ids, meta, maf_threshold, max_missing_rate,
+                                                               snps_only, mmap_window_mb, packed, packed_n_samples)
+    out = pl.scan_rows_lm(panel, rows, af, x, y, flip=flip, ixx=ixx, progress=progress_callback,
+                          progress_every=progress_every)
+    written = write_assoc_tsv_counts(out_tsv, *cols, af, miss.astype(np.float32), out[:, :3].cpu().numpy())
+    _done(progress_callback, total)
+    return written, total
+
+
+def lm2_stream_bed_to_tsv(prefix, y, x, cov_all, cov_indices, out_tsv, sample_ids=None, row_indices=None, row_flip=None,
+                          row_missing=None, row_maf=None, maf_threshold=0.0, max_missing_rate=1.0, genetic_model="add",
+                          het_threshold=0.02, snps_only=False, chunk_size=10000, threads=0, progress_callback=None,
+                          progress_every=0, mmap_window_mb=None, packed=None, packed_n_samples=0):
+    """src/stats/glm2.rs:364-885: the SNP-by-covariate interaction scan y ~ X + g + g o c_1 + ... + g o c_k of a PLINK prefix,
+    c = the columns `cov_indices` of `cov_all` (n, n_cov), written as the LM2 table (`tsv.write_lm2_tsv`) -> (rows written,
+    rows scanned).  `x` (n, q_base) carries the intercept.  At most 8 interaction columns in this build.  `packed` /
+    `packed_n_samples`: an already staged payload of the prefix (host array or device tensor) instead of reading the .bed."""
+    from . import pipeline as pl
+    from .lm2 import LM2_MAX_INTERACTIONS
+    from .tsv import write_lm2_tsv
+    y, x = _lm_stream_checks(y, x, maf_threshold, max_missing_rate, genetic_model, het_threshold, chunk_size, mmap_window_mb)
+    n, q_base = int(y.shape[0]), int(x.shape[1])
+    cov = _c(cov_all, np.float64)
+    if cov.ndim != 2 or cov.shape[0] != n:
+        raise RuntimeError("cov_all.n_rows must equal len(y)")
+    n_cov = int(cov.shape[1])
+    if n_cov == 0:
+        raise RuntimeError("LM2 requires cov_all with at least one column")
+    pick = []
+    for v in _c(cov_indices, np.int64).ravel():
+        if v < 0:
+            raise RuntimeError("cov_indices must be >= 0")
+        if v >= n_cov:
+            raise RuntimeError(f"cov_indices out of range: {int(v)} >= {n_cov}")
+        pick.append(int(v))
+    if not pick:
+        raise RuntimeError("LM2 requires at least one explicitly selected covariate column.")
+    k = len(pick)
+    if n <= q_base + 1 + k:
+        raise RuntimeError(f"n too small: require n > q_base + 1 + n_interactions, got n={n}, q_base={q_base}, "
+                           f"n_interactions={k}")
+    if k > LM2_MAX_INTERACTIONS:
+        raise RuntimeError(f"LM2 supports at most {LM2_MAX_INTERACTIONS} interaction covariates in this build, got {k}")
+    meta = _lm_prepared_meta(row_indices, row_flip, row_missing, row_maf)
+    panel, rows, flip, af, miss, cols, total = _lm_stream_rows(prefix, n, sample_ids, meta, maf_threshold, max_missing_rate,
+                                                               snps_only, mmap_window_mb, packed, packed_n_samples)
+    out = pl.scan_rows_lm2(panel, rows, af, x, cov[:, pick], y, flip=flip, progress=progress_callback,
+                           progress_every=progress_every)
+    written = write_lm2_tsv(out_tsv, *cols, af, miss, out.cpu().numpy(), pick)
+    _done(progress_callback, total)
+    return written, total
+
+
 # ------------------------------------------------------------------------------------------------
 # Genotype rows as numbers and the two matrix-free products the reference's Python layer asks for beside the path
 # (src/stats/packed.rs:577-760, 2060-2560): decode of selected rows, M'alpha, cross-GRM times alpha

@@ -1047,6 +1047,64 @@ def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, 
     return out
 
 
+def scan_rows_lm2(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, cov_sel: np.ndarray, y: np.ndarray, flip=None,
+                  block_rows=LM_BLOCK_ROWS, progress=None, progress_every=0):
+    """SNP-by-covariate interaction scan of the given SNP rows of a resident panel (`lm2_fit_single_snp`, src/stats/glm2.rs:
+    142-325): per SNP y ~ X + g + g o c_1 + ... + g o c_k with c = the columns of `cov_sel` (n, k), k <= 8; `x` (n, q_base)
+    includes the intercept.  Host: the Gram-Schmidt basis of X, r_y and the weight columns (`lm2.py`), once; device: one pass
+    of the moment kernel and the per-SNP algebra per `block_rows` rows (`jxg_lm2_scan_p32`); rows whose Schur complement has
+    no plain inverse come back flagged and are solved here with the pseudo-inverse, from the device sums.
+    Returns a (len(rows), 4 (1 + k) + 4) f64 device tensor: (beta, se, chisq, pwald) of the SNP and of each interaction, then
+    chisq_int_joint, p_int_joint, chisq_joint, p_joint."""
+    from . import lm2
+    from .janusx import _raw_additive_lut
+    dev, n = panel.device, panel.n
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    cov_sel = np.ascontiguousarray(cov_sel, dtype=np.float64).reshape(len(y), -1)
+    if y.shape[0] != n or x.shape[0] != n:
+        raise RuntimeError(f"selected sample count {panel.n} != len(y) {y.shape[0]}")
+    q_base, k = int(x.shape[1]), int(cov_sel.shape[1])
+    if k < 1:
+        raise RuntimeError("LM2 requires at least one explicitly selected covariate column.")
+    if k > lm2.LM2_MAX_INTERACTIONS:
+        raise RuntimeError(f"LM2 supports at most {lm2.LM2_MAX_INTERACTIONS} interaction covariates in this build, got {k}")
+    if n <= q_base + 1 + k:
+        raise RuntimeError(f"n too small: require n > q_base + 1 + n_interactions, got n={n}, q_base={q_base}, "
+                           f"n_interactions={k}")
+    if not np.all(np.isfinite(cov_sel)):
+        raise RuntimeError("LM2 interaction covariates contain non-finite values")
+    mk, ncol = len(rows), 4 * (1 + k) + 4
+    out = torch.empty((mk, ncol), dtype=torch.float64, device=dev)
+    if mk == 0:
+        return out
+    q, r_y, rss0 = lm2.qr_projection(x, y)
+    q_rank, df = int(q.shape[1]), n - (q_base + 1 + k)       # df counts the columns of X as given, also when some were dropped
+    img, nblk, nblk_v = lm2.weight_image(*lm2.weight_columns(q, r_y, cov_sel))
+    img_t = torch.from_numpy(img).to(dev)
+    rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
+    # [0, max(2 af, 0), 1, 2], the calls mirrored where `flip` (`decode_packed_row_model_into_f64`, src/decode/decode.rs:307-364)
+    lut_t = torch.from_numpy(_raw_additive_lut(af, np.zeros(mk, dtype=bool) if flip is None else flip, True)).to(dev)
+    br = int(max(1, min(block_rows, mk)))
+    step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
+    sums = torch.empty((br, nblk * 16), dtype=torch.float64, device=dev)
+    flag = torch.zeros(br, dtype=torch.int32, device=dev)
+    for r0 in range(0, mk, br):
+        nr = min(br, mk - r0)
+        check(lib().jxg_lm2_scan_p32(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr, lut_t[r0:].data_ptr(), _ptr(img_t),
+                                     nblk, nblk_v, q_rank, k, rss0, df, _ptr(sums), out[r0:].data_ptr(), _ptr(flag), 0, _stream()))
+        # reading the flags waits for the block: nothing at the default block size, a serialisation with small `block_rows`
+        bad = torch.nonzero(flag[:nr]).ravel()
+        if bad.numel():
+            host = sums[bad].cpu().numpy()
+            fixed = np.stack([lm2.solve_from_sums(host[i], q_rank, k, nblk_v * 16, rss0, df) for i in range(len(host))])
+            out[r0 + bad] = torch.from_numpy(fixed).to(dev)
+        if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
+            last_tick = r0 + nr
+            progress(r0 + nr, mk)
+    return out
+
+
 @dataclass
 class GwasResult:
     keep: np.ndarray        # (m,) bool, kept SNPs in BED order

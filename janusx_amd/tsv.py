@@ -210,3 +210,47 @@ class AsyncAssocTsvWriter:
                          np.zeros((0, self.ncol)), False)
         os.replace(self.tmp, self.path)
         return self.rows
+
+
+# ---- LM2 table (src/stats/glm2.rs:58-67, 327-362) ---------------------------------------------------------------------
+
+def lm2_header(cov_indices) -> str:
+    """The eleven association columns, `beta_i{idx} se_i{idx} pwald_i{idx}` per selected covariate column (idx = its index into
+    the merged covariate table, in the order of the selection), then the two joint tests."""
+    cols = "chrom\tpos\tsnp\tallele0\tallele1\taf\tmiss\tbeta\tse\tchisq\tpwald"
+    for idx in cov_indices:
+        cols += f"\tbeta_i{int(idx)}\tse_i{int(idx)}\tpwald_i{int(idx)}"
+    return cols + "\tchisq_int_joint\tp_int_joint\tchisq_joint\tp_joint\n"
+
+
+def format_lm2_row(chrom, pos, snp, a0, a1, af, miss_count, st) -> str:
+    """st = one row of `pipeline.scan_rows_lm2`: (beta, se, chisq, pwald) per coefficient, then the two (chisq, p) pairs.
+    af `{:.4}`, miss as an integer, beta / se `{:.4}`, p `{:.4e}`, chisq `format_chisq_value` (src/math/linalg.rs:300-312)."""
+    k = (len(st) - 8) // 4
+    row = (f"{chrom}\t{pos}\t{snp}\t{a0}\t{a1}\t{fmt_f4(float(af))}\t{int(miss_count)}\t{fmt_f4(float(st[0]))}\t"
+           f"{fmt_f4(float(st[1]))}\t{fmt_e4(float(st[2]))}\t{fmt_e4(float(st[3]))}")
+    for j in range(1, k + 1):
+        row += f"\t{fmt_f4(float(st[4 * j]))}\t{fmt_f4(float(st[4 * j + 1]))}\t{fmt_e4(float(st[4 * j + 3]))}"
+    t = 4 * (k + 1)
+    return row + (f"\t{fmt_e4(float(st[t]))}\t{fmt_e4(float(st[t + 1]))}\t{fmt_e4(float(st[t + 2]))}\t"
+                  f"{fmt_e4(float(st[t + 3]))}\n")
+
+
+def write_lm2_tsv(path, chrom, pos, snp, a0, a1, af, miss_counts, stats, cov_indices, resolve=True) -> int:
+    """stats (rows, 4 (1 + k) + 4) f64 in BED order of the kept SNPs, k = len(cov_indices).  Returns rows written."""
+    k = len(cov_indices)
+    if stats.ndim != 2 or stats.shape[1] != 4 * (1 + k) + 4:
+        raise RuntimeError(f"LM2 result table has {stats.shape} columns, {4 * (1 + k) + 4} expected for {k} interactions")
+    tmp = f"{path}.tmp.{os.getpid()}"
+    with open(tmp, "w") as fh:
+        fh.write(lm2_header(cov_indices))
+        buf = []
+        for i in range(stats.shape[0]):
+            name = resolve_snp_name(snp[i], chrom[i], pos[i]) if resolve else snp[i]
+            buf.append(format_lm2_row(chrom[i], pos[i], name, a0[i], a1[i], af[i], miss_counts[i], stats[i]))
+            if len(buf) >= 8192:
+                fh.write("".join(buf))
+                buf = []
+        fh.write("".join(buf))
+    os.replace(tmp, path)
+    return int(stats.shape[0])
