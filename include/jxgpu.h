@@ -789,6 +789,31 @@ int jxg_ld_score_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t
 int jxg_sample_counts_p32(const uint8_t *d_p32, int64_t m, int n, int32_t *d_counts, void *stream);
 int jxg_sample_counts_chunk(void);
 
+/* ---- KING robust kinship and the unrelated-sample set (`jx grm -king`; csrc/k_king.hip; src/math/KING.rs, Manichaikul et al. 2010).
+ * With Z / H / A the indicators of the codes 00 / 10 / 11 of a sample over the m rows of a P32 image and N = Z + H + A (01 = missing
+ * and the pad samples of the last tile count nowhere), the pair counts of `king_pair_counts_serial` (src/math/bitwise.rs:259-300;
+ * fields of `KingBitCounts`, :127-135) are integer Grams over the SNP axis on the int8 matrix pipes:
+ *     shared_nonmissing = N_i N_j, ibs0 = Z_i A_j + A_i Z_j, same_hom = Z_i Z_j + A_i A_j, both_het = H_i H_j, het_i_obs = H_i N_j,
+ *     het_j_obs = N_i H_j,   kinship = (both_het - 2 ibs0) / (het_i_obs + het_j_obs) in f64, NaN when the denominator is 0
+ * (`king_stats_from_counts`, src/math/KING.rs:217-243).
+ *   jxg_king_related_p32 : every pair i < j whose kinship is finite and >= kinship_threshold (finite), as rows (d_i, d_j, d_ibs0,
+ *                          d_kinship) of `capacity` slots each, in no particular order (`king_related_pairs_from_bitplanes`,
+ *                          :430-528, without its early stop: the exact set, see README "Known differences").  *d_count (device,
+ *                          64 bits) ends at the number of such pairs whatever the capacity; rows beyond the capacity are not
+ *                          written and the caller runs again with a larger buffer.  No n x n matrix is formed.
+ *                          JXGPU_KING_TILE = 64 | 128 forces the tile shape (default: 128 from 1024 tiles of 128 x 128 on).
+ *   jxg_king_counts_p32  : d_counts (6, i1 - i0, j1 - j0) int32, planes in the field order of `KingBitCounts`, of the pairs
+ *                          (i, j), i in [i0, i1), j in [j0, j1) (any pairs: i >= j included).
+ *   jx_king_prune        : host, no GPU call.  `king_prune_related_graph` (:669-743) on a CSR graph (offsets n + 1, neighbors): a
+ *                          max-heap of (live degree, sample id) with lazy deletion, ties to the larger id, popped until the top live
+ *                          degree is <= 0.  removed (pop order) and kept (ascending) hold n slots each.  A neighbour >= n is refused.
+ * m <= 2^29 rows (exact i32 sums). */
+int jxg_king_related_p32(const uint8_t *d_p32, int64_t m, int n, double kinship_threshold, int64_t capacity, uint32_t *d_i,
+                         uint32_t *d_j, uint32_t *d_ibs0, double *d_kinship, uint64_t *d_count, void *stream);
+int jxg_king_counts_p32(const uint8_t *d_p32, int64_t m, int n, int i0, int i1, int j0, int j1, int32_t *d_counts, void *stream);
+int jx_king_prune(int64_t n, const int64_t *offsets, const uint32_t *neighbors, uint32_t *kept, int64_t *n_kept, uint32_t *removed,
+                  int64_t *n_removed);
+
 #ifdef __cplusplus
 }
 #endif

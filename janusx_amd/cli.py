@@ -153,6 +153,46 @@ def _dist_setup():
     return rank, world
 
 
+def _check_king_args(args):
+    """`jx grm -bfile PREFIX -king [THRESHOLD]`: the combinations that are refused, before any file or device is touched."""
+    for flag, on in (("-sparse", args.sparse is not None), ("-grm", args.grm is not None), ("-txt", bool(getattr(args, "txt", False)))):
+        if on:
+            raise SystemExit(f"grm: -king cannot be combined with {flag}")
+    if not args.bfile:
+        raise SystemExit("grm: -king needs -bfile PREFIX")
+    if not np.isfinite(float(args.king)):
+        raise SystemExit("grm: KING kinship_threshold must be finite")
+
+
+def _cmd_grm_king(args):
+    """KING robust kinship of a PLINK prefix (an extension: the reference has the function `king_unrelated_set_from_bed`,
+    src/math/KING.rs:794-824, and no command): related pairs, the unrelated set and the removed samples, filtered by this
+    command's -maf / -geno / -snps-only with het threshold 0."""
+    _check_king_args(args)
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    from . import janusx as jxrs
+    from .bed import read_fam_ids
+    src = jxrs._bed_prefix(args.bfile)
+    out = _resolve_out(args, src)
+    t0 = time.perf_counter()
+    try:
+        kept, removed, pairs, n_sites, n = jxrs._king_from_bed(src, args.maf, args.geno, 0.0, bool(getattr(args, "snps_only", False)),
+                                                               float(args.king))
+    except (RuntimeError, ValueError) as e:
+        raise SystemExit(f"grm: {e}") from None
+    ids = read_fam_ids(src)
+    if len(ids) != n:
+        raise SystemExit(f"grm: {src}.fam lists {len(ids)} samples, the payload has {n}")
+    paths = jxrs.write_king_tables(out, ids, n_sites, pairs, kept, removed)
+    print(f"KING kinship >= {float(args.king):g}: n={n} sites={n_sites} edges={int(pairs[0].shape[0])} kept={int(kept.shape[0])} "
+          f"removed={int(removed.shape[0])} ({time.perf_counter() - t0:.2f}s)")
+    for path in paths:
+        print(f"  {path}")
+    return 0
+
+
 def cmd_grm(args):
     from . import janusx as jxrs
     from .bed import read_fam_ids
@@ -160,6 +200,8 @@ def cmd_grm(args):
         raise SystemExit("grm needs -bfile PREFIX (or -grm FILE.npy -sparse [cutoff])")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and args.grm is not None:
         raise SystemExit("thresholding an existing dense GRM runs on one GPU: start it without the launcher")
+    if getattr(args, "king", None) is not None:
+        return _cmd_grm_king(args)
     out = _resolve_out(args, args.bfile or args.grm)
     t0 = time.perf_counter()
     if args.grm is not None:
@@ -1514,6 +1556,11 @@ def main(argv=None):
                    help="write the dense GRM as plain text ({out}.cGRM.txt, %%.6f) instead of NPY")
     r.add_argument("-sparse", "--sparse", nargs="?", const=0.05, default=None, type=float,
                    help="write a sparse `.spgrm` keeping off-diagonal kinship > cutoff (negative: keep everything)")
+    r.add_argument("-king", "--king", nargs="?", const=0.05, default=None, type=float,
+                   help="KING robust kinship instead of a GRM (an extension: the reference has the function and no command): "
+                        "related pairs with kinship >= THRESHOLD (bare flag: 0.05) -> {out}.king.kin0, the greedy unrelated set -> "
+                        "{out}.king.unrelated.id and the removed samples -> {out}.king.related.id.  Sites are filtered by this "
+                        "command's -maf / -geno defaults (0.02 / 0.05), not the function's (0.01 / 0.1); not with -sparse / -grm / -txt")
     r.add_argument("-t", "--thread", type=int, default=0, help="accepted for compatibility; unused")
     r.set_defaults(func=cmd_grm)
     q = sub.add_parser("gs")

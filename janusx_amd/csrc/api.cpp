@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <mutex>
 #include <new>
+#include <queue>
 #include <chrono>
 #include <vector>
 
@@ -1367,5 +1368,52 @@ extern "C" int jx_ld_prune_greedy(const double *maf, int64_t nrows, const int64_
             if (!at_least_one_prune) break;
         }
     }
+    return 0;
+}
+
+// Greedy unrelated set of a related-pair graph (`king_prune_related_graph`, src/math/KING.rs:669-743): CSR graph (offsets n + 1,
+// neighbors), a max-heap of (live degree, sample id) with lazy deletion - ties go to the larger id - popped until the top live
+// degree is <= 0.  removed: in pop order; kept: ascending; both hold n slots, the counts go to n_kept / n_removed.
+extern "C" int jx_king_prune(int64_t n, const int64_t *offsets, const uint32_t *neighbors, uint32_t *kept, int64_t *n_kept,
+                             uint32_t *removed, int64_t *n_removed) {
+    if (n < 0 || n > 0xffffffffLL) return fail("KING adjacency uses u32 sample ids; got n_samples=" + std::to_string(n) + " > 4294967295");
+    if (n > 0 && offsets[0] != 0) return fail("jx_king_prune: offsets[0] must be 0");
+    for (int64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return fail("jx_king_prune: offsets must not decrease");
+        if (offsets[i + 1] - offsets[i] > 0x7fffffffLL) return fail("jx_king_prune: degree beyond int32");
+        for (int64_t e = offsets[i]; e < offsets[i + 1]; ++e)
+            if ((int64_t)neighbors[e] >= n)
+                return fail("KING neighbor index out of range: neighbors[" + std::to_string(i) + "] contains " +
+                            std::to_string(neighbors[e]) + " >= " + std::to_string(n));
+    }
+    std::vector<int32_t> live((size_t)n);
+    std::vector<uint8_t> active((size_t)n, 1);
+    std::vector<std::pair<int32_t, uint32_t>> start;
+    start.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        live[i] = (int32_t)(offsets[i + 1] - offsets[i]);
+        start.emplace_back(live[i], (uint32_t)i);
+    }
+    std::priority_queue<std::pair<int32_t, uint32_t>> heap(std::less<std::pair<int32_t, uint32_t>>(), std::move(start));
+    int64_t nr = 0;
+    while (!heap.empty()) {
+        const std::pair<int32_t, uint32_t> top = heap.top();
+        heap.pop();
+        const uint32_t id = top.second;
+        if (!active[id] || top.first != live[id]) continue;      // a stale entry
+        if (live[id] <= 0) break;
+        active[id] = 0;
+        live[id] = 0;
+        removed[nr++] = id;
+        for (int64_t e = offsets[id]; e < offsets[id + 1]; ++e) {
+            const uint32_t nb = neighbors[e];
+            if (active[nb]) heap.emplace(--live[nb], nb);
+        }
+    }
+    int64_t nk = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (active[i]) kept[nk++] = (uint32_t)i;
+    *n_kept = nk;
+    *n_removed = nr;
     return 0;
 }

@@ -5836,3 +5836,254 @@ def gstats_bed_ldscore(prefix, window_kind, window_value, threads=0):
         raise RuntimeError(f"BED/BIM row mismatch: bed={m}, bim={int(cc.shape[0])}")
     m_counts, ldsc = ldscore_packed(payload, n, cc, ps, cm, window_kind, window_value)
     return m_counts, ldsc, n
+
+
+# ------------------------------------------------------------------------------------------------
+# KING (src/math/KING.rs)
+# ------------------------------------------------------------------------------------------------
+# Robust kinship of Manichaikul et al. 2010 from the integer pair counts of csrc/k_king.hip (exact i32 Grams of the code
+# indicators on the int8 matrix pipes), the related-pair graph and the greedy unrelated set.  The reference's early stop
+# (`king_kinship_upper_bound`, :245-262) is not mirrored: the related set is the exact one (README, "Known differences").
+
+KING_DEFAULT_KINSHIP_THRESHOLD = 0.05
+KING_DEFAULT_MAX_EXACT_PAIRS = 8_000_000_000
+KING_MAX_ROWS = 1 << 29
+_KING_COUNT_FIELDS = ("shared_nonmissing", "ibs0", "same_hom", "both_het", "het_i_obs", "het_j_obs")
+
+
+def _king_validate(packed, n_samples):
+    """`validate_king_inputs`, src/math/KING.rs:96-125, on a payload (m, bytes_per_snp) or a flat byte array -> (n, m); no device
+    call."""
+    n = int(n_samples)
+    if n <= 0:
+        raise RuntimeError("KING requires n_samples > 0")
+    if n > 0xFFFFFFFF:
+        raise RuntimeError(f"KING adjacency uses u32 sample ids; got n_samples={n} > 4294967295")
+    bps = (n + 3) // 4
+    shape = tuple(int(s) for s in packed.shape)
+    if len(shape) not in (1, 2):
+        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
+    nbytes = int(np.prod(shape, dtype=np.int64)) if shape else 0
+    if nbytes == 0:
+        raise RuntimeError("KING requires non-empty packed genotype data")
+    if (len(shape) == 2 and shape[1] != bps) or nbytes % bps != 0:
+        raise RuntimeError(f"KING packed payload length mismatch: packed_bytes={nbytes} not divisible by bytes_per_snp={bps}")
+    m = nbytes // bps
+    if m > KING_MAX_ROWS:
+        raise RuntimeError(f"KING pair counts are exact int32 sums: at most {KING_MAX_ROWS} variant sites, got {m}")
+    return n, m
+
+
+def _king_payload2d(packed, n):
+    return packed.reshape(-1, (n + 3) // 4) if len(packed.shape) == 1 else packed
+
+
+def _king_threshold(kinship_threshold):
+    t = float(kinship_threshold)
+    if not np.isfinite(t):
+        raise RuntimeError("KING kinship_threshold must be finite")
+    return t
+
+
+def _king_enforce_exact_budget(n):
+    """`king_enforce_exact_budget`, src/math/KING.rs:200-215: JANUSX_KING_MAX_EXACT_PAIRS (default 8e9, 0 = no limit)."""
+    raw = os.environ.get("JANUSX_KING_MAX_EXACT_PAIRS")
+    limit = KING_DEFAULT_MAX_EXACT_PAIRS
+    if raw is not None:
+        txt = raw.strip()
+        if txt.isascii() and (txt[1:] if txt[:1] == "+" else txt).isdigit() and int(txt) < (1 << 64):
+            limit = int(txt)
+    if limit == 0:
+        return
+    pairs = int(n) * max(int(n) - 1, 0) // 2
+    if pairs > limit:
+        raise RuntimeError(f"KING exact all-pairs budget exceeded: pairs={pairs} > limit={limit}. Set JANUSX_KING_MAX_EXACT_PAIRS=0 "
+                           "to force, or raise the limit explicitly.")
+
+
+def _king_counts(panel, i0, i1, j0, j1):
+    import torch
+    from .pipeline import _ptr, _stream
+    out = torch.empty((6, i1 - i0, j1 - j0), dtype=torch.int32, device=panel.device)
+    check(lib().jxg_king_counts_p32(_ptr(panel.p32), panel.m, panel.n, int(i0), int(i1), int(j0), int(j1), _ptr(out), _stream()))
+    return out.cpu().numpy()
+
+
+def king_pair_counts_packed(packed, n_samples, i0, i1, j0, j1):
+    """(6, i1 - i0, j1 - j0) int32 pair counts of the samples [i0, i1) x [j0, j1) of a packed payload (host array or torch CUDA
+    tensor), planes in the field order of `KingBitCounts` (src/math/bitwise.rs:127-135): shared_nonmissing, ibs0, same_hom,
+    both_het, het_i_obs, het_j_obs (extension: the reference counts one pair per call)."""
+    n, _m = _king_validate(packed, n_samples)
+    i0, i1, j0, j1 = int(i0), int(i1), int(j0), int(j1)
+    for name, lo, hi in (("sample_i", i0, i1), ("sample_j", j0, j1)):
+        if lo < 0 or hi < lo:
+            raise RuntimeError(f"KING {name} range [{lo}, {hi}) is not a range")
+        if hi > n:
+            raise RuntimeError(f"KING {name} out of range: {hi - 1} >= {n}")
+    if i1 == i0 or j1 == j0:
+        return np.zeros((6, i1 - i0, j1 - j0), dtype=np.int32)
+    return _king_counts(_panel(_king_payload2d(packed, n), n), i0, i1, j0, j1)
+
+
+def _king_stats_from_counts(c):
+    """`king_stats_from_counts`, src/math/KING.rs:217-243, from the six counts of one pair."""
+    shared, ibs0, same_hom, both_het, het_i, het_j = (int(v) for v in c)
+    ibs2 = both_het + same_hom
+    denom = het_i + het_j
+    kin = (float(both_het) - 2.0 * float(ibs0)) / float(denom) if denom > 0 else float("nan")
+    return {"shared_nonmissing": shared, "ibs0": ibs0, "ibs1": max(shared - (ibs0 + ibs2), 0), "ibs2": ibs2, "het_i_obs": het_i,
+            "het_j_obs": het_j, "both_het": both_het, "kinship": kin}
+
+
+def king_pair_stats(packed, n_samples, i, j):
+    """`king_pair_stats`, src/math/KING.rs:410-428, of the samples i and j of a packed payload -> dict with the `KingPairStats`
+    fields."""
+    n, _m = _king_validate(packed, n_samples)
+    i, j = int(i), int(j)
+    if i < 0 or i >= n:
+        raise RuntimeError(f"KING sample_i out of range: {i} >= {n}")
+    if j < 0 or j >= n:
+        raise RuntimeError(f"KING sample_j out of range: {j} >= {n}")
+    return _king_stats_from_counts(_king_counts(_panel(_king_payload2d(packed, n), n), i, i + 1, j, j + 1)[:, 0, 0])
+
+
+def _king_related_pairs(panel, threshold, max_rows=None, timings=None):
+    """Sorted related-pair table of a panel: the fused launch into a buffer of `max_rows` rows (default: 4 n + 65536), run again
+    with a buffer of the counted size when the count exceeds it."""
+    import torch
+    from .pipeline import _ptr, _stream
+    n = panel.n
+    cap = int(max_rows) if max_rows is not None else min(n * (n - 1) // 2, 4 * n + 65536)
+    cap = max(cap, 1)
+    dev = panel.device
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    launches = 0
+    t0 = time.perf_counter()
+    while True:
+        bi, bj, b0 = (torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3))
+        bk = torch.empty(cap, dtype=torch.float64, device=dev)
+        check(lib().jxg_king_related_p32(_ptr(panel.p32), panel.m, n, threshold, cap, _ptr(bi), _ptr(bj), _ptr(b0), _ptr(bk), _ptr(count),
+                                         _stream()))
+        launches += 1
+        total = int(count.item())
+        if total <= cap:
+            break
+        del bi, bj, b0, bk
+        cap = total                                   # the count is exact: the second launch fits
+    t1 = time.perf_counter()
+    i = bi[:total].cpu().numpy().view(np.uint32)
+    j = bj[:total].cpu().numpy().view(np.uint32)
+    order = np.lexsort((j, i))
+    if timings is not None:
+        timings.update(pairs_s=t1 - t0, launches=launches, rows=total)
+    return (np.ascontiguousarray(i[order]), np.ascontiguousarray(j[order]),
+            np.ascontiguousarray(b0[:total].cpu().numpy().view(np.uint32)[order]), np.ascontiguousarray(bk[:total].cpu().numpy()[order]))
+
+
+def _king_check_pairs_args(packed, n_samples, kinship_threshold, max_rows=None):
+    n, m = _king_validate(packed, n_samples)
+    t = _king_threshold(kinship_threshold)
+    if max_rows is not None and int(max_rows) < 1:
+        raise RuntimeError("KING max_rows must be >= 1")
+    _king_enforce_exact_budget(n)
+    return n, m, t
+
+
+def king_related_pairs_packed(packed, n_samples, kinship_threshold=KING_DEFAULT_KINSHIP_THRESHOLD, max_rows=None):
+    """`king_related_pairs_from_packed`, src/math/KING.rs:530-538: the pairs i < j with a finite kinship >= the threshold ->
+    (i uint32, j uint32, ibs0 uint32, kinship f64), ordered by (i, j).  `max_rows`: rows of the first device buffer (the launch is
+    repeated with the counted size when there are more)."""
+    n, _m, t = _king_check_pairs_args(packed, n_samples, kinship_threshold, max_rows)
+    return _king_related_pairs(_panel(_king_payload2d(packed, n), n), t, max_rows)
+
+
+def _king_graph(n, pi, pj):
+    """CSR adjacency of the related pairs (ordered by (i, j)): neighbours of a sample ascending (`king_related_graph_from_bitplanes`,
+    src/math/KING.rs:631-648) -> (offsets int64 (n + 1), neighbors uint32, degrees int32)."""
+    src = np.concatenate([pi, pj]).astype(np.int64)
+    dst = np.concatenate([pj, pi]).astype(np.uint32)
+    order = np.lexsort((dst, src))
+    degrees = np.bincount(src, minlength=n).astype(np.int32)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(degrees, out=offsets[1:])
+    return offsets, np.ascontiguousarray(dst[order]), degrees
+
+
+def king_related_graph_packed(packed, n_samples, kinship_threshold=KING_DEFAULT_KINSHIP_THRESHOLD):
+    """`king_related_graph_from_packed`, src/math/KING.rs:659-667 -> (neighbors: list of n ascending uint32 arrays, degrees int32 (n),
+    edge_count, n_sites)."""
+    n, m, t = _king_check_pairs_args(packed, n_samples, kinship_threshold)
+    pi, pj, _b0, _k = _king_related_pairs(_panel(_king_payload2d(packed, n), n), t)
+    offsets, nbrs, degrees = _king_graph(n, pi, pj)
+    return [nbrs[offsets[s]:offsets[s + 1]] for s in range(n)], degrees, int(pi.shape[0]), m
+
+
+def king_prune_related_graph(offsets, neighbors):
+    """`king_prune_related_graph`, src/math/KING.rs:669-743, on a CSR graph (`jx_king_prune`, host) -> (kept uint32 ascending, removed
+    uint32 in removal order)."""
+    offsets = _c(offsets, np.int64).ravel()
+    neighbors = _c(neighbors, np.uint32).ravel()
+    n = int(offsets.shape[0]) - 1
+    if n < 0:
+        raise RuntimeError("KING graph offsets must hold n + 1 entries")
+    if n and (int(offsets[-1]) != int(neighbors.shape[0]) or int(offsets[0]) != 0):
+        raise RuntimeError(f"KING graph offsets do not match its neighbours: offsets[n]={int(offsets[-1])} neighbors={int(neighbors.shape[0])}")
+    kept, removed = np.empty(max(n, 1), dtype=np.uint32), np.empty(max(n, 1), dtype=np.uint32)
+    nk, nr = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    check(lib().jx_king_prune(n, _p(offsets), _p(neighbors), _p(kept), _p(nk), _p(removed), _p(nr)))
+    return kept[:int(nk[0])].copy(), removed[:int(nr[0])].copy()
+
+
+def _king_unrelated_set(panel, threshold, timings=None):
+    pi, pj, b0, kin = _king_related_pairs(panel, threshold, timings=timings)
+    t0 = time.perf_counter()
+    offsets, nbrs, _deg = _king_graph(panel.n, pi, pj)
+    kept, removed = king_prune_related_graph(offsets, nbrs)
+    if timings is not None:
+        timings.update(prune_s=time.perf_counter() - t0)
+    return kept, removed, (pi, pj, b0, kin)
+
+
+def king_unrelated_set_packed(packed, n_samples, kinship_threshold=KING_DEFAULT_KINSHIP_THRESHOLD, threads=0, timings=None):
+    """`king_unrelated_set_from_packed`, src/math/KING.rs:745-753 -> (kept uint32 ascending, removed uint32 in removal order,
+    edge_count, n_sites).  `threads` is accepted and unused."""
+    n, m, t = _king_check_pairs_args(packed, n_samples, kinship_threshold)
+    kept, removed, pairs = _king_unrelated_set(_panel(_king_payload2d(packed, n), n), t, timings)
+    return kept, removed, int(pairs[0].shape[0]), m
+
+
+def _king_from_bed(prefix, maf_threshold, max_missing_rate, het_threshold, snps_only, kinship_threshold):
+    t = _king_threshold(kinship_threshold)
+    pk, _miss, _maf, _std, _flip, _keep, n, _tot = prepare_bed_2bit_packed(prefix, float(maf_threshold), float(max_missing_rate),
+                                                                           float(het_threshold), snps_only)
+    n, m, t = _king_check_pairs_args(pk, n, t)
+    kept, removed, pairs = _king_unrelated_set(_panel(pk, n), t)
+    return kept, removed, pairs, m, n
+
+
+def king_unrelated_set_from_bed(prefix, maf_threshold=0.01, max_missing_rate=0.1, het_threshold=0.0, snps_only=False,
+                                kinship_threshold=KING_DEFAULT_KINSHIP_THRESHOLD, threads=0):
+    """`king_unrelated_set_from_bed_py`, src/math/KING.rs:794-824: `prepare_bed_2bit_packed`, the related pairs, their graph and
+    the greedy prune -> (kept uint32, removed uint32, edge_count, n_sites).  `threads` is accepted and unused."""
+    kept, removed, pairs, m, _n = _king_from_bed(prefix, maf_threshold, max_missing_rate, het_threshold, snps_only, kinship_threshold)
+    return kept, removed, int(pairs[0].shape[0]), m
+
+
+def king_format_kinship(value):
+    """Kinship as the `.king.kin0` table writes it: the shortest text that reads back to the same f64 (`repr`)."""
+    return repr(float(value))
+
+
+def write_king_tables(out, ids, n_sites, pairs, kept, removed):
+    """`{out}.king.kin0` (TSV `ID1 ID2 NSNP IBS0 KINSHIP`, the related pairs in (i, j) order, NSNP = kept sites),
+    `{out}.king.unrelated.id` (kept samples, ascending) and `{out}.king.related.id` (removed samples in removal order) -> paths."""
+    pi, pj, b0, kin = pairs
+    paths = [f"{out}.king.kin0", f"{out}.king.unrelated.id", f"{out}.king.related.id"]
+    with open(paths[0], "w", encoding="utf-8") as fh:
+        fh.write("ID1\tID2\tNSNP\tIBS0\tKINSHIP\n")
+        fh.writelines(f"{ids[int(a)]}\t{ids[int(b)]}\t{int(n_sites)}\t{int(z)}\t{king_format_kinship(k)}\n"
+                      for a, b, z, k in zip(pi, pj, b0, kin))
+    for path, sel in ((paths[1], kept), (paths[2], removed)):
+        with open(path, "w", encoding="utf-8") as fh:
+            fh.writelines(f"{ids[int(s)]}\n" for s in sel)
+    return paths
