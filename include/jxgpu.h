@@ -406,7 +406,8 @@ int jxg_lmm_loglike_null(const double *d_s, const double *d_xcov, const double *
  * of the symv launches sampled by the most recent jxg_eigh_f64 (one per 64-column panel), which = 3: the mean
  * algorithmic megabytes (lower triangle of the trailing matrix, f64) of those launches; which = 4 / 5: duration (ms) and algorithmic
  * GFLOP of the Q2 back-transformation of the most recent two-stage decomposition, 6 - 9: band reduction, bulge chasing, divide and
- * conquer, Q1 (ms), 10: 1 when the two-stage path ran, 16: apply launches of that Q2, 17: its form (0 three waves per unit, 1 one
+ * conquer, Q1 (ms; 6 includes the Q1 reflector blocks prepared beside the band reduction's last panels, JXGPU_Q1_TAIL_NT, and 9 only
+ * the blocks prepared in line), 10: 1 when the two-stage path ran, 16: apply launches of that Q2, 17: its form (0 three waves per unit, 1 one
  * wave per unit, 2 two sweep groups per pass, 3 balanced five / four units per CU); 18 - 21: the last jx_rrblup_pcg_packed solve --
  * wall ms of its iteration loop, its iterations, the summed HIP-event ms of its two streaming operator kernels (Z'p and Z (Z'p):
  * 2 x n_train x m / 4 payload bytes per application), wall ms of its set-up (images + pre-pass); 22 / 23: summed operator kernel

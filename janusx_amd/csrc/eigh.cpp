@@ -34,7 +34,8 @@ int ormtr_lower(hipStream_t st, const double *d_a, int n, const double *d_tau, d
 size_t sy2sb_work_doubles(int n);
 int sy2sb_bandwidth();
 int sy2sb_lower(hipStream_t st, double *d_a, int n, double *d_tau, double *d_ab, int ldab, double *d_work, int *d_flags,
-                bool allow_shard = false);
+                bool allow_shard = false, int (*panel_hook)(void *user, hipStream_t st, int final_cols, int nt) = nullptr,
+                void *hook_user = nullptr);
 int sy2sb_set_band_dist(int rank, int world, int (*allreduce)(void *, int64_t), void *user, double *staging,
                         int64_t staging_doubles, int min_n, int block);
 int64_t sy2sb_band_staging_doubles(int n);
@@ -47,13 +48,19 @@ int sb2st_chase(hipStream_t st, double *d_ab, int n, double *d_d, double *d_e, d
 size_t sbback_tq_doubles(int n, int ks);
 int sbback_apply_q2(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols,
                     double *d_tq, hipEvent_t ev_start, hipEvent_t ev_stop);
-extern float g_last_ms[24];   // [4] Q2 apply kernel ms, [5] its algorithmic GFLOP, [6] band reduction ms, [7] bulge chasing ms,
-                              // [8] divide and conquer ms, [9] Q1 back-transformation ms, [10] 1 = two-stage path taken
+extern float g_last_ms[24];   // [4] Q2 apply kernel ms, [5] its algorithmic GFLOP, [6] band reduction ms (with the Q1 blocks prepared
+                              // beside its last panels), [7] bulge chasing ms, [8] divide and conquer ms, [9] Q1 back-transformation ms
+                              // (with the blocks prepared in line only), [10] 1 = two-stage path taken
 int ormtr_lower_off(hipStream_t st, const double *d_a, int n, int off, int nref, const double *d_tau, double *d_c, int ncols);
-// the C-independent part of the Q1 back-transformation (V images, Gram, T, V T per block) prepared ahead on a side stream
+// the C-independent part of the Q1 back-transformation (V images, Gram, T, V T per block), prepared block by block
 struct OrmtrPlan;
 OrmtrPlan *ormtr_plan_new();
 void ormtr_plan_free(OrmtrPlan *p);
+size_t ormtr_plan_bytes(int n, int off, int nref);
+int ormtr_plan_begin(OrmtrPlan &plan, int n, int off, int nref);
+int ormtr_plan_blocks(const OrmtrPlan &plan);
+int ormtr_plan_block_end(const OrmtrPlan &plan, int b);
+int ormtr_prepare_block(hipStream_t st, OrmtrPlan &plan, int b, const double *d_a, const double *d_tau, int max_wgs);
 int ormtr_prepare(hipStream_t st, const double *d_a, int n, int off, int nref, const double *d_tau, OrmtrPlan &plan);
 int ormtr_apply(hipStream_t st, const OrmtrPlan &plan, double *d_c, int ncols);
 int sytrd_dist_active(int n);
@@ -77,6 +84,33 @@ constexpr int kRocsolverStedcMaxN = 46340;   // n^2 < 2^31: rocSOLVER 7.2 dstedc
 
 static rocblas_handle g_handle = nullptr;
 static std::mutex g_handle_mu;
+
+// Q1 blocks prepared beside the last panels of the band reduction (panel hook of sy2sb_lower): a block is issued on the preparation
+// stream as soon as the trailing size is at or below nt_max and all of its reflectors are final, ordered behind the main stream by an
+// event recorded here.  The blocks share their temporaries, so they go one behind the other on that one stream.
+struct Q1Tail {
+    OrmtrPlan *plan = nullptr;
+    const double *a = nullptr, *tau = nullptr;
+    int nt_max = 0, max_wgs = 0, next_block = 0;
+    hipStream_t prep = nullptr;
+    hipEvent_t ev_final = nullptr, ev_done = nullptr;
+};
+static int q1_tail_hook(void *user, hipStream_t st, int final_cols, int nt) {
+    Q1Tail &q = *static_cast<Q1Tail *>(user);
+    if (nt > q.nt_max) return 0;
+    bool ordered = false;
+    // the last block ends at the last reflector, which only the last panel delivers: left to the in-line preparation
+    while (q.next_block + 1 < ormtr_plan_blocks(*q.plan) && ormtr_plan_block_end(*q.plan, q.next_block) <= final_cols) {
+        if (!ordered) {
+            JX_HIP(hipEventRecord(q.ev_final, st));
+            JX_HIP(hipStreamWaitEvent(q.prep, q.ev_final, 0));
+            ordered = true;
+        }
+        if (ormtr_prepare_block(q.prep, *q.plan, q.next_block, q.a, q.tau, q.max_wgs)) return 1;
+        ++q.next_block;
+    }
+    return 0;
+}
 
 static rocblas_handle get_handle() {
     std::lock_guard<std::mutex> lk(g_handle_mu);
@@ -252,9 +286,14 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
             return 0;
         };
         // Q1 back-transformation, C-independent part (reflector images, Gram, T^-1, V T of every block: ~40 of its 165 ms at
-        // n = 20 000): prepared in line in front of the Q1 products.  Preparing it on a side stream beside the bulge chasing or the
-        // divide and conquer was measured in round 4 and moved the 40 ms instead of hiding them; removed.
+        // n = 20 000).  A block needs its own reflectors only, and those are final long before the band reduction ends: from a
+        // trailing size of JXGPU_Q1_TAIL_NT (default 8192; 0: everything in line) on, where the serial panel chain leaves most of the
+        // chip idle, the complete blocks are prepared on a stream of their own beside the last panels, in launches of at most 3/4 of
+        // the CUs (JXGPU_Q1_TAIL_WGS) so that the chain's single workgroups always find a free one.  The rest -- at least the last
+        // block -- is prepared in line in front of the Q1 products.  (Beside the bulge chasing or the divide and conquer the CUs are
+        // taken: both placements were measured in round 4 and moved the 40 ms instead of hiding them)
         std::unique_ptr<OrmtrPlan, void (*)(OrmtrPlan *)> q1_plan(nullptr, ormtr_plan_free);
+        Q1Tail q1_tail;
         DevBuf ts_work, ts_ab, ts_tau2, ts_ctrl, ts_flags, ts_tq;
         ScratchLease ts_v2;
         const int ldab = sb2st_ldab(), ks = sb2st_steps(n);
@@ -273,9 +312,48 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
             static const bool force_single = getenv("JXGPU_DIST_EIGH_FORCE") && atoi(getenv("JXGPU_DIST_EIGH_FORCE")) != 0;
             const bool shard_band = (dist_two || force_single) && sy2sb_band_dist_active(n);
             g_last_band_sharded = shard_band ? 1 : 0;
+            // one rank only; read per call (the forms are compared inside one process)
+            const int q1_tail_nt = getenv("JXGPU_Q1_TAIL_NT") ? atoi(getenv("JXGPU_Q1_TAIL_NT")) : 8192;
+            const int q1_nref = n - sy2sb_bandwidth() - 1;
+            if (q1_tail_nt > 0 && !dist_two && !force_single && q1_nref > 0) {
+                // the plan's memory is now held during the band reduction: only where that leaves room for the Q2 workspace
+                size_t fr = 0, tot = 0;
+                const size_t need = ormtr_plan_bytes(n, sy2sb_bandwidth(), q1_nref) + sizeof(double) * sbback_tq_doubles(n, ks);
+                if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > need + ((size_t)8 << 30)) {
+                    static hipStream_t prep = nullptr;
+                    static hipEvent_t ev_prep[2] = {nullptr, nullptr};
+                    static int tail_wgs = 0;
+                    if (!prep) {
+                        JX_HIP(hipEventCreateWithFlags(&ev_prep[0], hipEventDisableTiming));
+                        JX_HIP(hipEventCreateWithFlags(&ev_prep[1], hipEventDisableTiming));
+                        int dev = 0, cus = 0;
+                        JX_HIP(hipGetDevice(&dev));
+                        JX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+                        tail_wgs = getenv("JXGPU_Q1_TAIL_WGS") ? atoi(getenv("JXGPU_Q1_TAIL_WGS")) : cus * 3 / 4;
+                        if (tail_wgs < 16) tail_wgs = 16;
+                        JX_HIP(hipStreamCreateWithFlags(&prep, hipStreamNonBlocking));
+                    }
+                    q1_plan.reset(ormtr_plan_new());
+                    if (ormtr_plan_begin(*q1_plan, n, sy2sb_bandwidth(), q1_nref)) return 1;
+                    q1_tail.plan = q1_plan.get();
+                    q1_tail.a = d_a;
+                    q1_tail.tau = tau.as<double>();
+                    q1_tail.nt_max = q1_tail_nt;
+                    q1_tail.max_wgs = tail_wgs;
+                    q1_tail.prep = prep;
+                    q1_tail.ev_final = ev_prep[0];
+                    q1_tail.ev_done = ev_prep[1];
+                }
+            }
             if (sy2sb_lower(st, d_a, n, tau.as<double>(), ts_ab.as<double>(), ldab, ts_work.as<double>(),
-                            ts_flags.as<int>(), shard_band))
+                            ts_flags.as<int>(), shard_band, q1_tail.plan ? q1_tail_hook : nullptr, &q1_tail))
                 return 1;
+            if (q1_tail.plan && q1_tail.next_block > 0) {
+                // Everything behind the band reduction is ordered behind the blocks prepared beside it: the in-line rest shares their
+                // temporaries and the Q1 products read them -- and the bulge chasing's persistent launch wants the whole chip.
+                JX_HIP(hipEventRecord(q1_tail.ev_done, q1_tail.prep));
+                JX_HIP(hipStreamWaitEvent(st, q1_tail.ev_done, 0));
+            }
             int hf[4] = {0, 0, 0, 0};
             JX_HIP(hipMemcpyAsync(hf, ts_flags.p, sizeof(hf), hipMemcpyDeviceToHost, st));
             {
@@ -291,6 +369,11 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
             if (flagged) {
                 if (trace) (void)stage_done("sy2sb (flagged)");
                 if (trace) fprintf(stderr, "[jxgpu eigh n=%d] band reduction flagged a panel (code %d): one-stage fallback\n", n, hf[0]);
+                // (the blocks prepared so far read reflectors that are now void: let them run out in front of the copy that overwrites
+                // what they read, and drop the plan)
+                if (q1_tail.plan) JX_HIP(hipStreamSynchronize(q1_tail.prep));
+                q1_tail.plan = nullptr;
+                q1_plan.reset();
                 JX_HIP(hipMemcpyAsync(d_a, c.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, st));
                 ts_tq.release();
                 twostage = false;
@@ -311,6 +394,9 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
                 // a sweep's bounded spin on its predecessor expired (the persistent launch assumes its workgroups are
                 // co-resident: a shared device can break that): restore the input from the copy and reduce it in one stage
                 if (trace) fprintf(stderr, "[jxgpu eigh n=%d] bulge chasing gave up waiting for a neighbour sweep: one-stage fallback\n", n);
+                if (q1_tail.plan) JX_HIP(hipStreamSynchronize(q1_tail.prep));
+                q1_tail.plan = nullptr;
+                q1_plan.reset();
                 JX_HIP(hipMemcpyAsync(d_a, c.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, st));
                 ts_tq.release();
                 twostage = false;
@@ -319,7 +405,7 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
                 if (stage_done("sb2st")) return 1;
             }
         }
-        if (twostage) q1_plan.reset(ormtr_plan_new());
+        if (twostage && !q1_plan) q1_plan.reset(ormtr_plan_new());
         if (!twostage) {
             if (sytrd_lower(h, st, d_a, n, d_w, e.as<double>(), tau.as<double>())) return 1;
             if (stage_done("sytrd")) return 1;

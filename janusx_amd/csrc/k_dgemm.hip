@@ -519,6 +519,24 @@ static int dg_reduce(hipStream_t st, const DgemmArgs &g) {
     return 0;
 }
 
+// K split dgemm takes for an m x n x k product called with ksplit <= 0 and a workspace of `ws_doubles` (0: none): a caller that
+// issues the product in row chunks passes it to every chunk, so that the chunks sum over K in the order of the whole call.
+int dgemm_auto_split(int m, int n, int k, size_t ws_doubles) {
+    if (m <= 0 || n <= 0 || k <= 0) return 1;
+    const bool small_n = n <= 64, small_m = m <= 64;
+    const int bm = small_m ? 64 : 128, bn = (small_n || small_m) ? 64 : 128;
+    const int64_t tiles = (int64_t)ceil_div(m, bm) * ceil_div(n, bn);
+    const int ktiles = ceil_div(k, DG_BK);
+    int ksplit = 1;
+    if (tiles < 384) {
+        ksplit = (int)((768 + tiles - 1) / tiles);
+        const int maxsplit = ktiles / 8 > 0 ? ktiles / 8 : 1;    // at least 128 of K per slice
+        if (ksplit > maxsplit) ksplit = maxsplit;
+        if (ksplit < 1) ksplit = 1;
+    }
+    return dg_fit_split(ksplit, m, n, ws_doubles);
+}
+
 // C (m x n) = alpha op(A) op(B) + beta C.  ksplit <= 0: chosen so that the launch fills the chip; a split over K needs
 // `ws` (ksplit m n doubles; the split is reduced to what fits, 1 without a workspace).
 int dgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, double alpha, const double *a, int64_t lda,
@@ -533,17 +551,7 @@ int dgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, double alpha, c
     const bool small_n = n <= 64, small_m = m <= 64;
     const int bm = small_m ? 64 : 128, bn = (small_n || small_m) ? 64 : 128;
     const int tm = ceil_div(m, bm), tn = ceil_div(n, bn);
-    if (ksplit <= 0) {
-        const int64_t tiles = (int64_t)tm * tn;
-        const int ktiles = ceil_div(k, DG_BK);
-        ksplit = 1;
-        if (tiles < 384) {
-            ksplit = (int)((768 + tiles - 1) / tiles);
-            const int maxsplit = ktiles / 8 > 0 ? ktiles / 8 : 1;    // at least 128 of K per slice
-            if (ksplit > maxsplit) ksplit = maxsplit;
-            if (ksplit < 1) ksplit = 1;
-        }
-    }
+    if (ksplit <= 0) ksplit = dgemm_auto_split(m, n, k, ws ? ws_doubles : 0);
     g.ksplit = dg_fit_split(ksplit, m, n, ws ? ws_doubles : 0);
     dim3 grid(tm, tn, g.ksplit);
     int rc;

@@ -18,8 +18,9 @@ int oz_planes_override_get();
 void oz_planes_override_set(int planes);
 size_t oz_image_bytes(int rows, int k, int planes = 0);
 OzImage oz_image_at(void *mem, int rows, int k, int planes = 0);
-// operand element (r, k) = x[r * rs + k * cs], rs == 1 or cs == 1
-int oz_slice(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im);
+// operand element (r, k) = x[r * rs + k * cs], rs == 1 or cs == 1; max_wgs > 0: built in row chunks of launches of at most that many
+// workgroups (same bits)
+int oz_slice(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im, int max_wgs = 0);
 // C (m x n, column-major, ldc) = alpha A B' + beta C from images (a: >= m rows, b: >= n rows, same k).
 // mode 0: all tiles; 1: tiles with column tile >= row tile only; 2: A[r][k] = 0 for k < 128 (r / 128)
 int oz_mm(hipStream_t st, const OzImage &a, const OzImage &b, int m, int n, double alpha, double beta, double *c, int64_t ldc,

@@ -322,17 +322,33 @@ __global__ __launch_bounds__(512, 2) void oz_mm_kernel(OzArgs g) {
     }
 }
 
-template <int P> static int oz_slice_launch(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im) {
+// max_wgs > 0: row blocks [rb0, rb0 + nrbc) only, eight k steps per workgroup whatever that leaves of the chip
+template <int P> static int oz_slice_launch(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im, int max_wgs) {
     int spb = 8;         // k steps per workgroup, fewer when that leaves the chip empty
-    while (spb > 1 && (int64_t)im.nrb * ceil_div(im.nks, spb) < 2048) spb /= 2;
-    dim3 grid((unsigned)ceil_div(im.nks, spb), (unsigned)im.nrb);
-    hipLaunchKernelGGL((oz_slice_kernel<P>), grid, dim3(256), 0, st, x, rs, cs, im.rows, im.k, im.nks, spb, im.scale, im.q);
-    JX_LAUNCH_CHECK();
+    if (max_wgs <= 0) {
+        while (spb > 1 && (int64_t)im.nrb * ceil_div(im.nks, spb) < 2048) spb /= 2;
+        dim3 grid((unsigned)ceil_div(im.nks, spb), (unsigned)im.nrb);
+        hipLaunchKernelGGL((oz_slice_kernel<P>), grid, dim3(256), 0, st, x, rs, cs, im.rows, im.k, im.nks, spb, im.scale, im.q);
+        JX_LAUNCH_CHECK();
+        return 0;
+    }
+    // capped form: the same kernel on sub-images of whole row blocks (a row block's digits and scales are contiguous)
+    while (ceil_div(im.nks, spb) > max_wgs) spb *= 2;
+    const int gx = ceil_div(im.nks, spb), per = std::max(1, max_wgs / gx);
+    for (int rb0 = 0; rb0 < im.nrb; rb0 += per) {
+        const int nrbc = std::min(per, im.nrb - rb0);
+        const int rows = std::min(im.rows - rb0 * OZ_TM, nrbc * OZ_TM);
+        hipLaunchKernelGGL((oz_slice_kernel<P>), dim3((unsigned)gx, (unsigned)nrbc), dim3(256), 0, st, x + (int64_t)rb0 * OZ_TM * rs, rs,
+                           cs, rows, im.k, im.nks, spb, im.scale + (size_t)rb0 * OZ_TM,
+                           im.q + (int64_t)rb0 * im.nks * (P * OZ_PLANE));
+        JX_LAUNCH_CHECK();
+    }
     return 0;
 }
 
-// operand element (r, k) = x[r * rs + k * cs], rs == 1 or cs == 1
-int oz_slice(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im) {
+// operand element (r, k) = x[r * rs + k * cs], rs == 1 or cs == 1.  max_wgs > 0: no launch larger than that many workgroups (the
+// image is built in row chunks; same bits -- the maxima are exact and every digit depends on its own element and row scale only)
+int oz_slice(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzImage &im, int max_wgs) {
     if (im.rows <= 0 || im.k <= 0) return 0;
     if (rs != 1 && cs != 1) return fail("oz_slice: one stride has to be 1");
     if (im.nrb > 65535) return fail("oz_slice: more than 65535 row blocks");
@@ -340,18 +356,32 @@ int oz_slice(hipStream_t st, const double *x, int64_t rs, int64_t cs, const OzIm
     {
         // enough workgroups to fill the chip whatever the operand's shape
         const bool kfast = cs == 1;
-        const int rgroups = kfast ? ceil_div(im.rows, 16) : ceil_div(im.rows, 256);
+        const int rpg = kfast ? 16 : 256;                // rows per row group
+        const int rgroups = ceil_div(im.rows, rpg);
         int kchunk = kfast ? 2048 : 256;
-        while (kchunk > 64 && (int64_t)rgroups * ceil_div(im.k, kchunk) < 2048) kchunk /= 2;
         if (rgroups > 65535) return fail("oz_slice: too many row groups");
-        hipLaunchKernelGGL(oz_rowmax_kernel, dim3((unsigned)ceil_div(im.k, kchunk), (unsigned)rgroups), dim3(256), 0, st, x, rs, cs,
-                           im.rows, im.k, kchunk, reinterpret_cast<unsigned long long *>(im.scale));
-        JX_LAUNCH_CHECK();
+        unsigned long long *const sc = reinterpret_cast<unsigned long long *>(im.scale);
+        if (max_wgs <= 0) {
+            while (kchunk > 64 && (int64_t)rgroups * ceil_div(im.k, kchunk) < 2048) kchunk /= 2;
+            hipLaunchKernelGGL(oz_rowmax_kernel, dim3((unsigned)ceil_div(im.k, kchunk), (unsigned)rgroups), dim3(256), 0, st, x, rs, cs,
+                               im.rows, im.k, kchunk, sc);
+            JX_LAUNCH_CHECK();
+        } else {
+            while (ceil_div(im.k, kchunk) > max_wgs) kchunk *= 2;
+            const int gx = ceil_div(im.k, kchunk), per = std::max(1, max_wgs / gx);
+            for (int g0 = 0; g0 < rgroups; g0 += per) {
+                const int ng = std::min(per, rgroups - g0);
+                const int rows = std::min(im.rows - g0 * rpg, ng * rpg);
+                hipLaunchKernelGGL(oz_rowmax_kernel, dim3((unsigned)gx, (unsigned)ng), dim3(256), 0, st, x + (int64_t)g0 * rpg * rs, rs,
+                                   cs, rows, im.k, kchunk, sc + (size_t)g0 * rpg);
+                JX_LAUNCH_CHECK();
+            }
+        }
     }
     switch (im.planes) {
-        case 4: return oz_slice_launch<4>(st, x, rs, cs, im);
-        case 5: return oz_slice_launch<5>(st, x, rs, cs, im);
-        case 6: return oz_slice_launch<6>(st, x, rs, cs, im);
+        case 4: return oz_slice_launch<4>(st, x, rs, cs, im, max_wgs);
+        case 5: return oz_slice_launch<5>(st, x, rs, cs, im, max_wgs);
+        case 6: return oz_slice_launch<6>(st, x, rs, cs, im, max_wgs);
     }
     return fail("oz_slice: unsupported plane count");
 }

@@ -593,8 +593,14 @@ int sy2sb_band_dist_active(int n) {
 // Look-ahead: the trailing update of panel p is split into the block column of panel p + 1 (a narrow GEMM) and the
 // rest; the factorisation chain of panel p + 1 (~15 small launches, latency-bound) then runs on a side stream beside the
 // rest of the update, which is what fills the chip.  Panel buffers, T and the zero-panel flag alternate by panel parity.
+//
+// panel_hook (optional): called once per panel on the host, after the main stream has waited for that panel's factorisation chain
+// and its rank-2k update is issued, with the number of leading columns whose reflectors (d_a below the band, d_tau) are final in
+// the order of `st` -- every later launch touches the trailing matrix only -- and the trailing size.  The eigensolver uses it to
+// issue work that needs those reflectors alone beside the last panels, where the chain leaves most of the chip idle.
 int sy2sb_lower(hipStream_t st, double *d_a, int n, double *d_tau, double *d_ab, int ldab, double *d_work,
-                int *d_flags, bool allow_shard) {
+                int *d_flags, bool allow_shard, int (*panel_hook)(void *user, hipStream_t st, int final_cols, int nt),
+                void *hook_user) {
     const int ncol = n - SB - 1;                     // columns with entries below the band
     JX_HIP(hipMemsetAsync(d_tau, 0, sizeof(double) * (size_t)n, st));
     JX_HIP(hipMemsetAsync(d_flags, 0, sizeof(int) * 4, st));
@@ -778,6 +784,7 @@ int sy2sb_lower(hipStream_t st, double *d_a, int n, double *d_tau, double *d_ab,
             } else {
                 if (dsyr2k_lower_nt(st, nt, 2 * SB, -1.0, v1, ld, wc, ld, 1.0, a22, ld)) return 1;
             }
+            if (panel_hook && panel_hook(hook_user, st, j0 + pw, nt)) return 1;
         }
     }
     hipLaunchKernelGGL(sb_extract_band_kernel, dim3((unsigned)(((int64_t)n * ldab + 255) / 256)), dim3(256), 0, st, d_a, n,

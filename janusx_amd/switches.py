@@ -66,6 +66,11 @@ SWITCHES = {
     "JXGPU_DIST_BAND_MIN_N": ("knob", "16384", "size from which the band reduction is sharded", "test_sharded_band_reduction_rccl_single_rank"),
     "JXGPU_DIST_BAND_BLOCK": ("test", "auto", "block rows of the sharded band reduction", "test_sharded_band_reduction_rccl_single_rank"),
     "JXGPU_DIST_DC_WINDOW": ("knob", "1", "0: top-level merge replicated", "untested"),
+    "JXGPU_Q1_TAIL_NT": ("knob", "8192", "trailing size of the band reduction from which complete Q1 reflector blocks are prepared beside "
+                         "its last panels (same bits); 0: all of them in line in front of the Q1 products",
+                         "test_q1_blocks_prepared_beside_the_band_reduction_give_the_same_bits"),
+    "JXGPU_Q1_TAIL_WGS": ("knob", "3/4 of the CUs", "largest launch of that preparation in workgroups (the rest of the CUs serve the panel chain)",
+                          "test_q1_blocks_prepared_beside_the_band_reduction_give_the_same_bits (default)"),
     "JXGPU_SYR2K_PIPE_WGS": ("knob", "7/8 of the CUs", "workgroups of the persistent rank-2k update (the rest of the CUs serve the panel chain)",
                              "test_rank_2k_update_forms_give_the_same_bits"),
     "JXGPU_SPLMM_ROUTE": ("knob", "auto", "dense | block | factor: form of K + lambda I of the sparse-GRM routes",
