@@ -313,7 +313,8 @@ int launch_grm_i8_lut(hipStream_t st, const uint8_t *p32, int64_t m_total, const
     const int64_t ntiles = (int64_t)nt128 * (nt128 + 1) / 2;
     if (ntiles > 0x7fffffffLL) return fail("jxg_grm_accumulate: too many tiles");
     const int64_t kc = 131072;
-    const bool big = ntl256 >= 3 * 256;
+    const int tile_env = getenv("JXGPU_GRM_I8_TILE") ? atoi(getenv("JXGPU_GRM_I8_TILE")) : 0;   // 256 / 128 force a tile shape, as in launch_grm_i8
+    const bool big = tile_env ? tile_env >= 256 : ntl256 >= 3 * 256;
     for (int64_t kb = r0; kb < r1; kb += kc) {
         const int64_t ke = std::min(r1, kb + kc);
         if (big)

@@ -20,15 +20,18 @@ SWITCHES = {
                               "test_full_size_c3_properties[0.0-False] (6) / [0.0-True] (5)"),
     "JXGPU_STEDC_OZ_PLANES": ("numerics", "unset (follows JXGPU_OZ_PLANES)", "planes of the divide-and-conquer merges alone", "untested"),
     "JXGPU_GRM_MISS_DIGITS": ("numerics", "3", "2 = the two-digit dense missing-call GRM of rounds 4-5 (beta off by 1e-5..1e-4 end to end)",
-                              "test_end_to_end_two_stage (default); 2 is NOT a product state"),
+                              "test_end_to_end_two_stage (default), test_rows_with_missing_calls[dense2-*] (digit algebra); 2 is NOT a "
+                              "product state"),
     "JXGPU_GRM_MISS": ("numerics", "1", "0: rows with missing calls on the fp16 split kernel (f32 accumulation, like the reference)",
-                       "test_grm_missing_calls_sparse_correction"),
-    "JXGPU_GRM_MISS_MAX": ("numerics", "0.012", "largest missing share for the sparse correction", "test_grm_missing_calls_sparse_correction"),
+                       "test_grm_missing_calls_sparse_correction, test_rows_with_missing_calls[general] (bit for bit)"),
+    "JXGPU_GRM_MISS_MAX": ("numerics", "0.012", "largest missing share for the sparse correction",
+                           "test_grm_missing_calls_sparse_correction, test_rows_with_missing_calls[sparse] (bit for bit)"),
     "JXGPU_GRM_MISS_DENSE_MIN": ("numerics", "0.0015", "missing share from which the dense digit form replaces the sparse correction",
-                                 "test_grm_missing_calls_sparse_correction, scripts/diag_e2e_two_stage.py"),
-    "JXGPU_GRM_MISS_DENSE_ROWS": ("numerics", "16384", "fewest SNPs for the dense digit form", "test_grm_missing_calls_sparse_correction"),
+                                 "test_grm_missing_calls_sparse_correction, test_rows_with_missing_calls[sparse / dense*], scripts/diag_e2e_two_stage.py"),
+    "JXGPU_GRM_MISS_DENSE_ROWS": ("numerics", "16384", "fewest SNPs for the dense digit form",
+                                  "test_grm_missing_calls_sparse_correction, test_rows_with_missing_calls[dense*]"),
     "JXGPU_GRM_FP4": ("form", "0", "1: the count Gram of the 256-tile form on the fp4 matrix pipes from a nibble image (exact like the int8 kernel)",
-                      "test_grm_count_gram_on_the_fp4_pipes"),
+                      "test_grm_count_gram_on_the_fp4_pipes, test_clean_rows[fp4-256] (bit for bit against numpy)"),
     "JXGPU_GRM_I8": ("numerics", "1", "0: exact-integer SNPs on the fp16 single-product kernel (f32 sums instead of exact i32)", "untested"),
     "JXGPU_GRM_EXACT": ("numerics", "1", "0: every SNP on the fp16 hi/lo split kernel", "untested"),
     "JXGPU_ROT_I8": ("numerics", "1", "0: design rows on the fp16 hi/lo rotation instead of the exact int8 planes",
@@ -81,7 +84,8 @@ SWITCHES = {
     "JXGPU_SPECTRAL_CACHE": ("knob", "1", "0: no reuse of the last sparse GRM's decomposition", "untested"),
     # ---- forms (same numbers) -----------------------------------------------------------------------------------------------
     **{k: ("form", "default", "kernel / launch shape of the same computation", t) for k, t in {
-        "JXGPU_BC_OWNED": "test_bulge_chasing_position_owned_equals_sweep_owned", "JXGPU_SB2ST_WGS": "untested", "JXGPU_GRM_I8_TILE": "test_sparse_grm_row_panels_write_the_same_file",
+        "JXGPU_BC_OWNED": "test_bulge_chasing_position_owned_equals_sweep_owned", "JXGPU_SB2ST_WGS": "untested", "JXGPU_GRM_I8_TILE": "test_sparse_grm_row_panels_write_the_same_file, test_clean_rows / test_row_panels / test_rows_with_missing_calls "
+                             "of test_gpu_grm_exact.py (128 and 256, the byte-LUT kernel included, bit for bit against numpy)",
         "JXGPU_GRM_TILE": "untested", "JXGPU_GRM_EXACT_BK": "untested", "JXGPU_ROT256": "untested", "JXGPU_SCAN_NOLDS": "untested",
         "JXGPU_SCAN_NOTILE": "untested", "JXGPU_SBBACK_BAL": "untested", "JXGPU_SBBACK_BAL5": "test_eigh_balanced_q2_forms",
         "JXGPU_SBBACK_BAL_MIN": "untested", "JXGPU_SBBACK_BAL_PER": "untested", "JXGPU_SBBACK_GROUPS": "untested", "JXGPU_SBBACK_NW": "untested",
