@@ -815,6 +815,40 @@ int jxg_king_counts_p32(const uint8_t *d_p32, int64_t m, int n, int i0, int i1, 
 int jx_king_prune(int64_t n, const int64_t *offsets, const uint32_t *neighbors, uint32_t *kept, int64_t *n_kept, uint32_t *removed,
                   int64_t *n_removed);
 
+/* ---- Multi-trait LM scan (`jx gwas -lm -trait-level`; csrc/k_lm_traits.hip; the shared-projection route of
+ * src/stats/lm_trait.rs:481-686): sums = G [Q | R] on the int8 matrix pipes, then the per-(SNP, trait) rule of
+ * `lm_assoc_from_shared_projection` (:303-335).
+ *   jxg_lmt_cpad     : columns of the plane image of an operand of `ncols` columns (the next multiple of 32).
+ *   jxg_lmt_prepare  : d_b = `ncols` f64 columns of n samples, column c at d_b + c ldb -> d_planes (4, cpad, npad) int8 signed radix-128
+ *                      digits (npad = 128 ceil(n / 128); k order inside a 16-sample group as the 2-bit decode produces it, byte 4 q + b
+ *                      = sample 4 b + q; pad samples and pad columns zero), d_sexp (cpad) i32 = e with 2^e the smallest power of two
+ *                      >= max |b_c| (0 for a zero column), d_scale (cpad) f64 = 2^(e - 27), d_colsum (cpad) i64 = the column's integer
+ *                      sum over the samples.  b_c = scale ((q1 128 + q2) 128 + q3) 128 + q4) up to scale / 2: exact for a column whose
+ *                      entries are multiples of 2^(e - 27).  The entries must be finite.  d_rem (optional, laid out as d_b): what the
+ *                      digits leave of every entry, exact in f64; prepared as an operand of its own it adds 28 more bits.
+ *   jxg_lmt_sums_p32 : d_sums[r][c] = sum_i v(r, i) b_c[i] for the rows d_rows[0 .. nrows) (nullptr: 0 .. nrows - 1) of a P32 image,
+ *                      v = [0, mean_r, 1, 2] by 2-bit code, or [2, mean_r, 1, 0] where d_flip[r] != 0 (d_mean f32, d_flip u8, by
+ *                      position in the row list).  Integer plane sums combined in 64 bits, one f64 rounding for the called part, one
+ *                      for the missing-call part and one for their sum: the bits of a (row, column) depend on nothing else in the
+ *                      call.  n < 2^31 / 254.
+ *   jxg_lmt_stats    : per (row r, trait t): gg = d_dsum[r] - sum_k (d_qg[r][k] + d_qg_lo[r][k])^2 (d_qg_lo optional, same layout),
+ *                      gy = d_gy[r][t], df = n - rank - 1 -> beta, se,
+ *                      chisq = n ln(1 + t^2 / df), p (two-sided Student t; 1 for a void row whose beta, se and chisq are NaN).
+ *                      d_out (when given): element [t][r] at d_out + t out_trait_stride + 4 r.  d_count (when given): every (t, r) with
+ *                      p <= pmax takes the next slot of the 64-bit device counter (NOT reset by the call: the caller zeroes it once and
+ *                      several calls append) and, when the slot is < capacity, writes d_hit_trait = trait0 + t, d_hit_row = row0 + r and
+ *                      d_hit_vals (4 f64, the same bits as the dense form); the counter ends at the true total. */
+int jxg_lmt_cpad(int ncols);
+int jxg_lmt_prepare(const double *d_b, int64_t ldb, int n, int ncols, int8_t *d_planes, double *d_scale, int64_t *d_colsum,
+                    int32_t *d_sexp, double *d_rem, void *stream);
+int jxg_lmt_sums_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const float *d_mean,
+                     const uint8_t *d_flip, const int8_t *d_planes, const double *d_scale, const int64_t *d_colsum, int ncols,
+                     double *d_sums, int64_t ld_sums, void *stream);
+int jxg_lmt_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq, int rank, const double *d_gy, int64_t ldg, int ntraits,
+                  const double *d_dsum, int nrows, const double *d_rss0, int n, double *d_out, int64_t out_trait_stride, double pmax, int64_t capacity,
+                  int trait0, int row0, int32_t *d_hit_trait, int32_t *d_hit_row, double *d_hit_vals, uint64_t *d_count,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

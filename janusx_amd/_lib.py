@@ -170,6 +170,10 @@ SIGNATURES = {
     "jxg_king_related_p32": [c_p, c_l, c_i, c_d, c_l, c_p, c_p, c_p, c_p, c_p, c_p],
     "jxg_king_counts_p32": [c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
     "jx_king_prune": [c_l, c_p, c_p, c_p, c_p, c_p, c_p],
+    "jxg_lmt_cpad": [c_i],
+    "jxg_lmt_prepare": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "jxg_lmt_sums_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_l, c_p],
+    "jxg_lmt_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_l, c_d, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

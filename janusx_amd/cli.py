@@ -5,6 +5,8 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
 
   python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-lm | -lm2 COVCOL | -lmm | -lmm2 | -fvlmm) [-k 1|2|GRM.npy] [-c COV.tsv]
                             [-maf 0.02] [-geno 0.05] [-het 1.0] [-o OUT] [-force-model]
+  python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv -n T1 -n T2 ... -lm -trait-level [-trait-pmax P] [-c COV.tsv] [-o OUT]
+                            (many traits in one pass: traits that share a sample mask are scanned together, one table {out}.lm.tsv)
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
@@ -442,6 +444,61 @@ def _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, a
               f"({time.perf_counter() - t1:.2f}s)")
 
 
+def group_traits_by_samples(traits, samples_of):
+    """Traits (column indices, in selection order) grouped by their sample set: -> [(keep_idx, [trait, ...])], the groups in the
+    order of their first trait, the traits of a group in selection order.  `samples_of(trait)` -> int64 FAM positions."""
+    groups, where = [], {}
+    for ti in traits:
+        keep_idx = np.asarray(samples_of(ti), dtype=np.int64)
+        key = keep_idx.tobytes()
+        if key not in where:
+            where[key] = len(groups)
+            groups.append((keep_idx, []))
+        groups[where[key]][1].append(ti)
+    return groups
+
+
+def _run_lm_trait_level(packed_t, n_fam, traits, names, samples_of, design_of, y_of, args, bim, out, pmax):
+    """`jx gwas -lm -trait-level`: the traits grouped by sample mask; per group one panel, one QC pass (-maf, -geno, -het), one
+    design and one multi-trait scan (`janusx._lm_traits_group`; a group of one trait takes the single-trait scan), all into the
+    combined table {out}.lm.tsv with `miss` as the count of missing samples."""
+    from . import janusx as jxrs
+    from . import pipeline as pl
+    from . import stats as st
+    from .tsv import TraitTableWriter, resolve_snp_name, trait_site_prefixes
+    t0 = time.perf_counter()
+    path = f"{out}.lm.tsv"
+    writer = TraitTableWriter(path)
+    done = 0
+    try:
+        for keep_idx, members in group_traits_by_samples(traits, samples_of):
+            n = len(keep_idx)
+            label = ",".join(names[ti] for ti in members[:3]) + ("" if len(members) <= 3 else f",... ({len(members)} traits)")
+            if n < 10:
+                print(f"[{label}] only {n} phenotyped samples, skipped")
+                continue
+            t1 = time.perf_counter()
+            panel = pl.Panel(packed_t, n_fam, keep_idx)
+            counts = panel.counts()
+            keep, af, _miss = st.gwas_scan_row_stats(counts, n, args.maf, args.geno, args.het)
+            rows = np.nonzero(keep)[0]
+            prefixes = trait_site_prefixes([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows],
+                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in rows],
+                                           [bim.a0[j] for j in rows], [bim.a1[j] for j in rows], af[rows],
+                                           counts[rows, 0].astype(np.float32), as_rate=False)
+            y = np.stack([y_of(keep_idx, ti) for ti in members])
+            jxrs._lm_traits_group(writer, panel, rows, np.zeros(len(rows), dtype=bool), af[rows], design_of(keep_idx), y,
+                                  [names[ti] for ti in members], prefixes, pmax)
+            done += len(members)
+            print(f"[{label}] -lm -trait-level: n={n} snps={len(rows)} traits={len(members)} ({time.perf_counter() - t1:.2f}s)")
+            del panel
+    except BaseException:
+        writer.abort()
+        raise
+    lines = writer.close()
+    print(f"-lm -trait-level: {done} traits, {lines} rows -> {path} ({time.perf_counter() - t0:.2f}s)")
+
+
 def cmd_gwas(args):
     import torch
     from . import janusx as jxrs
@@ -468,6 +525,18 @@ def cmd_gwas(args):
         lm2_sel = _parse_lm2_covariate_selector(lm2_flag)
     except ValueError as e:
         raise SystemExit(str(e))
+    trait_level = bool(getattr(args, "trait_level", False))
+    trait_pmax = getattr(args, "trait_pmax", None)
+    if trait_pmax is not None and not trait_level:
+        raise SystemExit("-trait-pmax belongs to -trait-level")
+    if trait_level:
+        # the reference's conditions (python/janusx/assoc/workflow_model_packed.py:5046-5064), before anything is loaded
+        if not getattr(args, "lm", False):
+            raise SystemExit("-trait-level: the LM trait-level route requires -lm (the reference's trait-level -lmm is not built).")
+        if trait_pmax is not None and not (0.0 <= float(trait_pmax) <= 1.0):
+            raise SystemExit("-trait-pmax must be within [0, 1]")
+        if len(_select_traits(_read_table(args.pheno)[1], args.ncol)) <= 1:
+            raise SystemExit("LM trait-level route requires at least 2 traits.")
     rank, world = _dist_setup()
     # the payload goes to HBM in windows (bed.stage_bed_payload: `mmap_window_mb` of the reference's BED routes); nothing
     # below holds a host copy of it
@@ -614,8 +683,8 @@ def cmd_gwas(args):
                     for sid in fam:
                         fh.write(f"{sid}\n")
             print(f"Sparse GRM cutoff={args.splmm}: nnz={nnz} -> {sparse_path} ({time.perf_counter() - t0:.2f}s)")
-    for ti in traits:
-        name = names[ti]
+    def trait_samples(ti):
+        """FAM positions of the samples of trait `ti`: a finite phenotype and, with -c, finite covariates."""
         rows_ok = []
         for j, sid in enumerate(fam):
             i = pos.get(sid)
@@ -624,17 +693,32 @@ def cmd_gwas(args):
             if args.cov and (sid not in cpos or not np.all(np.isfinite(cv[cpos[sid]]))):
                 continue
             rows_ok.append(j)
-        keep_idx = np.array(rows_ok, dtype=np.int64)
+        return np.array(rows_ok, dtype=np.int64)
+
+    def trait_design(keep_idx):
+        x = np.ones((len(keep_idx), 1))
+        if qmat is not None:                    # design = [1 | Q | C] (workflow.py:1545-1560)
+            x = np.concatenate([x, qmat[keep_idx]], axis=1)
+        if args.cov:
+            x = np.concatenate([x, np.array([cv[cpos[fam[j]]] for j in keep_idx])], axis=1)
+        return x
+
+    if trait_level:
+        if lm2_idx is not None or dense_models or args.splmm is not None:
+            print("-trait-level: serves -lm; the other models of this run go trait by trait as without it")
+        if rank == 0:
+            _run_lm_trait_level(packed_t, n_fam, traits, names, trait_samples, trait_design,
+                                lambda keep_idx, ti: np.array([ph[pos[fam[j]], ti] for j in keep_idx]), args, bim, out, trait_pmax)
+        run_lm = False
+    for ti in traits:
+        name = names[ti]
+        keep_idx = trait_samples(ti)
         n = len(keep_idx)
         if n < 10:
             print(f"[{name}] only {n} phenotyped samples, skipped")
             continue
         y = np.array([ph[pos[fam[j]], ti] for j in keep_idx])
-        x = np.ones((n, 1))
-        if qmat is not None:                    # design = [1 | Q | C] (workflow.py:1545-1560)
-            x = np.concatenate([x, qmat[keep_idx]], axis=1)
-        if args.cov:
-            x = np.concatenate([x, np.array([cv[cpos[fam[j]]] for j in keep_idx])], axis=1)
+        x = trait_design(keep_idx)
         if (run_lm or lm2_idx is not None) and rank == 0:
             cov_rows = np.array([cv[cpos[fam[j]]] for j in keep_idx]) if lm2_idx is not None else None
             _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, args, bim, out, name)
@@ -1493,6 +1577,11 @@ def main(argv=None):
     g.add_argument("-n", "--n", dest="ncol", action="append", default=None)
     g.add_argument("-lm", "--lm", action="store_true", default=False,
                    help="plain linear model -> {out}.{trait}.lm.tsv")
+    g.add_argument("-trait-level", "--trait-level", dest="trait_level", action="store_true", default=False,
+                   help="with -lm and two or more traits: traits that share a sample mask are scanned together on the matrix "
+                        "pipes and all land in one table {out}.lm.tsv with a phenotype column")
+    g.add_argument("-trait-pmax", "--trait-pmax", dest="trait_pmax", type=float, default=None, metavar="P",
+                   help="with -trait-level: write only the rows with pwald <= P (an extension; the reference has no such flag)")
     g.add_argument("-lm2", "--lm2", nargs="?", const="__SELF__", default=None, metavar="COVCOL",
                    help="linear model with SNP-by-covariate interaction terms over the selected columns of the merged -c table "
                         "-> {out}.{trait}.lm2.tsv; 0-based selectors like 0, 0:3, :2, 0,3; without columns it runs -lm")

@@ -3346,6 +3346,287 @@ def lm2_stream_bed_to_tsv(prefix, y, x, cov_all, cov_indices, out_tsv, sample_id
 
 
 # ------------------------------------------------------------------------------------------------
+# Multi-trait LM scan (src/stats/lm_trait.rs): many traits against one panel, one combined table
+# ------------------------------------------------------------------------------------------------
+
+def _lm_single_as_trait_stats(stats, n, q0):
+    """(m, 4) beta, se, pwald, plrt of `pipeline.scan_rows_lm` -> (m, 4) beta, se, chisq = n ln(1 + t^2 / df), pwald in the
+    combined table's terms: a row without a finite beta and a finite positive se has chisq NaN and p 1."""
+    st = np.array(stats, dtype=np.float64, copy=True)
+    df = n - q0 - 1
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(st[:, 0]) & np.isfinite(st[:, 1]) & (st[:, 1] > 0.0)
+        t = st[:, 0] / st[:, 1]
+        chisq = np.where(ok, float(n) * np.log(1.0 + t * t / float(df)), np.nan)
+        p = np.where(ok & np.isfinite(st[:, 2]), np.clip(st[:, 2], np.finfo(np.float64).tiny, 1.0), 1.0)
+    return np.stack([st[:, 0], st[:, 1], chisq, p], axis=1)
+
+
+def _lm_traits_group(writer, panel, rows, flip, af, x, y_trait_major, names, prefixes, pmax=None, on_trait=None):
+    """One group of traits that share the samples of `panel`, the design and the rows, appended to the combined table trait by
+    trait: two or more through `pipeline.scan_rows_lm_traits` (in calls of at most 1 GiB of dense results), one alone through
+    `pipeline.scan_rows_lm`.  pmax: only the rows with pwald <= pmax are written.  on_trait(name) after each trait."""
+    from . import pipeline as pl
+    y = _c(y_trait_major, np.float64)
+    T, m, n = int(y.shape[0]), len(rows), panel.n
+    if T == 1:
+        st = _lm_single_as_trait_stats(pl.scan_rows_lm(panel, rows, af, x, y[0], flip=flip).cpu().numpy(), n, int(x.shape[1]))
+        if pmax is None:
+            writer.put(prefixes, st, names[0])
+        else:
+            sel = np.nonzero(st[:, 3] <= float(pmax))[0]
+            writer.put(prefixes, st[sel], names[0], sel)
+        if on_trait is not None:
+            on_trait(names[0])
+        return
+    step = T if pmax is not None else max(1, min(pl.LMT_MAX_TRAIT_BATCH, (1 << 30) // (32 * max(m, 1))))
+    for t0 in range(0, T, step):
+        t1 = min(T, t0 + step)
+        if pmax is None:
+            dense = pl.scan_rows_lm_traits(panel, rows, af, x, y[t0:t1], flip=flip).cpu().numpy()
+            for t in range(t0, t1):
+                writer.put(prefixes, dense[t - t0], names[t])
+                if on_trait is not None:
+                    on_trait(names[t])
+        else:
+            hits = pl.scan_rows_lm_traits(panel, rows, af, x, y[t0:t1], flip=flip, pmax=float(pmax))
+            cut = np.searchsorted(hits.trait, np.arange(t1 - t0 + 1))
+            for t in range(t0, t1):
+                a, b = int(cut[t - t0]), int(cut[t - t0 + 1])
+                writer.put(prefixes, hits.stats[a:b], names[t], hits.row[a:b])
+                if on_trait is not None:
+                    on_trait(names[t])
+
+
+def _lmt_rows_check(label, ri, fl, mi, mf, n_snps):
+    if not (fl.shape[0] == mi.shape[0] == mf.shape[0] == ri.shape[0]):
+        raise ValueError(f"{label}prepared row metadata length mismatch: row_indices={ri.shape[0]}, row_flip={fl.shape[0]}, "
+                         f"row_missing={mi.shape[0]}, row_maf={mf.shape[0]}")
+    if ri.size and (ri.min() < 0 or ri.max() >= n_snps):
+        bad = int(ri[(ri < 0) | (ri >= n_snps)][0])
+        raise ValueError(f"{label}row index {bad} out of range for n_snps={n_snps}")
+    if ri.size > 1 and np.any(np.diff(ri) < 0):
+        raise ValueError(f"{label}prepared row_indices must be sorted in ascending BED order")
+
+
+def _lmt_same(a, b):
+    """The sharing test of `jobs_support_shared_fast_path` (lm_trait.rs:192-224, without its host-memory cap): design, samples,
+    rows, flips, and the bits of row_missing and row_maf."""
+    return (a["x"].shape == b["x"].shape and np.array_equal(a["x"].view(np.int64), b["x"].view(np.int64))
+            and np.array_equal(a["sidx"], b["sidx"]) and np.array_equal(a["ri"], b["ri"]) and np.array_equal(a["fl"], b["fl"])
+            and np.array_equal(a["mi"].view(np.int32), b["mi"].view(np.int32))
+            and np.array_equal(a["mf"].view(np.int32), b["mf"].view(np.int32)))
+
+
+def _lmt_run(bed_prefix, n_fam, jobs, out_tsv, progress_callback, mmap_window_mb, pmax):
+    """Jobs (validated) -> the combined table.  Consecutive jobs that pass `_lmt_same` form a group; a group of one goes
+    through the single-trait scan."""
+    from . import bed as _bed
+    from .tsv import TraitTableWriter, resolve_snp_name, trait_site_prefixes
+    t_start = time.perf_counter()
+    pk, _n_full, bim = _bed.stage_bed_payload(bed_prefix, mmap_window_mb)
+    groups = []
+    for job in jobs:
+        if groups and _lmt_same(groups[-1][0], job):
+            groups[-1].append(job)
+        else:
+            groups.append([job])
+    out, total = [], len(jobs)
+    writer = TraitTableWriter(out_tsv)
+    try:
+        panel, panel_key = None, None
+        for grp in groups:
+            j0 = grp[0]
+            if panel_key is None or not np.array_equal(panel_key, j0["sidx"]):
+                panel = None                         # one image at a time
+                panel, panel_key = _panel(pk, n_fam, j0["sidx"]), j0["sidx"]
+            rows = j0["ri"]
+            sel = [int(j) for j in rows]
+            prefixes = trait_site_prefixes([bim.chrom[j] for j in sel], [bim.pos[j] for j in sel],
+                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in sel],
+                                           [bim.a0[j] for j in sel], [bim.a1[j] for j in sel], j0["mf"], j0["mi"])
+            order = iter(grp)
+
+            def on_trait(_name):
+                job = next(order)
+                out.append((job["name"], job["n_idv"], len(rows), len(rows), time.perf_counter() - t_start))
+                if progress_callback is not None:
+                    progress_callback(len(out), total, job["name"])
+
+            _lm_traits_group(writer, panel, rows, j0["fl"], j0["mf"], j0["x"], np.stack([j["y"] for j in grp]),
+                             [j["name"] for j in grp], prefixes, pmax, on_trait)
+    except BaseException:
+        writer.abort()
+        raise
+    writer.close()
+    return out
+
+
+def _lmt_head_checks(chunk_size, mmap_window_mb):
+    if int(chunk_size) <= 0:
+        raise ValueError("chunk_size must be > 0")
+    if mmap_window_mb is not None and int(mmap_window_mb) <= 0:
+        raise ValueError("mmap_window_mb must be > 0")
+
+
+def _lmt_fam(prefix):
+    from . import bed as _bed
+    bed_prefix = _bed_prefix(prefix)
+    try:
+        fam = _bed.read_fam_ids(bed_prefix)
+    except OSError as e:
+        raise ValueError(str(e))
+    if not fam:
+        raise ValueError("no samples in PLINK FAM")
+    return bed_prefix, fam
+
+
+def _lmt_n_snps(bed_prefix):
+    with open(f"{bed_prefix}.bim") as fh:
+        return sum(1 for ln in fh if len(ln.split()) >= 6)
+
+
+def lm_trait_assoc_bed_matrix_to_tsv(prefix, trait_names, y_trait_major, x, sample_indices, row_indices, row_flip, row_missing,
+                                     row_maf, out_tsv, chunk_size=10000, threads=0, progress_callback=None, mmap_window_mb=None,
+                                     pmax=None):
+    """`lm_trait_assoc_bed_matrix_to_tsv`, src/stats/lm_trait.rs:909-1054: T traits (`y_trait_major` (T, n)) that share the
+    samples `sample_indices` (positions in the FAM), the design `x` (n, q0, intercept included) and the prepared rows, scanned
+    with the plain LM and written as one combined table (`tsv.HEADER_TRAITS`: all rows of trait 1, then trait 2, ...) ->
+    [(name, n_idv, kept_rows, scanned_rows, elapsed_s)].  Every argument error is a ValueError raised before the payload is read.
+    `progress_callback(done_traits, total_traits, name)`.  `chunk_size` / `threads` are accepted for signature parity.
+    Extension: `pmax` writes only the rows with pwald <= pmax."""
+    _lmt_head_checks(chunk_size, mmap_window_mb)
+    names = [str(v) for v in trait_names]
+    if not names:
+        return []
+    if any(not v.strip() for v in names):
+        raise ValueError("trait_names must not contain empty values")
+    y = _c(y_trait_major, np.float64)
+    xx = _c(x, np.float64)
+    if y.ndim != 2:
+        raise ValueError("y_trait_major must be a 2D float64 array")
+    if xx.ndim != 2:
+        raise ValueError("x must be a 2D float64 array")
+    sidx = _c(sample_indices, np.int64).ravel()
+    ri = _c(row_indices, np.int64).ravel()
+    fl = np.asarray(row_flip).astype(bool).ravel()
+    mi = _c(row_missing, np.float32).ravel()
+    mf = _c(row_maf, np.float32).ravel()
+    if y.shape[0] != len(names):
+        raise ValueError(f"y_trait_major rows ({y.shape[0]}) must equal len(trait_names) ({len(names)})")
+    if xx.shape[1] == 0:
+        raise ValueError("x must have at least one column")
+    if xx.shape[0] != y.shape[1]:
+        raise ValueError(f"x rows ({xx.shape[0]}) must equal y_trait_major cols ({y.shape[1]})")
+    if sidx.shape[0] != y.shape[1]:
+        raise ValueError(f"sample_indices length ({sidx.shape[0]}) must equal y_trait_major cols ({y.shape[1]})")
+    if not (fl.shape[0] == mi.shape[0] == mf.shape[0] == ri.shape[0]):
+        _lmt_rows_check("", ri, fl, mi, mf, 0)
+    bed_prefix, fam = _lmt_fam(prefix)
+    bad = sidx[(sidx < 0) | (sidx >= len(fam))]
+    if bad.size:
+        raise ValueError(f"sample index {int(bad[0])} out of range for n_samples={len(fam)}")
+    _lmt_rows_check("", ri, fl, mi, mf, _lmt_n_snps(bed_prefix))
+    jobs = [dict(name=names[t], n_idv=int(y.shape[1]), y=y[t], x=xx, sidx=sidx, ri=ri, fl=fl, mi=mi, mf=mf)
+            for t in range(len(names))]
+    return _lmt_run(bed_prefix, len(fam), jobs, out_tsv, progress_callback, mmap_window_mb, pmax)
+
+
+def lm_trait_assoc_bed_to_tsv(prefix, trait_specs, out_tsv, chunk_size=10000, threads=0, progress_callback=None,
+                              mmap_window_mb=None, pmax=None):
+    """`lm_trait_assoc_bed_to_tsv`, src/stats/lm_trait.rs:1057-1290: one dict per trait with the keys trait_name, y, x,
+    sample_indices | sample_ids, row_indices, row_flip, row_missing, row_maf and optionally n_idv.  Consecutive specs with the
+    same samples, design and rows (`jobs_support_shared_fast_path`) are scanned together on the matrix pipes; the others go
+    trait by trait through the single-trait LM scan into the same combined table.  Returns and raises as
+    `lm_trait_assoc_bed_matrix_to_tsv`."""
+    _lmt_head_checks(chunk_size, mmap_window_mb)
+    if not isinstance(trait_specs, list):
+        raise ValueError("trait_specs must be a list of per-trait dict objects")
+    if not trait_specs:
+        return []
+    bed_prefix, fam = _lmt_fam(prefix)
+    fam_index, n_snps, jobs = None, None, []
+    for k, spec in enumerate(trait_specs):
+        if not isinstance(spec, dict):
+            raise ValueError(f"trait_specs[{k}] must be a dict with trait_name/y/x/(sample_indices|sample_ids)/row_* keys")
+
+        def req(key):
+            if key not in spec or spec[key] is None:
+                raise ValueError(f"missing required key '{key}'")
+            return spec[key]
+
+        name = str(req("trait_name"))
+        if not name.strip():
+            raise ValueError(f"trait_specs[{k}].trait_name must not be empty")
+        y = _c(req("y"), np.float64)
+        if y.ndim != 1:
+            raise ValueError(f"trait_specs[{k}].y must be a 1D float64 array")
+        xx = _c(req("x"), np.float64)
+        if xx.ndim != 2:
+            raise ValueError(f"trait_specs[{k}].x must be a 2D float64 array")
+        if xx.shape[1] == 0:
+            raise ValueError(f"trait_specs[{k}].x must have at least one column")
+        if xx.shape[0] != y.shape[0]:
+            raise ValueError(f"trait_specs[{k}] x rows ({xx.shape[0]}) must equal len(y) ({y.shape[0]})")
+        if spec.get("sample_indices") is not None:
+            sidx = _c(spec["sample_indices"], np.int64).ravel()
+            if sidx.shape[0] != y.shape[0]:
+                raise ValueError(f"trait_specs[{k}] sample_indices length ({sidx.shape[0]}) must equal len(y) ({y.shape[0]})")
+            bad = sidx[(sidx < 0) | (sidx >= len(fam))]
+            if bad.size:
+                raise ValueError(f"trait_specs[{k}] sample index {int(bad[0])} out of range for n_samples={len(fam)}")
+        else:
+            sample_ids = [str(v) for v in req("sample_ids")]
+            if len(sample_ids) != y.shape[0]:
+                raise ValueError(f"trait_specs[{k}] sample_ids length ({len(sample_ids)}) must equal len(y) ({y.shape[0]})")
+            if fam_index is None:
+                fam_index = {sid: i for i, sid in enumerate(fam)}
+            for sid in sample_ids:
+                if sid not in fam_index:
+                    raise ValueError(f"trait_specs[{k}] sample ID '{sid}' not found in BED/FAM")
+            sidx = np.array([fam_index[sid] for sid in sample_ids], dtype=np.int64)
+        ri = _c(req("row_indices"), np.int64).ravel()
+        fl = np.asarray(req("row_flip")).astype(bool).ravel()
+        mi = _c(req("row_missing"), np.float32).ravel()
+        mf = _c(req("row_maf"), np.float32).ravel()
+        if n_snps is None:
+            n_snps = _lmt_n_snps(bed_prefix)
+        _lmt_rows_check(f"trait_specs[{k}] ", ri, fl, mi, mf, n_snps)
+        n_idv = int(spec["n_idv"]) if spec.get("n_idv") is not None else int(y.shape[0])
+        jobs.append(dict(name=name, n_idv=n_idv, y=y, x=xx, sidx=sidx, ri=ri, fl=fl, mi=mi, mf=mf))
+    return _lmt_run(bed_prefix, len(fam), jobs, out_tsv, progress_callback, mmap_window_mb, pmax)
+
+
+def lm_trait_assoc_packed(packed, n_samples, y_trait_major, x, row_flip, row_maf, sample_indices=None, row_indices=None,
+                          pmax=None):
+    """Extension (the reference scans files only): the multi-trait LM scan of a packed payload in memory.  `y_trait_major`
+    (T, n), `x` (n, q0) with the intercept, `row_flip` / `row_maf` per scanned row (the rows `row_indices` of the payload, or all).
+    -> (T, m, 4) f64 beta, se, chisq, pwald; with `pmax` the arrays (trait int32, row int32, stats (k, 4)) of the pairs with
+    pwald <= pmax, ordered by (trait, row), row = position in `row_indices`."""
+    from . import pipeline as pl
+    if int(n_samples) <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    y = _c(y_trait_major, np.float64)
+    xx = _c(x, np.float64)
+    if y.ndim != 2 or xx.ndim != 2 or xx.shape[0] != y.shape[1]:
+        raise RuntimeError("y_trait_major must be (T, n) and x (n, q0)")
+    idx, n_sel = _opt_idx(sample_indices)
+    if (n_sel if idx is not None else int(n_samples)) != y.shape[1]:
+        raise RuntimeError(f"sample_indices length mismatch: got {n_sel if idx is not None else int(n_samples)}, "
+                           f"expected y_trait_major cols={y.shape[1]}")
+    panel = _panel(packed, n_samples, idx)
+    rows = np.arange(panel.m, dtype=np.int64) if row_indices is None else _c(row_indices, np.int64).ravel()
+    if rows.size and (rows.min() < 0 or rows.max() >= panel.m):
+        raise RuntimeError(f"row_indices out of range for n_snps={panel.m}")
+    fl = np.asarray(row_flip).astype(bool).ravel()
+    mf = _c(row_maf, np.float32).ravel()
+    if fl.shape[0] != len(rows) or mf.shape[0] != len(rows):
+        raise RuntimeError(f"row_flip / row_maf length mismatch: got {fl.shape[0]} / {mf.shape[0]}, expected {len(rows)}")
+    res = pl.scan_rows_lm_traits(panel, rows, mf, xx, y, flip=fl, pmax=pmax)
+    return res.cpu().numpy() if pmax is None else (res.trait, res.row, res.stats)
+
+
+# ------------------------------------------------------------------------------------------------
 # Genotype rows as numbers and the two matrix-free products the reference's Python layer asks for beside the path
 # (src/stats/packed.rs:577-760, 2060-2560): decode of selected rows, M'alpha, cross-GRM times alpha
 # ------------------------------------------------------------------------------------------------

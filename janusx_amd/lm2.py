@@ -15,14 +15,12 @@ from .tsv import MIN_POSITIVE
 LM2_MAX_INTERACTIONS = 8
 
 
-def qr_projection(x: np.ndarray, y: np.ndarray):
-    """Twice-reorthogonalised modified Gram-Schmidt basis of the columns of x (n, q_base): a column of zero norm, or whose
-    residual norm^2 is <= 1e-12 max(|col|^2, 1), is dropped.  -> (Q (n, q_rank), r_y (n), rss0)."""
+def qr_basis(x: np.ndarray):
+    """Twice-reorthogonalised modified Gram-Schmidt basis of the columns of x (n, q_base) (`LmQrProjection::from_design`,
+    src/stats/glm.rs:243-355): a column of zero norm, or whose residual norm^2 is <= 1e-12 max(|col|^2, 1), is dropped.
+    -> Q (n, q_rank)."""
     x = np.ascontiguousarray(x, dtype=np.float64)
-    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
     n, q0 = x.shape
-    if y.shape[0] != n:
-        raise RuntimeError("y length mismatch")
     if n == 0:
         raise RuntimeError("empty LM design")
     if q0 == 0:
@@ -47,7 +45,18 @@ def qr_projection(x: np.ndarray, y: np.ndarray):
     rank = len(cols)
     if n <= rank + 1:
         raise RuntimeError(f"n too small: require n > rank(X)+1, got n={n}, rank={rank}")
-    q = np.ascontiguousarray(np.stack(cols, axis=1)) if rank else np.zeros((n, 0))
+    return np.ascontiguousarray(np.stack(cols, axis=1)) if rank else np.zeros((n, 0))
+
+
+def qr_projection(x: np.ndarray, y: np.ndarray):
+    """Twice-reorthogonalised modified Gram-Schmidt basis of the columns of x (n, q_base): a column of zero norm, or whose
+    residual norm^2 is <= 1e-12 max(|col|^2, 1), is dropped.  -> (Q (n, q_rank), r_y (n), rss0)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64).ravel()
+    n = x.shape[0]
+    if y.shape[0] != n:
+        raise RuntimeError("y length mismatch")
+    q = qr_basis(x)
     r_y = y - q @ (q.T @ y)
     if not np.all(np.isfinite(r_y)):
         raise RuntimeError("LM QR residualization produced non-finite values")

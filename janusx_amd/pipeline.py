@@ -1047,6 +1047,163 @@ def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, 
     return out
 
 
+LMT_MAX_TRAIT_BATCH = 1024        # `resolve_trait_batch_size`, src/stats/lm_trait.rs:288-300
+LMT_SCRATCH_BYTES = 256 << 20     # the sums of one row block: rows per block = this / (8 (rank + trait batch))
+LMT_HIT_CAPACITY = 1 << 20        # slots of the first hit buffer
+LmTraitHits = namedtuple("LmTraitHits", "trait row stats")
+
+
+class _LmtOperand:
+    """Digit planes of f64 columns (`jxg_lmt_prepare`): `cols` is (C, n), one column per row, a host array or a contiguous f64
+    device tensor.  keep_rem: `rem` (C, n) on the device = what the four digits leave of every entry."""
+
+    def __init__(self, cols, n: int, npad: int, dev, keep_rem=False):
+        self.ncols = int(cols.shape[0])
+        cpad = lib().jxg_lmt_cpad(self.ncols)
+        b = cols if torch.is_tensor(cols) else torch.from_numpy(np.ascontiguousarray(cols, dtype=np.float64)).to(dev)
+        self.rem = torch.empty((self.ncols, n), dtype=torch.float64, device=dev) if keep_rem else None
+        self.planes = torch.empty((4, cpad, npad), dtype=torch.int8, device=dev)
+        self.scale = torch.empty(cpad, dtype=torch.float64, device=dev)
+        self.colsum = torch.empty(cpad, dtype=torch.int64, device=dev)
+        self.sexp = torch.empty(cpad, dtype=torch.int32, device=dev)
+        check(lib().jxg_lmt_prepare(_ptr(b), n, n, self.ncols, _ptr(self.planes), _ptr(self.scale), _ptr(self.colsum),
+                                    _ptr(self.sexp), _ptr(self.rem), _stream()))
+
+
+def lm_traits_row_d(counts: np.ndarray, n: int, mean_g: np.ndarray, flip: np.ndarray) -> np.ndarray:
+    """sum_i v^2 of the mean-imputed additive rows from their (missing, het, hom_alt) counts: n_1 + 4 n_2 + n_miss mean^2 with the
+    f32 mean squared in f64 (n_2 = the homozygotes of the other allele where the row is flipped)."""
+    c = np.asarray(counts, dtype=np.int64)
+    miss, het, hom = c[:, 0], c[:, 1], c[:, 2]
+    two = np.where(flip, n - miss - het - hom, hom)
+    m64 = np.asarray(mean_g, dtype=np.float32).astype(np.float64)
+    return (het + 4 * two).astype(np.float64) + miss.astype(np.float64) * (m64 * m64)
+
+
+def scan_rows_lm_traits(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, Y: np.ndarray, flip=None, pmax=None,
+                        trait_batch=None, hit_capacity=None, progress=None, block_rows=None):
+    """Multi-trait LM scan of the given SNP rows of a resident panel: the shared-projection route of the reference
+    (`lm_trait_assoc_bed_to_tsv_shared_fast`, src/stats/lm_trait.rs:481-686) for traits that share the samples, the design `x`
+    (n, q0, intercept included) and the rows.  `Y` is TRAIT-MAJOR, (T, n) like the reference's `y_trait_major`; every value must be
+    finite (masks are the caller's job).  Host: the f64 Gram-Schmidt basis Q of `x` (`lm2.qr_basis`), R = Y - Q Q'Y and rss0 per
+    trait; device: the digit planes of [Q | R] (`jxg_lmt_prepare`; Q twice: its digits and what they leave), per row block G Q
+    once and G R per batch of at most `trait_batch` (<= 1024) traits (`jxg_lmt_sums_p32`), and the statistics
+    (`jxg_lmt_stats`).  Rows decode as in `scan_rows_lm`:
+    [0, mean, 1, 2] with mean = clip(2 af, 0, 2) in f32, or [2, mean, 1, 0] where `flip`.
+    pmax None -> a (T, len(rows), 4) f64 device tensor [beta, se, chisq, p].
+    pmax = P  -> LmTraitHits(trait int32, row int32 (position in `rows`), stats (k, 4) f64) of every (trait, row) with p <= P,
+    sorted by (trait, row); `hit_capacity` sizes the first device buffer, a block whose hits do not fit is run again into a larger
+    one.  `progress(done_rows, total_rows)` after every row block."""
+    from . import lm2
+    dev, n = panel.device, panel.n
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise RuntimeError("Y must be trait-major with shape (n_traits, n_samples)")
+    T = int(Y.shape[0])
+    if Y.shape[1] != n or x.ndim != 2 or x.shape[0] != n:
+        raise RuntimeError(f"selected sample count {n} != trait length {Y.shape[1]} / design rows {x.shape[0]}")
+    if T == 0:
+        raise RuntimeError("no traits given")
+    bad = np.nonzero(~np.all(np.isfinite(Y), axis=1))[0]
+    if bad.size:
+        raise RuntimeError(f"trait {int(bad[0])} contains non-finite values")
+    if pmax is not None and not (float(pmax) == float(pmax)):
+        raise RuntimeError("pmax must not be NaN")
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    mk = len(rows)
+    if mk and (rows.min() < 0 or rows.max() >= panel.m):
+        raise RuntimeError("row index out of range")
+    tb = LMT_MAX_TRAIT_BATCH if trait_batch is None else int(trait_batch)
+    if tb < 1:
+        raise RuntimeError("trait_batch must be >= 1")
+    tb = min(tb, LMT_MAX_TRAIT_BATCH, T)
+    q = lm2.qr_basis(x)
+    rank = int(q.shape[1])
+    qty = q.T @ Y.T                                        # (rank, T)
+    R = Y - (q @ qty).T
+    if not np.all(np.isfinite(R)):
+        raise RuntimeError("LM QR residualization produced non-finite values")
+    rss0 = np.einsum("tn,tn->t", R, R)
+    hits = pmax is not None
+    if mk == 0:
+        if hits:
+            return LmTraitHits(np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 4)))
+        return torch.empty((T, 0, 4), dtype=torch.float64, device=dev)
+
+    mean_g = np.clip(np.float32(2.0) * np.asarray(af, dtype=np.float32), np.float32(0.0), np.float32(2.0))
+    fl = np.zeros(mk, dtype=bool) if flip is None else np.asarray(flip, dtype=bool)
+    if len(mean_g) != mk or len(fl) != mk:
+        raise RuntimeError("af / flip length != number of rows")
+    d_row = lm_traits_row_d(panel.counts()[rows], n, mean_g, fl)
+    rows_t = torch.from_numpy(rows).to(dev)
+    mean_t = torch.from_numpy(np.ascontiguousarray(mean_g)).to(dev)
+    flip_t = torch.from_numpy(fl.astype(np.uint8)).to(dev)
+    d_t = torch.from_numpy(d_row).to(dev)
+    rss0_t = torch.from_numpy(np.ascontiguousarray(rss0)).to(dev)
+    # Q takes eight digits, as two operands: gg = d - sum qg^2 meets an absolute threshold and needs qg to f64 accuracy
+    op_q = _LmtOperand(q.T, n, panel.npad, dev, keep_rem=True) if rank else None
+    op_q_lo = _LmtOperand(op_q.rem, n, panel.npad, dev) if rank else None
+    op_r = [_LmtOperand(R[t0:t0 + tb], n, panel.npad, dev) for t0 in range(0, T, tb)]
+
+    # rows per block: a fixed scratch budget (whole row tiles), or what the caller asks for
+    br = int(block_rows) if block_rows else max(128, min(LMT_SCRATCH_BYTES // (8 * (rank + tb)), 1 << 22) // 128 * 128)
+    br = max(1, min(br, mk))
+    qg = torch.empty((br, max(rank, 1)), dtype=torch.float64, device=dev)
+    qg_lo = torch.empty_like(qg)
+    gy = torch.empty((br, tb), dtype=torch.float64, device=dev)
+    out = None if hits else torch.empty((T, mk, 4), dtype=torch.float64, device=dev)
+    if hits:
+        cap = max(1, int(hit_capacity) if hit_capacity is not None else min(mk * T, LMT_HIT_CAPACITY))
+        h_t = torch.empty(cap, dtype=torch.int32, device=dev)
+        h_r = torch.empty(cap, dtype=torch.int32, device=dev)
+        h_v = torch.empty((cap, 4), dtype=torch.float64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        total = 0
+
+    def sums(op, dst, r0, nr):
+        check(lib().jxg_lmt_sums_p32(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr, mean_t[r0:].data_ptr(),
+                                     flip_t[r0:].data_ptr(), _ptr(op.planes), _ptr(op.scale), _ptr(op.colsum), op.ncols,
+                                     _ptr(dst), dst.shape[1], _stream()))
+
+    def stats(r0, nr, t0, nt):
+        check(lib().jxg_lmt_stats(_ptr(qg), _ptr(qg_lo) if rank else None, qg.shape[1], rank, _ptr(gy), gy.shape[1], nt,
+                                  d_t[r0:].data_ptr(), nr, rss0_t[t0:].data_ptr(), n, None if hits else out[t0:, r0:].data_ptr(), mk * 4,
+                                  float(pmax) if hits else 0.0, cap if hits else 0, t0, r0, _ptr(h_t) if hits else None,
+                                  _ptr(h_r) if hits else None, _ptr(h_v) if hits else None, _ptr(count) if hits else None,
+                                  _stream()))
+
+    for r0 in range(0, mk, br):
+        nr = min(br, mk - r0)
+        if rank:
+            sums(op_q, qg, r0, nr)
+            sums(op_q_lo, qg_lo, r0, nr)
+        for bi, t0 in enumerate(range(0, T, tb)):
+            nt = min(tb, T - t0)
+            sums(op_r[bi], gy, r0, nr)
+            stats(r0, nr, t0, nt)
+            if hits:
+                seen = int(count.item())
+                if seen > cap:                      # this block's hits did not fit: a larger buffer, the block's statistics again
+                    cap = max(seen, 2 * cap)
+                    grown = (torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                             torch.empty((cap, 4), dtype=torch.float64, device=dev))
+                    for dst, src in zip(grown, (h_t, h_r, h_v)):
+                        dst[:total] = src[:total]
+                    h_t, h_r, h_v = grown
+                    count.fill_(total)
+                    stats(r0, nr, t0, nt)
+                    seen = int(count.item())
+                total = seen
+        if progress is not None:
+            progress(r0 + nr, mk)
+    if not hits:
+        return out
+    ht, hr, hv = h_t[:total].cpu().numpy(), h_r[:total].cpu().numpy(), h_v[:total].cpu().numpy()
+    order = np.lexsort((hr, ht))
+    return LmTraitHits(np.ascontiguousarray(ht[order]), np.ascontiguousarray(hr[order]), np.ascontiguousarray(hv[order]))
+
+
 def scan_rows_lm2(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, cov_sel: np.ndarray, y: np.ndarray, flip=None,
                   block_rows=LM_BLOCK_ROWS, progress=None, progress_every=0):
     """SNP-by-covariate interaction scan of the given SNP rows of a resident panel (`lm2_fit_single_snp`, src/stats/glm2.rs:

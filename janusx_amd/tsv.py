@@ -254,3 +254,115 @@ def write_lm2_tsv(path, chrom, pos, snp, a0, a1, af, miss_counts, stats, cov_ind
         fh.write("".join(buf))
     os.replace(tmp, path)
     return int(stats.shape[0])
+
+
+# ---- combined multi-trait LM table (src/stats/lm_trait.rs:226-286, 645-654) ----------------------------------------------
+
+HEADER_TRAITS = "chrom\tpos\tsnp\tallele0\tallele1\taf\tmiss\tbeta\tse\tchisq\tpwald\tphenotype\n"
+
+
+def row_missing_is_rate(row_missing) -> bool:
+    """`infer_row_missing_mode` (lm_trait.rs:226-235): rates when every value is finite and within [-1e-6, 1 + 1e-6] in f32,
+    counts otherwise."""
+    import numpy as np
+    mi = np.asarray(row_missing, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        return bool(np.all(np.isfinite(mi) & (mi >= np.float32(-1.0e-6)) & (mi <= np.float32(1.0) + np.float32(1.0e-6))))
+
+
+def _round_i64(v: float) -> int:
+    """Rust `f32::round() as i64`: halves away from zero, NaN -> 0, saturating."""
+    if v != v:
+        return 0
+    if not math.isfinite(v):
+        return 2 ** 63 - 1 if v > 0 else -2 ** 63
+    return max(min(int(math.copysign(math.floor(abs(v) + 0.5), v)), 2 ** 63 - 1), -2 ** 63)
+
+
+def trait_site_prefixes(chrom, pos, snp, a0, a1, af, row_missing, as_rate=None):
+    """`build_site_prefixes` (lm_trait.rs:237-286): `chrom pos snp a0 a1 af miss` and a trailing tab per row; af `{:.4}`, miss
+    `{:.4}` as a rate or `round() as i64` as a count (as_rate None: `row_missing_is_rate`)."""
+    import numpy as np
+    mi = np.asarray(row_missing, dtype=np.float32)
+    if as_rate is None:
+        as_rate = row_missing_is_rate(mi)
+    out = []
+    for i in range(len(chrom)):
+        if as_rate:
+            ms = fmt_f4(float(mi[i]))
+        else:
+            ms = str(_round_i64(float(mi[i])))
+        out.append(f"{chrom[i]}\t{pos[i]}\t{snp[i]}\t{a0[i]}\t{a1[i]}\t{fmt_f4(float(np.float32(af[i])))}\t{ms}\t")
+    return out
+
+
+def format_trait_rows(prefixes, stats, name, rows=None) -> str:
+    """The lines of one trait: `prefix beta se chisq pwald phenotype`, beta / se `{:.4}`, chisq `format_chisq_value`, pwald
+    `{:.4e}`.  stats (k, 4) f64; rows: the k positions into `prefixes` (default: all, in order)."""
+    buf = []
+    for i in range(len(stats)):
+        b, s, c, p = (float(v) for v in stats[i])
+        buf.append(f"{prefixes[i if rows is None else rows[i]]}{fmt_f4(b)}\t{fmt_f4(s)}\t{fmt_e4(c)}\t{fmt_e4(p)}\t{name}\n")
+    return "".join(buf)
+
+
+class TraitTableWriter:
+    """The combined table of a multi-trait scan, written batch by batch on its own thread: `put(prefixes, stats, name, rows)`
+    hands one trait's (or one batch of one trait's) results over and returns; the thread formats and appends them in the order
+    they were put.  `close()` waits, renames the temporary file and returns the number of data lines."""
+
+    def __init__(self, path, depth=8):
+        import queue
+        import threading
+        self.path, self.tmp = path, f"{path}.tmp.{os.getpid()}"
+        self.lines, self.err = 0, None
+        self.q = queue.Queue(maxsize=depth)
+        self.fh = open(self.tmp, "w")
+        self.fh.write(HEADER_TRAITS)
+        self.th = threading.Thread(target=self._run, name="jx-trait-writer", daemon=True)
+        self.th.start()
+
+    def _run(self):
+        while True:
+            item = self.q.get()
+            if item is None:
+                return
+            if self.err is not None:
+                continue
+            try:
+                prefixes, stats, name, rows = item
+                for i0 in range(0, len(stats), 65536):
+                    sl = slice(i0, i0 + 65536)
+                    self.fh.write(format_trait_rows(prefixes[sl], stats[sl], name) if rows is None else
+                                  format_trait_rows(prefixes, stats[sl], name, rows[sl]))
+                self.lines += len(stats)
+            except BaseException as e:        # noqa: BLE001 - reported by put() / close()
+                self.err = e
+
+    def put(self, prefixes, stats, name, rows=None):
+        if self.err is not None:
+            raise self.err
+        self.q.put((prefixes, stats, name, rows))
+
+    def abort(self):
+        self.err = self.err or RuntimeError("aborted")
+        self.q.put(None)
+        self.th.join()
+        self.fh.close()
+        try:
+            os.remove(self.tmp)
+        except OSError:
+            pass
+
+    def close(self) -> int:
+        self.q.put(None)
+        self.th.join()
+        self.fh.close()
+        if self.err is not None:
+            try:
+                os.remove(self.tmp)
+            except OSError:
+                pass
+            raise self.err
+        os.replace(self.tmp, self.path)
+        return self.lines
