@@ -351,6 +351,23 @@ int jxg_lmm_scan_chain(const float *d_grot, int nrows, int n, const double *d_s,
 int jxg_lmm_scan_exact_chain(const float *d_grot, int nrows, int n, const double *d_s, const double *d_xcov, const double *d_y,
                              int p, double low, double high, double tol, int max_iter, const int32_t *d_chain_off, int nchains,
                              double *d_carry, int with_plrt, double nullml, double *d_out, int32_t *d_evals, void *stream);
+/* D3 for MANY traits along warm-start chains on one block of rotated rows (trait-level LMM; `jx gwas -lmm -trait-level-lmm`).
+ * Shared by all traits: d_grot (nrows, n), d_s, d_xcov and the chain offsets (nchains + 1, relative to this block).  Per trait
+ * t < ntraits: its table workspace at d_work + t work_stride_bytes (jxg_lmm_tables_build with the trait's y~; a multiple of 16 and
+ * at least jxg_lmm_tables_bytes), d_out + t out_rows 3 (beta, se, p; no plrt column), d_evals + t out_rows (or NULL) and the carried
+ * states d_carry + t carry_stride (as jxg_lmm_scan_chain_tab).  One workgroup per (chain, trait): its waves split the samples of
+ * every evaluation and add their parts in a fixed order -- the table of a trait has the same bits alone or in any batch, in one
+ * call or cut into blocks.  p <= 7 (beyond, loop jxg_lmm_scan_chain_tab); ntraits <= 65535.
+ * _nw: the same with the number of waves per workgroup given (4, 8 or 16) -- the measurement behind the fixed choice; results
+ * depend on it in the last bits. */
+int jxg_lmm_traits_chain_tab(const float *d_grot, int nrows, int n, const double *d_s, const double *d_xcov, int p, double low,
+                             double high, const void *d_work, int64_t work_stride_bytes, int ntraits, double tol, int max_iter,
+                             const int32_t *d_chain_off, int nchains, double *d_carry, int64_t carry_stride, double *d_out,
+                             int64_t out_rows, int32_t *d_evals, void *stream);
+int jxg_lmm_traits_chain_tab_nw(const float *d_grot, int nrows, int n, const double *d_s, const double *d_xcov, int p, double low,
+                                double high, const void *d_work, int64_t work_stride_bytes, int ntraits, double tol, int max_iter,
+                                const int32_t *d_chain_off, int nchains, double *d_carry, int64_t carry_stride, double *d_out,
+                                int64_t out_rows, int32_t *d_evals, int nw, void *stream);
 /* The series form of D3 in two steps (csrc/k_scan_fast.hip): jxg_lmm_series_coef_tab turns a block of rotated rows into every
  * SNP's Chebyshev series of its SNP-specific sums (one pass over the rows on the f64 matrix pipes; d_scoef: nrows x
  * jxg_lmm_series_doubles(p, low, high) doubles, d_ssq: nrows), jxg_lmm_series_brent_tab runs the Brent searches on stored series

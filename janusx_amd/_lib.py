@@ -137,6 +137,10 @@ SIGNATURES = {
     "jxg_sps_solve_multi": [c_i, c_p, c_p, c_p, c_d, c_p, c_p, c_i, c_i, c_d, c_i, c_p, c_p, c_p, c_p],
     "jxg_sps_scan_sums": [c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p],
     "jxg_lmm_scan_chain_tab": [c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
+    "jxg_lmm_traits_chain_tab": [c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_l, c_i, c_d, c_i, c_p, c_i, c_p, c_l, c_p, c_l, c_p,
+                                 c_p],
+    "jxg_lmm_traits_chain_tab_nw": [c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_l, c_i, c_d, c_i, c_p, c_i, c_p, c_l, c_p, c_l,
+                                    c_p, c_i, c_p],
     "jxg_lmm_scan_chain": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
     "jxg_lmm_scan_exact_chain": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_p, c_i, c_p, c_i, c_d, c_p, c_p, c_p],
     "jxg_lmm_series_doubles": [c_i, c_d, c_d],

@@ -7,6 +7,10 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
                             [-maf 0.02] [-geno 0.05] [-het 1.0] [-o OUT] [-force-model]
   python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv -n T1 -n T2 ... -lm -trait-level [-trait-pmax P] [-c COV.tsv] [-o OUT]
                             (many traits in one pass: traits that share a sample mask are scanned together, one table {out}.lm.tsv)
+  python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv -n T1 -n T2 ... -lmm -trait-level-lmm [-chunksize N] [-warm-start none|chain]
+                            [-warm-chain-pieces P] [-force-model] [-trait-pmax P]
+                            (traits that share a sample mask share one eigendecomposition and one rotation of every SNP block,
+                            one table {out}.lmm.tsv)
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
@@ -499,6 +503,59 @@ def _run_lm_trait_level(packed_t, n_fam, traits, names, samples_of, design_of, y
     print(f"-lm -trait-level: {done} traits, {lines} rows -> {path} ({time.perf_counter() - t0:.2f}s)")
 
 
+def _run_lmm_trait_level(packed_t, n_fam, k, traits, names, samples_of, design_of, y_of, args, bim, out, pmax):
+    """`jx gwas -lmm -trait-level-lmm`: the traits grouped by sample mask; per group ONE eigendecomposition, ONE rotation of the
+    design and of every SNP block for all its traits (`pipeline.run_traits_lmm`; a group of one trait takes the same code), all
+    into the combined table {out}.lmm.tsv: per trait the lines of its single-trait `.lmm.tsv` (`miss` as a rate) followed by the
+    phenotype column.  Unless -force-model, a group in which the null likelihood-ratio test sends any trait to the LM is left to
+    the trait-by-trait route.  -> the traits written here."""
+    from . import pipeline as pl
+    from .tsv import TraitTableWriter, assoc_trait_stats, resolve_snp_name, trait_site_prefixes
+    t0 = time.perf_counter()
+    path = f"{out}.lmm.tsv"
+    writer = TraitTableWriter(path)
+    chain = None
+    if _warm_start_mode(args) == "chain":
+        chain = (max(1, int(args.chunksize)), max(1, int(args.warm_chain_pieces)))
+    done = set()
+    try:
+        for keep_idx, members in group_traits_by_samples(traits, samples_of):
+            n = len(keep_idx)
+            label = ",".join(names[ti] for ti in members[:3]) + ("" if len(members) <= 3 else f",... ({len(members)} traits)")
+            if n < 10:
+                continue                 # the trait-by-trait loop reports it
+            t1 = time.perf_counter()
+            y = np.stack([y_of(keep_idx, ti) for ti in members])
+            res = pl.run_traits_lmm(packed_t, n_fam, k, keep_idx, y, design_of(keep_idx), args.maf, args.geno, args.het,
+                                    force_model=bool(args.force_model), warm_chain=chain)
+            if res.switch is not None:
+                _sw, stat, pv = res.null_lrt[res.switch]
+                print(f"[{label}] Warning: -trait-level-lmm: trait {names[members[res.switch]]} would switch to LM (null LRT "
+                      f"stat={stat:.4g}, p={pv:.4g} >= 0.05); this group goes trait by trait")
+                continue
+            rows = np.nonzero(res.keep)[0]
+            prefixes = trait_site_prefixes([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows],
+                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in rows],
+                                           [bim.a0[j] for j in rows], [bim.a1[j] for j in rows], res.af, res.miss, as_rate=True)
+            for pos_t, ti in enumerate(members):
+                st4 = assoc_trait_stats(res.stats[pos_t])
+                if pmax is None:
+                    writer.put(prefixes, st4, names[ti])
+                else:
+                    hit = np.nonzero(st4[:, 3] <= float(pmax))[0]
+                    writer.put(prefixes, st4[hit], names[ti], hit)
+                done.add(ti)
+            nulls = " ".join(f"{names[ti]}:lambda0={nf.lbd:.5g},pve={nf.pve:.4f}" for ti, nf in zip(members[:3], res.nulls))
+            print(f"[{label}] -lmm -trait-level-lmm: n={n} snps={len(rows)} traits={len(members)} {nulls} "
+                  f"({time.perf_counter() - t1:.2f}s)")
+    except BaseException:
+        writer.abort()
+        raise
+    lines = writer.close()
+    print(f"-lmm -trait-level-lmm: {len(done)} traits, {lines} rows -> {path} ({time.perf_counter() - t0:.2f}s)")
+    return done
+
+
 def cmd_gwas(args):
     import torch
     from . import janusx as jxrs
@@ -527,16 +584,24 @@ def cmd_gwas(args):
         raise SystemExit(str(e))
     trait_level = bool(getattr(args, "trait_level", False))
     trait_pmax = getattr(args, "trait_pmax", None)
-    if trait_pmax is not None and not trait_level:
+    trait_lmm = bool(getattr(args, "trait_level_lmm", False))
+    if trait_pmax is not None and not (trait_level or trait_lmm):
         raise SystemExit("-trait-pmax belongs to -trait-level")
     if trait_level:
         # the reference's conditions (python/janusx/assoc/workflow_model_packed.py:5046-5064), before anything is loaded
         if not getattr(args, "lm", False):
-            raise SystemExit("-trait-level: the LM trait-level route requires -lm (the reference's trait-level -lmm is not built).")
+            raise SystemExit("-trait-level: the LM trait-level route requires -lm (the trait-level route of -lmm is -trait-level-lmm).")
         if trait_pmax is not None and not (0.0 <= float(trait_pmax) <= 1.0):
             raise SystemExit("-trait-pmax must be within [0, 1]")
         if len(_select_traits(_read_table(args.pheno)[1], args.ncol)) <= 1:
             raise SystemExit("LM trait-level route requires at least 2 traits.")
+    if trait_lmm:
+        if not args.lmm:
+            raise SystemExit("-trait-level-lmm: the LMM trait-level route requires -lmm.")
+        if trait_pmax is not None and not (0.0 <= float(trait_pmax) <= 1.0):
+            raise SystemExit("-trait-pmax must be within [0, 1]")
+        if len(_select_traits(_read_table(args.pheno)[1], args.ncol)) <= 1:
+            raise SystemExit("LMM trait-level route requires at least 2 traits.")
     rank, world = _dist_setup()
     # the payload goes to HBM in windows (bed.stage_bed_payload: `mmap_window_mb` of the reference's BED routes); nothing
     # below holds a host copy of it
@@ -710,6 +775,14 @@ def cmd_gwas(args):
             _run_lm_trait_level(packed_t, n_fam, traits, names, trait_samples, trait_design,
                                 lambda keep_idx, ti: np.array([ph[pos[fam[j]], ti] for j in keep_idx]), args, bim, out, trait_pmax)
         run_lm = False
+    lmm_done = set()      # traits whose -lmm rows went into the combined table of -trait-level-lmm
+    if trait_lmm:
+        if world > 1:
+            print("-trait-level-lmm: one rank only; -lmm goes trait by trait as without it")
+        else:
+            lmm_done = _run_lmm_trait_level(packed_t, n_fam, k, traits, names, trait_samples, trait_design,
+                                            lambda keep_idx, ti: np.array([ph[pos[fam[j]], ti] for j in keep_idx]), args, bim, out,
+                                            trait_pmax)
     for ti in traits:
         name = names[ti]
         keep_idx = trait_samples(ti)
@@ -722,7 +795,8 @@ def cmd_gwas(args):
         if (run_lm or lm2_idx is not None) and rank == 0:
             cov_rows = np.array([cv[cpos[fam[j]]] for j in keep_idx]) if lm2_idx is not None else None
             _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, args, bim, out, name)
-        for mode in (["lmm"] if args.lmm else []) + (["lmm2"] if args.lmm2 else []) + (["fvlmm"] if args.fvlmm else []):
+        for mode in ((["lmm"] if args.lmm and ti not in lmm_done else []) + (["lmm2"] if args.lmm2 else []) +
+                     (["fvlmm"] if args.fvlmm else [])):
             t1 = time.perf_counter()
             # rows are formatted and written block by block on a writer thread while the device scans the next block
             # (src/stats/lmm.rs:975-1477 with its AsyncTsvWriter, src/stats/common.rs:374)
@@ -1580,8 +1654,12 @@ def main(argv=None):
     g.add_argument("-trait-level", "--trait-level", dest="trait_level", action="store_true", default=False,
                    help="with -lm and two or more traits: traits that share a sample mask are scanned together on the matrix "
                         "pipes and all land in one table {out}.lm.tsv with a phenotype column")
+    g.add_argument("-trait-level-lmm", "--trait-level-lmm", dest="trait_level_lmm", action="store_true", default=False,
+                   help="with -lmm and two or more traits: traits that share a sample mask share one eigendecomposition and one "
+                        "rotation of every SNP block and all land in one table {out}.lmm.tsv with a phenotype column")
     g.add_argument("-trait-pmax", "--trait-pmax", dest="trait_pmax", type=float, default=None, metavar="P",
-                   help="with -trait-level: write only the rows with pwald <= P (an extension; the reference has no such flag)")
+                   help="with -trait-level / -trait-level-lmm: write only the rows with pwald <= P (an extension; the reference "
+                        "has no such flag)")
     g.add_argument("-lm2", "--lm2", nargs="?", const="__SELF__", default=None, metavar="COVCOL",
                    help="linear model with SNP-by-covariate interaction terms over the selected columns of the merged -c table "
                         "-> {out}.{trait}.lm2.tsv; 0-based selectors like 0, 0:3, :2, 0,3; without columns it runs -lm")

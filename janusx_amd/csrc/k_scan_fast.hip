@@ -2369,3 +2369,200 @@ extern "C" int jxg_lmm2_scan(const float *d_grot, int nrows, int n, const double
     (void)hipFreeAsync(work, st);
     return rc;
 }
+
+// ---- trait-level LMM: many traits on ONE block of rotated rows, chains walked by whole workgroups ----------------------------
+// Bounds wider than two width-2 segments have no per-SNP series (series_ok), so a chain is walked by direct evaluations: with one
+// wave per chain (lmm_scan_fast_kernel) every evaluation is a pass of 64 lanes over all n samples and a block of rows holds only
+// block_rows / chunk chains -- a handful of busy waves.  Here one workgroup of NW waves serves one (chain, trait): grid.x = chain,
+// grid.y = trait; every wave owns a FIXED contiguous slice of the samples, forms its part of the SNP-specific sums
+// (fast_eval_accumulate + wave sum), the NW parts are added through LDS in wave order 0 .. NW - 1 (no atomics: the order is
+// fixed, the result deterministic) and every wave finishes the evaluation on the SAME numbers (fast_eval_finish, PRESUMMED):
+// Brent runs replicated and workgroup-uniform, which is what makes the barrier inside an evaluation legal.
+// The rows, s and X~ are shared by all traits; a trait has its own table workspace (y_c, smin, beta_mid, the lambda-only tables:
+// jxg_lmm_tables_build with its y~) at `work_stride` doubles, its own outputs, evaluation counts and carried chain states.
+// Row semantics as lmm_scan_fast_kernel along chains (carry_warm_start, src/stats/lmm.rs:134-161); no plrt column.
+namespace jx {
+
+template <int MAXD, int NW>
+__global__ __launch_bounds__(NW * 64) void lmm_traits_chain_kernel(
+    const float *__restrict__ grot, int n, const double *__restrict__ s, const double *__restrict__ xcov, int p,
+    const ChebHeader hd, const double *__restrict__ work, int64_t work_stride, double low, double high, double tol_in,
+    int max_iter, const int32_t *__restrict__ chain_off, double *__restrict__ carry, int64_t carry_stride,
+    double *__restrict__ out, int64_t out_rows, int32_t *__restrict__ evals_out) {
+    // two buffers of the NW partial sums: reduction j uses buffer j & 1, so ONE barrier per reduction is enough (a wave writes
+    // buffer b again only behind the barrier of the reduction in between, which every wave reaches after its reads of b)
+    __shared__ double part[2][NW][MAXD + 1];
+    if (MAXD == 2) p = 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int chain = blockIdx.x, trait = blockIdx.y;
+    const double *w = work + (int64_t)trait * work_stride;
+    const double *smin_ptr = w, *yc = w + CH_HDR, *coef = yc + (((int64_t)n + 1) & ~(int64_t)1);
+    const double smin = smin_ptr[0];
+    double *out_t = out + (int64_t)trait * out_rows * 3;
+    int32_t *evals_t = evals_out ? evals_out + (int64_t)trait * out_rows : nullptr;
+    double *carry_t = carry + (int64_t)trait * carry_stride;
+    // the slice of this wave: whole 64-sample strides, the same for every evaluation (waves beyond the samples add zeros)
+    const int slice = ((n + NW - 1) / NW + 63) / 64 * 64;
+    const int i0 = min(n, wave * slice), i1 = min(n, i0 + slice);
+    int flip = 0;
+    // sum of NV per-lane values over the workgroup, in wave order, the same bits in every lane of every wave
+    auto group_sum = [&](double (&v)[MAXD + 1], int nv) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < MAXD + 1; ++k)
+            if (k < nv) {
+                const double t = wave_allsum(v[k]);
+                if (lane == 0) part[flip][wave][k] = t;
+            }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MAXD + 1; ++k)
+            if (k < nv) {
+                double t = part[flip][0][k];
+#pragma unroll
+                for (int ww = 1; ww < NW; ++ww) t += part[flip][ww][k];
+                v[k] = t;
+            }
+        flip ^= 1;
+    };
+    const int r_beg = chain_off[chain], r_end = chain_off[chain + 1];
+    double last = carry_t[chain];
+    bool have_last = isfinite(last);
+    for (int r = r_beg; r < r_end; ++r) {
+        const float *g = grot + (int64_t)r * n;
+        double *o = out_t + (int64_t)r * 3;
+        double ssq;
+        {
+            double sq[MAXD + 1];
+#pragma unroll
+            for (int k = 0; k < MAXD + 1; ++k) sq[k] = 0.0;
+            for (int i = i0 + lane; i < i1; i += 64) {
+                const double v = (double)g[i];
+                sq[0] += v * v;
+            }
+            group_sum(sq, 1);
+            ssq = sq[0];
+        }
+        if (!isfinite(ssq) || ssq <= 1e-12) {
+            if (threadIdx.x == 0) {
+                o[0] = nan("");
+                o[1] = nan("");
+                o[2] = 1.0;
+                if (evals_t) evals_t[r] = 0;
+            }
+            continue;
+        }
+        FastEval<MAXD> ev;
+        auto eval_at = [&](double xx, bool want_ainv, const double *bmid) __attribute__((always_inline)) {
+            ev.ok = false;
+            ev.reml_neg = 1e8;
+            ev.q = 0.0;
+            ev.logdetv = 0.0;
+            ev.beta_k = 0.0;
+            ev.ainv_kk = 0.0;
+            const double lbd = fast_eval_lambda(xx, smin, n, p + 1);      // workgroup-uniform
+            if (lbd < 0.0) return;
+            double acc[MAXD + 1];
+#pragma unroll
+            for (int k = 0; k < MAXD + 1; ++k) acc[k] = 0.0;
+            fast_eval_accumulate<MAXD>(lbd, s, xcov, yc, g, i0, i1, 0, p, acc);
+            group_sum(acc, MAXD + 1);
+            fast_eval_finish<MAXD, true>(xx, hd, coef, n, p, want_ainv, bmid, acc, ev);
+        };
+        auto objective = [&](double xx) __attribute__((always_inline)) -> double {
+            eval_at(xx, false, nullptr);
+            return ev.reml_neg;
+        };
+        double x = 0.0;
+        int evals = 0;
+        brent_minimize(objective, low, high, tol_in, max_iter, have_last, last, x, evals);
+        last = x;
+        have_last = true;
+        // final_beta_se (src/stats/reml.rs:472-568) at the optimum
+        eval_at(x, true, smin_ptr + 8);
+        double beta = nan(""), se = nan("");
+        const int dim = p + 1;
+        if (ev.ok) {
+            const double sigma2 = ev.q / ((double)n - (double)dim);
+            const double var = sigma2 * ev.ainv_kk;
+            if (var > 0.0 && isfinite(var)) {
+                beta = ev.beta_k;
+                se = sqrt(var);
+            }
+        }
+        if (threadIdx.x == 0) {
+            if (evals_t) evals_t[r] = evals;
+            if (isfinite(beta) && isfinite(se) && se > 0.0) {
+                const double z = beta / se;
+                double pv = 2.0 * (0.5 * jx_erfc(fabs(z) / 1.4142135623730951));
+                if (pv < 2.2250738585072014e-308) pv = 2.2250738585072014e-308;
+                if (pv > 1.0) pv = 1.0;
+                o[0] = beta;
+                o[1] = se;
+                o[2] = isfinite(pv) ? pv : 1.0;
+            } else {
+                o[0] = nan("");
+                o[1] = nan("");
+                o[2] = 1.0;
+            }
+        }
+    }
+    if (threadIdx.x == 0 && have_last) carry_t[chain] = last;
+}
+
+}  // namespace jx
+
+// waves per workgroup of lmm_traits_chain_kernel, one value per MAXD (2 / 4 / 8): results depend on the summation order, so the
+// production entry never varies it.  Measured with scripts/time_lmm_traits.py (MAXD = 4 at n = 20 000, ten chains
+// of 10 000 rows, 16 traits): 13.6 s with 4 waves, 9.5 s with 8, 15.4 s with 16 (1024 threads leave 128 VGPRs: the tail spills)
+static int traits_chain_nw(int dim) { return dim <= 2 ? 8 : (dim <= 4 ? 8 : 8); }
+
+// jxg_lmm_traits_chain_tab with the number of waves per workgroup given (4 / 8 / 16): the measurement behind the fixed choice
+extern "C" int jxg_lmm_traits_chain_tab_nw(const float *d_grot, int nrows, int n, const double *d_s, const double *d_xcov, int p,
+                                           double low, double high, const void *d_work, int64_t work_stride_bytes, int ntraits,
+                                           double tol, int max_iter, const int32_t *d_chain_off, int nchains, double *d_carry,
+                                           int64_t carry_stride, double *d_out, int64_t out_rows, int32_t *d_evals, int nw,
+                                           void *stream) {
+    if (nrows <= 0 || nchains <= 0 || ntraits <= 0) return 0;
+    if (!d_chain_off || !d_carry) return fail("jxg_lmm_traits_chain_tab: chain offsets and carry states are required");
+    if (p < 1 || p + 1 > 8) return fail("jxg_lmm_traits_chain_tab: p out of range (1 .. 7; loop jxg_lmm_scan_chain_tab beyond)");
+    if (!(low < high)) return fail("low must be < high");
+    if (!fast_path_ok(p, low, high)) return fail("jxg_lmm_traits_chain_tab: configuration needs the exact scan path");
+    if (nw != 4 && nw != 8 && nw != 16) return fail("jxg_lmm_traits_chain_tab: waves per workgroup must be 4, 8 or 16");
+    if (work_stride_bytes % 16 != 0 || work_stride_bytes < jxg_lmm_tables_bytes(n, p, low, high))
+        return fail("jxg_lmm_traits_chain_tab: workspace stride below jxg_lmm_tables_bytes or not a multiple of 16");
+    if (out_rows < nrows || carry_stride < nchains) return fail("jxg_lmm_traits_chain_tab: strides below the rows / chains of the call");
+    if (ntraits > 65535) return fail("jxg_lmm_traits_chain_tab: more than 65535 traits in one launch");
+    const ChebHeader hd = make_header(p, low, high);
+    const int dim = p + 1;
+    const int64_t wstride = work_stride_bytes / (int64_t)sizeof(double);
+#define JX_TRAITS_LAUNCH(MAXDV, NWV)                                                                                          \
+    hipLaunchKernelGGL((lmm_traits_chain_kernel<MAXDV, NWV>), dim3(nchains, ntraits), dim3(NWV * 64), 0, (hipStream_t)stream,  \
+                       d_grot, n, d_s, d_xcov, p, hd, (const double *)d_work, wstride, low, high, tol, max_iter, d_chain_off, \
+                       d_carry, carry_stride, d_out, out_rows, d_evals)
+#define JX_TRAITS_BY_NW(MAXDV)                                                                                                \
+    do {                                                                                                                      \
+        if (nw == 4) JX_TRAITS_LAUNCH(MAXDV, 4);                                                                              \
+        else if (nw == 8) JX_TRAITS_LAUNCH(MAXDV, 8);                                                                         \
+        else JX_TRAITS_LAUNCH(MAXDV, 16);                                                                                     \
+    } while (0)
+    if (dim <= 2) JX_TRAITS_BY_NW(2);
+    else if (dim <= 4) JX_TRAITS_BY_NW(4);
+    else JX_TRAITS_BY_NW(8);
+#undef JX_TRAITS_BY_NW
+#undef JX_TRAITS_LAUNCH
+    JX_LAUNCH_CHECK();
+    return 0;
+}
+
+// The exact scan of `ntraits` traits along warm-start chains on ONE block of rotated rows (trait-level LMM).  Shared: d_grot
+// (nrows, n), d_s, d_xcov, the chain offsets (nchains + 1, relative to this block).  Per trait t: the table workspace at d_work +
+// t work_stride_bytes (jxg_lmm_tables_build with the trait's y~), d_out + t out_rows 3, d_evals + t out_rows (or NULL), d_carry +
+// t carry_stride (as jxg_lmm_scan_chain_tab).  p <= 7.
+extern "C" int jxg_lmm_traits_chain_tab(const float *d_grot, int nrows, int n, const double *d_s, const double *d_xcov, int p,
+                                        double low, double high, const void *d_work, int64_t work_stride_bytes, int ntraits,
+                                        double tol, int max_iter, const int32_t *d_chain_off, int nchains, double *d_carry,
+                                        int64_t carry_stride, double *d_out, int64_t out_rows, int32_t *d_evals, void *stream) {
+    return jxg_lmm_traits_chain_tab_nw(d_grot, nrows, n, d_s, d_xcov, p, low, high, d_work, work_stride_bytes, ntraits, tol, max_iter,
+                                       d_chain_off, nchains, d_carry, carry_stride, d_out, out_rows, d_evals, traits_chain_nw(p + 1),
+                                       stream);
+}

@@ -3626,6 +3626,66 @@ def lm_trait_assoc_packed(packed, n_samples, y_trait_major, x, row_flip, row_maf
     return res.cpu().numpy() if pmax is None else (res.trait, res.row, res.stats)
 
 
+def lmm_trait_assoc_packed(packed, n_samples, y_trait_major, x, grm, row_flip, row_maf, sample_indices=None, row_indices=None,
+                           chunk_size=10000, warm_start=None, warm_chain_pieces=1, force_model=True):
+    """Extension (the reference has no single native function for this route: its trait-level LMM,
+    `_run_mixed_trait_packed_multi_entry`, python/janusx/assoc/workflow_model_packed.py:5932-6723, is Python around
+    `lmm_rotate_y_with_ut_f64`, `lmm_reml_null_f32` and one `lmm_reml_assoc_packed_f32` per trait): T traits on the same samples
+    and design, scanned together -- ONE eigendecomposition of `grm` + 1e-6 I, ONE rotation of [X | Y], a null fit per trait
+    (-5, 5, 50, 1e-3) and ONE rotation of every SNP block for all traits; bounds [-5, 5], max_iter 50, tol 1e-2, start log10
+    lambda0 of the trait.  `y_trait_major` (T, n), `x` (n, p) with the intercept, `grm` (n, n) of the selected samples in their
+    order, or (n_samples, n_samples) of all samples when `sample_indices` selects among them; `row_flip` / `row_maf` per scanned
+    row (the rows `row_indices` of the payload, or all).  Warm start as `lmm_reml_assoc_packed_f32` (None = "chain"): chains of
+    `chunk_size` scanned rows cut into `warm_chain_pieces`; "none": every SNP starts from log10 lambda0.
+    force_model=False: `gwas_lmm_lm_null_lrt_decision` per trait; when any trait would switch to the LM nothing is scanned.
+    -> (stats (T, m, 3) f64 beta, se, p -- None when a trait would switch --, nulls: per trait (lambda0, ML0, REML0, pve)
+    -- with force_model=False followed by (switch, LRT statistic, p))."""
+    import torch
+    from . import pipeline as pl
+    from .stats import scan_lut_from_counts
+    if int(n_samples) <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    if int(chunk_size) <= 0:
+        raise RuntimeError("chunk_size must be > 0")
+    y = _c(y_trait_major, np.float64)
+    xx = _c(x, np.float64)
+    if y.ndim != 2 or xx.ndim != 2 or xx.shape[0] != y.shape[1]:
+        raise RuntimeError("y_trait_major must be (T, n) and x (n, p)")
+    n = int(y.shape[1])
+    idx, n_sel = _opt_idx(sample_indices)
+    if (n_sel if idx is not None else int(n_samples)) != n:
+        raise RuntimeError(f"sample_indices length mismatch: got {n_sel if idx is not None else int(n_samples)}, "
+                           f"expected y_trait_major cols={n}")
+    panel = _panel(packed, n_samples, idx)
+    rows = np.arange(panel.m, dtype=np.int64) if row_indices is None else _c(row_indices, np.int64).ravel()
+    if rows.size and (rows.min() < 0 or rows.max() >= panel.m):
+        raise RuntimeError(f"row_indices out of range for n_snps={panel.m}")
+    fl = np.asarray(row_flip).astype(bool).ravel()
+    mf = _c(row_maf, np.float32).ravel()
+    if fl.shape[0] != len(rows) or mf.shape[0] != len(rows):
+        raise RuntimeError(f"row_flip / row_maf length mismatch: got {fl.shape[0]} / {mf.shape[0]}, expected {len(rows)}")
+    k = grm if _is_device_tensor(grm) else torch.from_numpy(np.ascontiguousarray(np.asarray(grm))).to(panel.device)
+    if k.ndim != 2 or k.shape[0] != k.shape[1] or int(k.shape[0]) not in (n, int(n_samples)):
+        raise RuntimeError(f"grm must be ({n}, {n}) or ({int(n_samples)}, {int(n_samples)})")
+    sub = idx if (idx is not None and int(k.shape[0]) != n) else None
+    s, ut64 = pl.eigh_from_grm(k, 1e-6, sub, f32_consumer=True)
+    models = pl.SpectralModel.for_traits(s, ut64, xx, y)
+    del ut64
+    nulls = [(mdl.null.lbd, mdl.null.ml0, mdl.null.reml0, mdl.null.pve) for mdl in models]
+    if not force_model:
+        lrt = [tuple(gwas_lmm_lm_null_lrt_decision(y[ti], xx[:, 1:], nulls[ti][1])[:3]) for ti in range(len(models))]
+        nulls = [nl + d for nl, d in zip(nulls, lrt)]
+        if any(d[0] for d in lrt):
+            return None, nulls
+    lut = scan_lut_from_counts(mf, fl, panel.counts()[rows], n)
+    init = np.array([float(np.log10(nl[0])) if (np.isfinite(nl[0]) and nl[0] > 0.0) else float("nan") for nl in nulls])
+    chain_off = None
+    if _resolve_warm_start(warm_start, "JX_LMM_UNIFIED_NO_WARM_START") == "chain":
+        chain_off = pl.traits_chain_offsets(len(rows), int(chunk_size), int(warm_chain_pieces))
+    out = pl.scan_rows_lmm_traits(panel, models[0], rows, lut, models[0].y_rot, init, chain_off=chain_off)
+    return out.cpu().numpy(), nulls
+
+
 # ------------------------------------------------------------------------------------------------
 # Genotype rows as numbers and the two matrix-free products the reference's Python layer asks for beside the path
 # (src/stats/packed.rs:577-760, 2060-2560): decode of selected rows, M'alpha, cross-GRM times alpha

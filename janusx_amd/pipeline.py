@@ -11,6 +11,7 @@ Mirrors the reference's call stack for `jx gwas -lmm/-fvlmm` (SURVEY.md §3.1-3.
 """
 from __future__ import annotations
 
+import copy
 import math
 import os
 import time
@@ -402,6 +403,46 @@ class SpectralModel:
         self.n, self.p = int(self.S.shape[0]), int(self.xcov.shape[1])
         self.null = self._planes = self._fv = None
         return self
+
+    @classmethod
+    def for_traits(cls, s: torch.Tensor, ut64: torch.Tensor, x: np.ndarray, Y: np.ndarray):
+        """The models of T traits on the same samples and design (trait-level LMM): ONE cast of U^T and ONE rotation of
+        [X | Y] (n x (p + T)); the models share S, `ut`, `xcov` and -- through the first one, which the rotation stage is built
+        from -- the planes of U^T; each has its own y~ and null fit (-5, 5, 50, 1e-3 as the constructor).  Y: (T, n).
+        -> list of T models."""
+        dev = s.device
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        Y = np.ascontiguousarray(np.atleast_2d(np.asarray(Y, dtype=np.float64)))
+        n = int(s.shape[0])
+        if x.ndim != 2 or x.shape[0] != n or Y.shape[1] != n:
+            raise RuntimeError(f"design row mismatch: got {x.shape[0]} / {Y.shape[1]}, expected {n}")
+        p, nt = int(x.shape[1]), int(Y.shape[0])
+        base = cls.__new__(cls)
+        base.n, base.p, base.S = n, p, s
+        base.ut = torch.empty((n, n), dtype=torch.float32, device=dev)
+        check(lib().jxg_cast_f64_to_f32(_ptr(ut64), _ptr(base.ut), n * n, _stream()))
+        cols = np.concatenate([x, Y.T], axis=1)
+        parts = []
+        for c0 in range(0, p + nt, 16):                       # jxg_rotate_xy takes up to 16 columns
+            xy = torch.from_numpy(np.ascontiguousarray(cols[:, c0:c0 + 16])).to(dev)
+            part = torch.empty_like(xy)
+            check(lib().jxg_rotate_xy(_ptr(base.ut), n, _ptr(xy), int(xy.shape[1]), _ptr(part), _stream()))
+            parts.append(part)
+        rot = torch.cat(parts, dim=1)
+        base.xcov = rot[:, :p].contiguous()
+        base.y_rot = rot[:, p:].t().contiguous()              # (T, n): every trait's y~
+        base.null = base._planes = base._fv = None
+        models = []
+        for ti in range(nt):
+            mdl = base if ti == 0 else copy.copy(base)
+            mdl.y = base.y_rot[ti]
+            out3 = torch.empty(3, dtype=torch.float64, device=dev)
+            check(lib().jxg_lmm_reml_null(_ptr(mdl.S), _ptr(mdl.xcov), _ptr(mdl.y), n, p, -5.0, 5.0, 50, 1e-3, _ptr(out3),
+                                          _stream()))
+            lbd, ml0, reml0 = [float(v) for v in out3.cpu().numpy()]
+            mdl.null = mdl._profile(lbd, ml0, reml0)
+            models.append(mdl)
+        return models
 
     def _profile(self, lbd, ml0, reml0) -> NullFit:
         # assoc.py:907-951 `_lmm_profile_exact_vc` + :1845-1876 (host, O(n p^2))
@@ -877,6 +918,107 @@ def scan_rows(panel: Panel, model: SpectralModel, rows: np.ndarray, lut: np.ndar
         scanner = _fixed_lambda_scan(stage, model.p, out, w, py, wx, a_chol, ypy, df, False, with_plrt,
                                      float(nullml) if nullml is not None else 0.0, log_det_v)
     _run_blocks(scanner, out, br, 2 if mk > br else 1, times, on_block, progress, progress_every)
+    return (out, evals) if return_evals else out
+
+
+TRAITS_BLOCK_BYTES = 8 << 30      # rotated-row buffer of the trait-level LMM scan (one of two): a block's chains run side by side
+
+
+def scan_rows_lmm_traits(panel: Panel, shared: SpectralModel, rows: np.ndarray, lut: np.ndarray, y_rot, init, low=-5.0, high=5.0,
+                         max_iter=50, tol=1e-2, chain_off=None, block_rows=None, return_evals=False, on_trait=None,
+                         times: StageTimes = None):
+    """The exact per-SNP REML scan of T traits that share samples and design (`_run_mixed_trait_packed_multi_entry`,
+    python/janusx/assoc/workflow_model_packed.py:6473-6515): ONE rotation stage and ONE pass over the rows; every rotated block
+    is scanned for all traits before the next one is rotated (the reference rotates every block once per trait).
+    shared: S / U^T / X~ (any model of `SpectralModel.for_traits`); y_rot (T, n) f64: the traits' rotated phenotypes; init (T):
+    log10 lambda0 per trait, NaN = none (the interval midpoint).  chain_off as `scan_rows`: the chains that touch a block are
+    walked for all traits by ONE launch (`jxg_lmm_traits_chain_tab`, a workgroup per (chain, trait); per-trait carried states, so
+    a chain cut by a block continues in the next); without chains `jxg_lmm_scan_tab` once per trait on the same buffer.
+    block_rows: None = whole chains -- the largest multiple of the longest chain within TRAITS_BLOCK_BYTES -- or 32768 without
+    chains.  on_trait(t, table (m, 3) host array): called per trait, in order, when the scan is done.  times: receives "tables"
+    (host clock, synchronised) and the "rotate" / "scan" stage times of the blocks (device events).
+    -> (T, m, 3) f64 device tensor [beta, se, p] (and the (T, m) evaluation counts)."""
+    dev, n, p = panel.device, shared.n, shared.p
+    if panel.n != n:
+        raise RuntimeError(f"selected sample count {panel.n} != model n {n}")
+    if not torch.is_tensor(y_rot):
+        y_rot = torch.from_numpy(np.ascontiguousarray(y_rot, dtype=np.float64))
+    y_rot = y_rot.to(device=dev, dtype=torch.float64).contiguous()
+    if y_rot.ndim != 2 or int(y_rot.shape[1]) != n:
+        raise RuntimeError(f"y_rot must be (T, {n})")
+    nt, mk = int(y_rot.shape[0]), len(rows)
+    init = np.asarray(init, dtype=np.float64).ravel()
+    if len(init) != nt:
+        raise RuntimeError("one init_log10_lbd per trait (NaN: none)")
+    lo_b, hi_b, tol, max_iter = float(low), float(high), float(tol), int(max_iter)
+    out = torch.empty((nt, mk, 3), dtype=torch.float64, device=dev)
+    evals = torch.zeros((nt, mk), dtype=torch.int32, device=dev) if return_evals else None
+    if mk == 0 or nt == 0:
+        return (out, evals) if return_evals else out
+    co = None
+    if chain_off is not None:
+        co = np.ascontiguousarray(chain_off, dtype=np.int64)
+        if co.ndim != 1 or len(co) < 2 or co[0] != 0 or co[-1] != mk or np.any(np.diff(co) < 0):
+            raise RuntimeError("chain_off must ascend from 0 to len(rows)")
+    if block_rows is None:
+        block_rows = 32768
+        if co is not None:
+            longest = max(1, int(np.max(np.diff(co))))
+            block_rows = max(1, TRAITS_BLOCK_BYTES // (4 * n) // longest) * longest
+    br = int(min(block_rows, mk))
+    stage = DenseRotation(panel, shared, rows, lut, br)
+    s_p, x_p = _ptr(shared.S), _ptr(shared.xcov)
+    nbytes = int(lib().jxg_lmm_tables_bytes(n, p, lo_b, hi_b))
+    stride = (nbytes + 15) // 16 * 16
+    tables = None
+    if times is not None:
+        torch.cuda.synchronize()
+    t_tab = time.perf_counter()
+    if nbytes > 0:
+        tables = torch.empty((nt, stride), dtype=torch.uint8, device=dev)
+        for ti in range(nt):
+            check(lib().jxg_lmm_tables_build(s_p, x_p, y_rot[ti].data_ptr(), n, p, lo_b, hi_b, tables[ti].data_ptr(), _stream()))
+    if times is not None:
+        torch.cuda.synchronize()
+        times.add("tables", time.perf_counter() - t_tab)
+    ev_p = (lambda ti, r0: evals[ti, r0:].data_ptr()) if evals is not None else (lambda ti, r0: None)      # noqa: E731
+    if co is None:
+        def scan(grot, r0, nr):
+            for ti in range(nt):
+                warm, x0 = (1, float(init[ti])) if math.isfinite(init[ti]) else (0, 0.0)
+                if tables is not None:
+                    check(lib().jxg_lmm_scan_tab(_ptr(grot), nr, n, s_p, x_p, p, lo_b, hi_b, tables[ti].data_ptr(), tol, max_iter,
+                                                 warm, x0, 0, 0.0, out[ti, r0:].data_ptr(), ev_p(ti, r0), _stream()))
+                else:
+                    check(lib().jxg_lmm_scan_exact(_ptr(grot), nr, n, s_p, x_p, y_rot[ti].data_ptr(), p, lo_b, hi_b, tol, max_iter,
+                                                   warm, x0, 0, 0.0, out[ti, r0:].data_ptr(), ev_p(ti, r0), _stream()))
+    else:
+        nch = len(co) - 1
+        carry = torch.from_numpy(np.repeat(np.where(np.isfinite(init), init, np.nan)[:, None], nch, axis=1).copy()).to(dev)
+        batched = tables is not None and p + 1 <= 8
+
+        def scan(grot, r0, nr):
+            c0, loc_t = _chain_segments(co, r0, r0 + nr, dev)
+            if batched:
+                check(lib().jxg_lmm_traits_chain_tab(_ptr(grot), nr, n, s_p, x_p, p, lo_b, hi_b, _ptr(tables), stride, nt, tol,
+                                                     max_iter, _ptr(loc_t), len(loc_t) - 1, carry[0, c0:].data_ptr(), nch,
+                                                     out[0, r0:].data_ptr(), mk, ev_p(0, r0), _stream()))
+                return
+            # eight covariates and more (or no tables): the one-wave-per-chain entry per trait, on the shared rotated block
+            for ti in range(nt):
+                if tables is not None:
+                    check(lib().jxg_lmm_scan_chain_tab(_ptr(grot), nr, n, s_p, x_p, p, lo_b, hi_b, tables[ti].data_ptr(), tol,
+                                                       max_iter, _ptr(loc_t), len(loc_t) - 1, carry[ti, c0:].data_ptr(), 0, 0.0,
+                                                       out[ti, r0:].data_ptr(), ev_p(ti, r0), _stream()))
+                else:
+                    check(lib().jxg_lmm_scan_exact_chain(_ptr(grot), nr, n, s_p, x_p, y_rot[ti].data_ptr(), p, lo_b, hi_b, tol,
+                                                         max_iter, _ptr(loc_t), len(loc_t) - 1, carry[ti, c0:].data_ptr(), 0, 0.0,
+                                                         out[ti, r0:].data_ptr(), ev_p(ti, r0), _stream()))
+    # `_run_blocks` sizes its loop by the first dimension of the table it is handed: one trait's rows
+    _run_blocks(_Scanner(stage, scan), out[0], br, 2 if mk > br else 1, times)
+    if on_trait is not None:
+        for ti in range(nt):
+            on_trait(ti, out[ti].cpu().numpy())
     return (out, evals) if return_evals else out
 
 
@@ -1371,6 +1513,60 @@ def run_trait(packed: torch.Tensor, n_samples: int, k: torch.Tensor, keep_idx, y
     res = GwasResult(keep, af[rows], miss[rows], out.cpu().numpy(), model.null, 0, {})
     res.model_tag, res.null_lrt = mode, lrt
     return res
+
+
+@dataclass
+class TraitsResult:
+    keep: np.ndarray        # (m,) bool, kept SNPs in BED order
+    af: np.ndarray          # (m_kept,) f32
+    miss: np.ndarray        # (m_kept,) f32 missing rate
+    stats: np.ndarray       # (T, m_kept, 3) f64 beta, se, p -- None when `switch` is set
+    nulls: list             # T NullFit
+    null_lrt: list = None   # per trait (switch_to_lm, LRT statistic, p) when the decision was evaluated
+    switch: int = None      # index of the first trait whose null LRT asks for the LM: nothing was scanned
+
+
+def traits_chain_offsets(m_kept: int, chunk: int, pieces: int = 1):
+    """Warm-start chains of the trait-level LMM route: blocks of `chunk` KEPT rows, as on the packed route
+    (`lmm_reml_assoc_packed_f32` per trait, workflow_model_packed.py:6473-6493), cut into `pieces` by halving."""
+    return st.warm_chain_offsets(st.warm_chain_blocks_packed(int(m_kept), int(chunk), 0), int(m_kept), int(pieces))
+
+
+def run_traits_lmm(packed: torch.Tensor, n_samples: int, k: torch.Tensor, keep_idx, Y: np.ndarray, x: np.ndarray, maf=0.02,
+                   geno=0.05, het=1.0, force_model=True, warm_chain=None, on_trait=None) -> TraitsResult:
+    """One group of traits measured on the same samples with the same design, scanned together (trait-level LMM,
+    `_run_mixed_trait_packed_multi_entry`, python/janusx/assoc/workflow_model_packed.py:5932-6723): ONE eigendecomposition of
+    K[keep, keep] + 1e-6 I, ONE rotation of [X | Y], per trait the null fit (-5, 5, 50, 1e-3) and its profile, ONE QC pass and
+    ONE rotation of every SNP block for all traits (`scan_rows_lmm_traits`: bounds [-5, 5], max_iter 50, tol 1e-2, start log10
+    lambda0 of the trait where it is finite and positive).  Y: (T, n_keep), x with the intercept, both restricted to keep_idx.
+    warm_chain = (chunk, pieces) or None (no chains).  force_model=False: `gwas_lmm_lm_null_lrt_decision` per trait; if any
+    trait would switch to the LM nothing is scanned and `switch` names the first such trait (the caller runs the group trait by
+    trait).  One rank only."""
+    if dist_info()[1] > 1:
+        raise RuntimeError("run_traits_lmm runs on one rank")
+    keep_idx = None if keep_idx is None else np.asarray(keep_idx, dtype=np.int64)
+    Y = np.ascontiguousarray(np.atleast_2d(np.asarray(Y, dtype=np.float64)))
+    s, ut64 = eigh_from_grm(k, 1e-6, keep_idx, f32_consumer=True)
+    models = SpectralModel.for_traits(s, ut64, x, Y)
+    del ut64
+    nulls = [mdl.null for mdl in models]
+    panel = Panel(packed, n_samples, keep_idx)
+    counts = panel.counts()
+    n = panel.n
+    keep, af, miss = st.gwas_scan_row_stats(counts, n, maf, geno, het)
+    rows = np.nonzero(keep)[0]
+    lrt = None
+    if not force_model:
+        from .janusx import gwas_lmm_lm_null_lrt_decision
+        lrt = [tuple(gwas_lmm_lm_null_lrt_decision(Y[ti], np.asarray(x)[:, 1:], nulls[ti].ml0)[:3]) for ti in range(len(models))]
+        sw = [ti for ti, d in enumerate(lrt) if d[0]]
+        if sw:
+            return TraitsResult(keep, af[rows], miss[rows], None, nulls, lrt, sw[0])
+    lut = st.scan_lut_from_counts(af[rows], np.zeros(len(rows), dtype=bool), counts[rows], n)
+    init = np.array([math.log10(nf.lbd) if (math.isfinite(nf.lbd) and nf.lbd > 0.0) else float("nan") for nf in nulls])
+    chain_off = traits_chain_offsets(len(rows), warm_chain[0], warm_chain[1]) if warm_chain is not None else None
+    out = scan_rows_lmm_traits(panel, models[0], rows, lut, models[0].y_rot, init, chain_off=chain_off, on_trait=on_trait)
+    return TraitsResult(keep, af[rows], miss[rows], out.cpu().numpy(), nulls, lrt, None)
 
 
 def _scan_trait(panel, model, rows, lut, mode, max_iter, tol, warm_start, chain_off, on_block=None):

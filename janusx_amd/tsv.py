@@ -256,7 +256,7 @@ def write_lm2_tsv(path, chrom, pos, snp, a0, a1, af, miss_counts, stats, cov_ind
     return int(stats.shape[0])
 
 
-# ---- combined multi-trait LM table (src/stats/lm_trait.rs:226-286, 645-654) ----------------------------------------------
+# ---- combined multi-trait table (src/stats/lm_trait.rs:226-286, 645-654; the trait-level LMM route writes the same layout) ----
 
 HEADER_TRAITS = "chrom\tpos\tsnp\tallele0\tallele1\taf\tmiss\tbeta\tse\tchisq\tpwald\tphenotype\n"
 
@@ -304,6 +304,23 @@ def format_trait_rows(prefixes, stats, name, rows=None) -> str:
         b, s, c, p = (float(v) for v in stats[i])
         buf.append(f"{prefixes[i if rows is None else rows[i]]}{fmt_f4(b)}\t{fmt_f4(s)}\t{fmt_e4(c)}\t{fmt_e4(p)}\t{name}\n")
     return "".join(buf)
+
+
+def assoc_trait_stats(stats):
+    """(k, >= 3) [beta, se, p] of a single-trait association table -> (k, 4) [beta, se, chisq, pwald] as its row format prints them
+    (`format_row`: chisq = (beta / se)^2 and p clamped into [MIN_POSITIVE, 1] for a finite beta and a finite positive se, else
+    chisq NaN and p = 1), so that `format_trait_rows` gives the single-trait line followed by the phenotype column."""
+    import numpy as np
+    st = np.asarray(stats, dtype=np.float64)
+    b, s, p = st[:, 0], st[:, 1], st[:, 2]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ok = np.isfinite(b) & np.isfinite(s) & (s > 0.0)
+        z = b / s
+        out = np.empty((len(st), 4), dtype=np.float64)
+        out[:, 0], out[:, 1] = b, s
+        out[:, 2] = np.where(ok, z * z, np.nan)
+        out[:, 3] = np.where(ok & np.isfinite(p), np.minimum(np.maximum(p, MIN_POSITIVE), 1.0), 1.0)
+    return out
 
 
 class TraitTableWriter:
