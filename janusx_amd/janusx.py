@@ -3848,12 +3848,19 @@ def cross_grm_times_alpha_packed_f64(packed, n_samples, row_flip, row_maf, sampl
 # GBLUP (`jx gs -BLUP`, n <= 15 000 branch): src/stats/gblup.rs:1242-1516 `gblup_reml_npy_grm`
 # ------------------------------------------------------------------------------------------------
 
-def gblup_reml_grm(grm, train_sample_indices, y_train, test_sample_indices=None, train_pred_local_indices=None,
-                   g_eps=1e-8, low=-6.0, high=6.0, max_iter=50, tol=1e-4, threads=0,
-                   return_variance_components=False, estimate_only=False):
-    """In-memory form of `gblup_reml_npy_grm`: `grm` (n_full, n_full) f32/f64.  Returns the reference's 12-tuple
-    (pred_train (k,1), pred_test (t,1), pve, lambda, ml, reml, evd_backend, evd_elapsed, 0, sigma_g2, sigma_e2,
-    effect (empty))."""
+# ---- the argument front end the GBLUP / rrBLUP / HE mirrors below share: each check of the reference written once ----------
+
+def _gs_check_iter_opts(max_iter, tol, std_eps):
+    import math
+    if int(max_iter) == 0:
+        raise RuntimeError("max_iter must be > 0")
+    if not (math.isfinite(tol) and tol > 0.0):
+        raise RuntimeError("tol must be finite and > 0")
+    if not (math.isfinite(std_eps) and std_eps > 0.0):
+        raise RuntimeError("std_eps must be finite and > 0")
+
+
+def _gs_check_reml_opts(g_eps, low, high, max_iter, tol):
     import math
     if not (math.isfinite(g_eps) and g_eps >= 0.0):
         raise RuntimeError("g_eps must be finite and >= 0")
@@ -3863,6 +3870,145 @@ def gblup_reml_grm(grm, train_sample_indices, y_train, test_sample_indices=None,
         raise RuntimeError("max_iter must be > 0")
     if not (math.isfinite(tol) and tol > 0.0):
         raise RuntimeError("tol must be finite and > 0")
+
+
+def _gs_require_stats(who, path, maf, row_flip, packed_n_samples):
+    if maf is None:
+        raise RuntimeError(f"{who}: {path} path requires `maf` argument.")
+    if row_flip is None:
+        raise RuntimeError(f"{who}: {path} path requires `row_flip` argument.")
+    if int(packed_n_samples) == 0:
+        raise RuntimeError(f"{who}: {path} path requires packed_n_samples > 0.")
+
+
+def _gs_payload(who, prefix, packed, packed_n_samples, maf, row_flip):
+    """The caller's payload with its maf / row_flip, or -- nothing of that given -- the file's payload with the loader's own
+    statistics -> (payload, n_samples, maf, row_flip).  A payload that already lives in HBM is used in place (no host copy of
+    50 GB)."""
+    if packed is None and int(packed_n_samples) <= 0:
+        pk, _miss, maf, _std, n_samples = load_bed_2bit_packed(prefix)
+        return pk, n_samples, maf, bed_packed_row_flip_mask(pk, n_samples)
+    if packed is None:
+        raise RuntimeError(f"{who}: packed payload path requires `packed` argument.")
+    _gs_require_stats(who, "packed payload", maf, row_flip, packed_n_samples)
+    pk = packed if _is_device_tensor(packed) else _c(packed, np.uint8)
+    if len(pk.shape) != 2:
+        raise RuntimeError("packed BED payload must be 2D (m, bytes_per_snp).")
+    return (pk.contiguous() if _is_device_tensor(pk) else pk), int(packed_n_samples), maf, row_flip
+
+
+def _gs_check_payload_shape(pk, n_samples):
+    if int(pk.shape[0]) == 0:
+        raise RuntimeError("No SNP rows found in BED input.")
+    if pk.shape[1] != (n_samples + 3) // 4:
+        raise RuntimeError(f"packed second dimension mismatch: got {pk.shape[1]}, expected {(n_samples + 3) // 4}")
+
+
+def _gs_kept_rows(m_total, maf, row_flip, site_keep):
+    """-> (rows int64 or None when every row of the payload is kept, maf f32 and flip mask of the kept rows)."""
+    maf_full = _c(maf, np.float32).ravel()
+    if maf_full.shape[0] != m_total:
+        raise RuntimeError(f"maf length mismatch: got {maf_full.shape[0]}, expected {m_total}")
+    flip_full = np.asarray(row_flip).astype(bool).ravel()
+    if flip_full.shape[0] != m_total:
+        raise RuntimeError(f"row_flip length mismatch: got {flip_full.shape[0]}, expected {m_total}")
+    if site_keep is None:
+        return None, maf_full, flip_full
+    mask = np.asarray(site_keep).astype(bool).ravel()
+    if mask.shape[0] != m_total:
+        raise RuntimeError(f"site_keep length mismatch: got {mask.shape[0]}, expected {m_total}")
+    rows = np.nonzero(mask)[0].astype(np.int64)
+    if rows.shape[0] == 0:
+        raise RuntimeError("No SNPs remained after applying site_keep mask.")
+    if rows.shape[0] == m_total:
+        return None, maf_full, flip_full
+    return rows, maf_full[rows], flip_full[rows]
+
+
+def _gs_meta_rows(row_source_indices, row_flip, row_maf, empty_msg):
+    """The metadata triple of the streaming GBLUP forms -> (rows int64, flip mask, maf f32), one entry per row."""
+    src = _c(row_source_indices, np.int64).ravel()
+    if src.size == 0:
+        raise RuntimeError(empty_msg)
+    if (src < 0).any():
+        raise RuntimeError("row_source_indices must be non-negative.")
+    flip = np.asarray(row_flip).astype(bool).ravel()
+    maf = _c(row_maf, np.float32).ravel()
+    if flip.shape[0] != src.shape[0] or maf.shape[0] != src.shape[0]:
+        raise RuntimeError(f"metadata length mismatch: row_source_indices={src.shape[0]}, row_flip={flip.shape[0]}, "
+                           f"row_maf={maf.shape[0]}")
+    return src, flip, maf
+
+
+def _gs_train_y(train_sample_indices, y_train, n_samples, min_train=1, few_msg="train_sample_indices must not be empty."):
+    """-> (training sample indices int64, phenotype f64), checked in the reference's order."""
+    tr = _c(train_sample_indices, np.int64).ravel()
+    if tr.size and (tr.min() < 0 or tr.max() >= n_samples):
+        raise RuntimeError("train_sample_indices out of range")
+    if tr.shape[0] < min_train:
+        raise RuntimeError(few_msg)
+    y = _c(y_train, np.float64).ravel()
+    if y.shape[0] != tr.shape[0]:
+        raise RuntimeError(f"y_train length mismatch: got {y.shape[0]}, expected {tr.shape[0]}")
+    if not np.all(np.isfinite(y)):
+        raise RuntimeError("y_train contains non-finite values.")
+    return tr, y
+
+
+def _gs_test_idx(test_sample_indices, n_samples):
+    te = np.zeros(0, dtype=np.int64) if test_sample_indices is None else _c(test_sample_indices, np.int64).ravel()
+    if te.size and (te.min() < 0 or te.max() >= n_samples):
+        raise RuntimeError("test_sample_indices out of range")
+    return te
+
+
+def _gs_pick_idx(train_pred_local_indices, n_train):
+    if train_pred_local_indices is None:
+        return None
+    pick = _c(train_pred_local_indices, np.int64).ravel()
+    if pick.size and (pick.min() < 0 or pick.max() >= n_train):
+        raise RuntimeError("train_pred_local_indices out of range")
+    return pick
+
+
+def _gs_standardise(p, std_eps):
+    """Row mean 2p and inverse standard deviation 1 / sqrt(2p(1-p)) in f32 of the (clipped) frequencies `p`, 0 where the
+    variance does not exceed max(std_eps, 1e-12) -> (rm, ri, number of rows above the cut)."""
+    f32 = np.float32
+    rm = (f32(2.0) * p).astype(f32)
+    var = np.maximum((f32(2.0) * p * (f32(1.0) - p)).astype(f32), f32(0.0))
+    good = var > f32(max(float(std_eps), 1e-12))
+    ri = np.zeros_like(var)
+    ri[good] = (f32(1.0) / np.sqrt(var[good])).astype(f32)
+    return rm, ri, int(np.count_nonzero(good))
+
+
+def _rrblup_row_stats(maf_keep, rows, m_total, row_mean, row_inv_sd, std_eps):
+    """`rrblup_subset_or_validate_stats` (rrblup.rs:568-625): the caller's row_mean / row_inv_sd, of the kept rows or of all
+    rows of the payload, or those of the minor frequencies clipped to [0, 0.5] -> (rm, ri, m_effective)."""
+    f32 = np.float32
+    if (row_mean is None) != (row_inv_sd is None):
+        raise RuntimeError("rrBLUP standardization requires row_mean and row_inv_sd together when overriding row stats.")
+    if row_mean is None:
+        return _gs_standardise(np.clip(maf_keep, f32(0.0), f32(0.5)).astype(f32), std_eps)
+    rm = _c(row_mean, f32).ravel()
+    ri = _c(row_inv_sd, f32).ravel()
+    eff_m = int(maf_keep.shape[0])
+    if rm.shape[0] == m_total and ri.shape[0] == m_total and rows is not None:
+        rm, ri = rm[rows], ri[rows]
+    elif rm.shape[0] != eff_m or ri.shape[0] != eff_m:
+        raise RuntimeError(f"External row_mean/row_inv_sd length mismatch: mean={rm.shape[0]}, inv={ri.shape[0]}, "
+                           f"expected active={eff_m} or full={m_total}.")
+    return rm, ri, int(np.count_nonzero(np.isfinite(ri) & (ri > 0)))
+
+
+def gblup_reml_grm(grm, train_sample_indices, y_train, test_sample_indices=None, train_pred_local_indices=None,
+                   g_eps=1e-8, low=-6.0, high=6.0, max_iter=50, tol=1e-4, threads=0,
+                   return_variance_components=False, estimate_only=False):
+    """In-memory form of `gblup_reml_npy_grm`: `grm` (n_full, n_full) f32/f64.  Returns the reference's 12-tuple
+    (pred_train (k,1), pred_test (t,1), pve, lambda, ml, reml, evd_backend, evd_elapsed, 0, sigma_g2, sigma_e2,
+    effect (empty))."""
+    _gs_check_reml_opts(g_eps, low, high, max_iter, tol)
     k = np.asarray(grm)
     if k.ndim != 2 or k.shape[0] != k.shape[1]:
         raise RuntimeError("GRM must be a square matrix")
@@ -3937,16 +4083,7 @@ def gblup_effect_from_meta_stream(prefix, sample_indices, alpha, row_source_indi
     a = _c(alpha, np.float64).ravel()
     if a.shape[0] != tr.shape[0]:
         raise RuntimeError(f"alpha length mismatch: got {a.shape[0]}, expected {tr.shape[0]}")
-    src = _c(row_source_indices, np.int64).ravel()
-    if src.size == 0:
-        raise RuntimeError("row_source_indices must not be empty.")
-    if (src < 0).any():
-        raise RuntimeError("row_source_indices must be non-negative.")
-    flip = np.asarray(row_flip).astype(bool).ravel()
-    maf = _c(row_maf, np.float32).ravel()
-    if flip.shape[0] != src.shape[0] or maf.shape[0] != src.shape[0]:
-        raise RuntimeError(f"metadata length mismatch: row_source_indices={src.shape[0]}, row_flip={flip.shape[0]}, "
-                           f"row_maf={maf.shape[0]}")
+    src, flip, maf = _gs_meta_rows(row_source_indices, row_flip, row_maf, "row_source_indices must not be empty.")
     if tr.size == 0:
         raise RuntimeError("compute_effect_beta_from_meta_stream: sample_idx must not be empty")
     if int(src.max()) >= int(packed.shape[0]):
@@ -4003,14 +4140,7 @@ def gblup_reml_packed_bed(prefix, train_sample_indices, y_train, test_sample_ind
     from . import pipeline as pl
     from . import stats as st
     from .bed import read_bed_payload
-    if not (math.isfinite(g_eps) and g_eps >= 0.0):
-        raise RuntimeError("g_eps must be finite and >= 0")
-    if not (math.isfinite(low) and math.isfinite(high) and low < high):
-        raise RuntimeError("low/high must be finite and low < high")
-    if int(max_iter) == 0:
-        raise RuntimeError("max_iter must be > 0")
-    if not (math.isfinite(tol) and tol > 0.0):
-        raise RuntimeError("tol must be finite and > 0")
+    _gs_check_reml_opts(g_eps, low, high, max_iter, tol)
     packed_loaded = None
     if row_source_indices is None or row_flip is None or row_maf is None:
         # `site_keep` route (gblup.rs:1986-2140): the whole payload (or the rows of the mask) with the loader's own row
@@ -4025,27 +4155,10 @@ def gblup_reml_packed_bed(prefix, train_sample_indices, y_train, test_sample_ind
         if m_total == 0:
             raise RuntimeError("No SNP rows found in BED input.")
         flip_all = bed_packed_row_flip_mask(packed_loaded, n_loaded)
-        if site_keep is not None:
-            mask = np.asarray(site_keep).astype(bool).ravel()
-            if mask.shape[0] != m_total:
-                raise RuntimeError(f"site_keep length mismatch: got {mask.shape[0]}, expected {m_total}")
-            row_source_indices = np.nonzero(mask)[0].astype(np.int64)
-            if row_source_indices.size == 0:
-                raise RuntimeError("No SNPs remained after applying site_keep mask.")
-        else:
-            row_source_indices = np.arange(m_total, dtype=np.int64)
-        row_flip = np.asarray(flip_all)[row_source_indices]
-        row_maf = np.asarray(maf_all, dtype=np.float32)[row_source_indices]
-    src = np.asarray(row_source_indices, dtype=np.int64).ravel()
-    if src.size == 0:
-        raise RuntimeError("row_source_indices must not be empty for metadata streaming path.")
-    if (src < 0).any():
-        raise RuntimeError("row_source_indices must be non-negative.")
-    flip = np.asarray(row_flip).astype(bool).ravel()
-    maf = _c(row_maf, np.float32).ravel()
-    if flip.shape[0] != src.shape[0] or maf.shape[0] != src.shape[0]:
-        raise RuntimeError(f"metadata length mismatch: row_source_indices={src.shape[0]}, row_flip={flip.shape[0]}, "
-                           f"row_maf={maf.shape[0]}")
+        rows, row_maf, row_flip = _gs_kept_rows(m_total, maf_all, flip_all, site_keep)
+        row_source_indices = np.arange(m_total, dtype=np.int64) if rows is None else rows
+    src, flip, maf = _gs_meta_rows(row_source_indices, row_flip, row_maf,
+                                   "row_source_indices must not be empty for metadata streaming path.")
     if packed_loaded is not None:
         packed, n_samples = packed_loaded, int(n_loaded)
     else:
@@ -4054,19 +4167,8 @@ def gblup_reml_packed_bed(prefix, train_sample_indices, y_train, test_sample_ind
         raise RuntimeError("No samples found in BED input.")
     if src.max() >= packed.shape[0]:
         raise RuntimeError("row_source_indices out of range")
-    tr = _c(train_sample_indices, np.int64).ravel()
-    if tr.size == 0:
-        raise RuntimeError("train_sample_indices must not be empty.")
-    if tr.min() < 0 or tr.max() >= n_samples:
-        raise RuntimeError("train_sample_indices out of range")
-    y = _c(y_train, np.float64).ravel()
-    if y.shape[0] != tr.shape[0]:
-        raise RuntimeError(f"y_train length mismatch: got {y.shape[0]}, expected {tr.shape[0]}")
-    if not np.all(np.isfinite(y)):
-        raise RuntimeError("y_train contains non-finite values.")
-    te = np.zeros(0, dtype=np.int64) if test_sample_indices is None else _c(test_sample_indices, np.int64).ravel()
-    if te.size and (te.min() < 0 or te.max() >= n_samples):
-        raise RuntimeError("test_sample_indices out of range")
+    tr, y = _gs_train_y(train_sample_indices, y_train, n_samples)
+    te = _gs_test_idx(test_sample_indices, n_samples)
     n_tr = int(tr.shape[0])
     if n_tr <= 1:
         raise RuntimeError("GBLUP REML requires at least 2 training samples.")
@@ -4214,38 +4316,13 @@ def rrblup_pcg_bed(prefix, train_sample_indices, y_train, test_sample_indices=No
     k_trace_mean, beta f32 (m)).  `block_rows`, `threads`, `blas_threads` are accepted and ignored; the streaming-stats
     form (maf/row_flip with a prefix and no payload) loads the payload from the prefix."""
     import math
-    if int(max_iter) == 0:
-        raise RuntimeError("max_iter must be > 0")
-    if not (math.isfinite(tol) and tol > 0.0):
-        raise RuntimeError("tol must be finite and > 0")
-    if not (math.isfinite(std_eps) and std_eps > 0.0):
-        raise RuntimeError("std_eps must be finite and > 0")
+    from . import stats as st
+    _gs_check_iter_opts(max_iter, tol, std_eps)
     if (not math.isfinite(lambda_value)) or lambda_value < 0.0:
         raise RuntimeError("lambda_value must be finite and >= 0")
     f32 = np.float32
-    if packed is not None:
-        if maf is None:
-            raise RuntimeError("rrblup_pcg_bed: packed payload path requires `maf` argument.")
-        if row_flip is None:
-            raise RuntimeError("rrblup_pcg_bed: packed payload path requires `row_flip` argument.")
-        if int(packed_n_samples) == 0:
-            raise RuntimeError("rrblup_pcg_bed: packed payload path requires packed_n_samples > 0.")
-        n_samples = int(packed_n_samples)
-        if _is_device_tensor(packed):        # a payload that already lives in HBM is used in place (no host copy of 50 GB)
-            if packed.dim() != 2:
-                raise RuntimeError("packed BED payload must be 2D (m, bytes_per_snp).")
-            pk = packed.contiguous()
-        else:
-            pk = _c(packed, np.uint8)
-            if pk.ndim != 2:
-                raise RuntimeError("packed BED payload must be 2D (m, bytes_per_snp).")
-    elif maf is not None or row_flip is not None or int(packed_n_samples) > 0:
-        if maf is None:
-            raise RuntimeError("rrblup_pcg_bed: streaming stats path requires `maf` argument.")
-        if row_flip is None:
-            raise RuntimeError("rrblup_pcg_bed: streaming stats path requires `row_flip` argument.")
-        if int(packed_n_samples) == 0:
-            raise RuntimeError("rrblup_pcg_bed: streaming stats path requires packed_n_samples > 0.")
+    if packed is None and (maf is not None or row_flip is not None or int(packed_n_samples) > 0):
+        _gs_require_stats("rrblup_pcg_bed", "streaming stats", maf, row_flip, packed_n_samples)
         if not str(prefix).strip():
             raise RuntimeError("rrblup_pcg_bed: streaming stats path requires non-empty prefix.")
         from .bed import read_bed_payload
@@ -4254,84 +4331,20 @@ def rrblup_pcg_bed(prefix, train_sample_indices, y_train, test_sample_indices=No
         if n_file != n_samples:
             raise RuntimeError(f"packed_n_samples mismatch: got {n_samples}, BED has {n_file}")
     else:
-        pk, _miss, maf, _std, n_samples = load_bed_2bit_packed(prefix)
-        row_flip = bed_packed_row_flip_mask(pk, n_samples)
+        pk, n_samples, maf, row_flip = _gs_payload("rrblup_pcg_bed", prefix, packed, packed_n_samples, maf, row_flip)
+    _gs_check_payload_shape(pk, n_samples)
     m_total = int(pk.shape[0])
-    if m_total == 0:
-        raise RuntimeError("No SNP rows found in BED input.")
-    if pk.shape[1] != (n_samples + 3) // 4:
-        raise RuntimeError(f"packed second dimension mismatch: got {pk.shape[1]}, expected {(n_samples + 3) // 4}")
-    maf_full = _c(maf, f32).ravel()
-    if maf_full.shape[0] != m_total:
-        raise RuntimeError(f"maf length mismatch: got {maf_full.shape[0]}, expected {m_total}")
-    flip_full = np.asarray(row_flip).astype(bool).ravel()
-    if flip_full.shape[0] != m_total:
-        raise RuntimeError(f"row_flip length mismatch: got {flip_full.shape[0]}, expected {m_total}")
-    rows = None
-    maf_keep, flip_keep = maf_full, flip_full
-    if site_keep is not None:
-        mask = np.asarray(site_keep).astype(bool).ravel()
-        if mask.shape[0] != m_total:
-            raise RuntimeError(f"site_keep length mismatch: got {mask.shape[0]}, expected {m_total}")
-        keep_idx = np.nonzero(mask)[0].astype(np.int64)
-        if keep_idx.shape[0] == 0:
-            raise RuntimeError("No SNPs remained after applying site_keep mask.")
-        if keep_idx.shape[0] != m_total:
-            rows = keep_idx
-            maf_keep = np.clip(maf_full[keep_idx], f32(0.0), f32(0.5)).astype(f32)
-            flip_keep = flip_full[keep_idx]
+    rows, maf_keep, flip_keep = _gs_kept_rows(m_total, maf, row_flip, site_keep)
     eff_m = int(maf_keep.shape[0])
-    tr = _c(train_sample_indices, np.int64).ravel()
-    if tr.size == 0:
-        raise RuntimeError("train_sample_indices must not be empty.")
-    if tr.min() < 0 or tr.max() >= n_samples:
-        raise RuntimeError("train_sample_indices out of range")
-    y = _c(y_train, np.float64).ravel()
-    if y.shape[0] != tr.shape[0]:
-        raise RuntimeError(f"y_train length mismatch: got {y.shape[0]}, expected {tr.shape[0]}")
-    if not np.all(np.isfinite(y)):
-        raise RuntimeError("y_train contains non-finite values.")
-    te = np.zeros(0, dtype=np.int64) if test_sample_indices is None else _c(test_sample_indices, np.int64).ravel()
-    if te.size and (te.min() < 0 or te.max() >= n_samples):
-        raise RuntimeError("test_sample_indices out of range")
-    pick = None
-    if train_pred_local_indices is not None:
-        pick = _c(train_pred_local_indices, np.int64).ravel()
-        if pick.size and (pick.min() < 0 or pick.max() >= tr.shape[0]):
-            raise RuntimeError("train_pred_local_indices out of range")
+    tr, y = _gs_train_y(train_sample_indices, y_train, n_samples)
+    te = _gs_test_idx(test_sample_indices, n_samples)
     n_train = int(tr.shape[0])
+    pick = _gs_pick_idx(train_pred_local_indices, n_train)
     lambda_use = f32(max(float(lambda_value), 1e-8))
-    std_eps32 = f32(max(float(std_eps), 1e-12))
-    # row standardisation (`rrblup_subset_or_validate_stats`, rrblup.rs:568-625)
-    if (row_mean is None) != (row_inv_sd is None):
-        raise RuntimeError("rrBLUP standardization requires row_mean and row_inv_sd together when overriding row stats.")
-    if row_mean is not None:
-        rm = _c(row_mean, f32).ravel()
-        ri = _c(row_inv_sd, f32).ravel()
-        if rm.shape[0] == eff_m and ri.shape[0] == eff_m:
-            pass
-        elif rm.shape[0] == m_total and ri.shape[0] == m_total and rows is not None:
-            rm, ri = rm[rows], ri[rows]
-        else:
-            raise RuntimeError(f"External row_mean/row_inv_sd length mismatch: mean={rm.shape[0]}, inv={ri.shape[0]}, "
-                               f"expected active={eff_m} or full={m_total}.")
-        m_effective = int(np.count_nonzero(np.isfinite(ri) & (ri > 0)))
-        if m_effective == 0:
-            raise RuntimeError("rrBLUP standardization received zero effective markers from external row_inv_sd.")
-    else:
-        pq = np.clip(maf_keep, f32(0.0), f32(0.5)).astype(f32)
-        rm = (f32(2.0) * pq).astype(f32)
-        var = np.maximum((f32(2.0) * pq * (f32(1.0) - pq)).astype(f32), f32(0.0))
-        good = var > std_eps32
-        ri = np.zeros_like(var)
-        ri[good] = (f32(1.0) / np.sqrt(var[good])).astype(f32)
-        m_effective = int(np.count_nonzero(good))
-    g0 = np.where(flip_keep, f32(2.0), f32(0.0)).astype(f32)
-    g2 = np.where(flip_keep, f32(0.0), f32(2.0)).astype(f32)
-    lut = np.zeros((eff_m, 4), dtype=f32)
-    lut[:, 0] = (g0 - rm) * ri
-    lut[:, 2] = (f32(1.0) - rm) * ri
-    lut[:, 3] = (g2 - rm) * ri
+    rm, ri, m_effective = _rrblup_row_stats(maf_keep, rows, m_total, row_mean, row_inv_sd, std_eps)
+    if row_mean is not None and m_effective == 0:
+        raise RuntimeError("rrBLUP standardization received zero effective markers from external row_inv_sd.")
+    lut = st.grm_lut_from_mean_scale(rm, ri, flip_keep)
     need_all = pick is None
     need_train = need_all or bool(compute_trainvar) or (pick is not None and pick.size > 0)
     beta = np.zeros(eff_m, dtype=f32)
@@ -4340,6 +4353,7 @@ def rrblup_pcg_bed(prefix, train_sample_indices, y_train, test_sample_indices=No
     sc = np.zeros(8, dtype=np.float64)
     from .dist import distributed_pcg, shard_range
     shard = distributed_pcg()
+    pk_s, rows_s, lut_s, beta_s = pk, rows, lut, beta          # what this process solves: every kept row, or its shard of them
     if shard is not None:
         # marker-sharded solve (dist.enable_distributed_pcg): this rank's contiguous range of the kept rows; the device layer
         # all-reduces Z'p and the iteration's scalars, beta is gathered in rank (= row) order afterwards
@@ -4356,12 +4370,12 @@ def rrblup_pcg_bed(prefix, train_sample_indices, y_train, test_sample_indices=No
             pk_s = pk[torch.from_numpy(rows_all[lo:hi]).to(pk.device)].contiguous() if rows is not None else pk[lo:hi]
         else:
             pk_s = np.ascontiguousarray(pk[rows_all[lo:hi]])
-        lut_s = np.ascontiguousarray(lut[lo:hi])
-        beta_s = np.zeros(hi - lo, dtype=f32)
-        check(lib().jx_rrblup_pcg_packed(_payload(pk_s, n_samples)[1], hi - lo, n_samples, None, hi - lo, _p(lut_s), _p(tr), n_train, _p(y),
-                                         _p(te) if te.size else None, int(te.shape[0]), float(lambda_value), float(tol),
-                                         int(max_iter), _p(beta_s), _p(pred_tr_full), _p(pred_te) if te.size else None,
-                                         _p(sc)))
+        rows_s, lut_s, beta_s = None, np.ascontiguousarray(lut[lo:hi]), np.zeros(hi - lo, dtype=f32)
+    check(lib().jx_rrblup_pcg_packed(_payload(pk_s, n_samples)[1], int(pk_s.shape[0]), n_samples, _p(rows_s), int(beta_s.shape[0]),
+                                     _p(lut_s), _p(tr), n_train, _p(y), _p(te) if te.size else None, int(te.shape[0]),
+                                     float(lambda_value), float(tol), int(max_iter), _p(beta_s), _p(pred_tr_full),
+                                     _p(pred_te) if te.size else None, _p(sc)))
+    if shard is not None:
         sizes = [shard_range(eff_m, r, world) for r in range(world)]
         width = max(b - a for a, b in sizes)
         pad = torch.zeros(width, dtype=torch.float32)
@@ -4376,11 +4390,6 @@ def rrblup_pcg_bed(prefix, train_sample_indices, y_train, test_sample_indices=No
             tdist.all_gather(parts, pad)
         for (a, b), t in zip(sizes, parts):
             beta[a:b] = t[: b - a].numpy()
-    else:
-        check(lib().jx_rrblup_pcg_packed(_payload(pk, n_samples)[1], m_total, n_samples, _p(rows), eff_m, _p(lut), _p(tr), n_train, _p(y),
-                                         _p(te) if te.size else None, int(te.shape[0]), float(lambda_value), float(tol),
-                                         int(max_iter), _p(beta), _p(pred_tr_full), _p(pred_te) if te.size else None,
-                                         _p(sc)))
     converged, iters, rel_res, sum_ss = bool(sc[0] != 0.0), int(sc[1]), float(sc[2]), float(sc[3])
     if progress_callback is not None:
         try:
@@ -4422,6 +4431,7 @@ def rrblup_exact_snp_packed(packed, n_samples, train_sample_indices, y_train, te
     beta f32 (m), row_mean f32 (m), row_inv_sd f32 (m), eigensolver name).  `sample_block`, `threads`, `blas_threads` are
     accepted and ignored."""
     import math
+    from . import stats as st
     n_samples = int(n_samples)
     if n_samples == 0:
         raise RuntimeError("n_samples must be > 0")
@@ -4444,78 +4454,19 @@ def rrblup_exact_snp_packed(packed, n_samples, train_sample_indices, y_train, te
         raise RuntimeError("rrblup_exact_snp_packed requires `maf` argument.")
     if row_flip is None:
         raise RuntimeError("rrblup_exact_snp_packed requires `row_flip` argument.")
-    maf_full = _c(maf, f32).ravel()
-    if maf_full.shape[0] != m_total:
-        raise RuntimeError(f"maf length mismatch: got {maf_full.shape[0]}, expected {m_total}")
-    flip_full = np.asarray(row_flip).astype(bool).ravel()
-    if flip_full.shape[0] != m_total:
-        raise RuntimeError(f"row_flip length mismatch: got {flip_full.shape[0]}, expected {m_total}")
-    rows = None
-    maf_keep, flip_keep = maf_full, flip_full
-    if site_keep is not None:
-        mask = np.asarray(site_keep).astype(bool).ravel()
-        if mask.shape[0] != m_total:
-            raise RuntimeError(f"site_keep length mismatch: got {mask.shape[0]}, expected {m_total}")
-        keep_idx = np.nonzero(mask)[0].astype(np.int64)
-        if keep_idx.shape[0] == 0:
-            raise RuntimeError("No SNPs remained after applying site_keep mask.")
-        if keep_idx.shape[0] != m_total:
-            rows = keep_idx
-            maf_keep = np.clip(maf_full[keep_idx], f32(0.0), f32(0.5)).astype(f32)
-            flip_keep = flip_full[keep_idx]
+    rows, maf_keep, flip_keep = _gs_kept_rows(m_total, maf, row_flip, site_keep)
     eff_m = int(maf_keep.shape[0])
     if eff_m == 0:
         raise RuntimeError("rrblup_exact_snp_packed received zero active markers.")
-    tr = _c(train_sample_indices, np.int64).ravel()
-    if tr.size and (tr.min() < 0 or tr.max() >= n_samples):
-        raise RuntimeError("train_sample_indices out of range")
+    tr, y = _gs_train_y(train_sample_indices, y_train, n_samples, 2,
+                        "rrblup_exact_snp_packed requires at least two training samples.")
     n_train = int(tr.shape[0])
-    if n_train <= 1:
-        raise RuntimeError("rrblup_exact_snp_packed requires at least two training samples.")
-    y = _c(y_train, np.float64).ravel()
-    if y.shape[0] != n_train:
-        raise RuntimeError(f"y_train length mismatch: got {y.shape[0]}, expected {n_train}")
-    if not np.all(np.isfinite(y)):
-        raise RuntimeError("y_train contains non-finite values.")
-    te = np.zeros(0, dtype=np.int64) if test_sample_indices is None else _c(test_sample_indices, np.int64).ravel()
-    if te.size and (te.min() < 0 or te.max() >= n_samples):
-        raise RuntimeError("test_sample_indices out of range")
-    pick = None
-    if train_pred_local_indices is not None:
-        pick = _c(train_pred_local_indices, np.int64).ravel()
-        if pick.size and (pick.min() < 0 or pick.max() >= n_train):
-            raise RuntimeError("train_pred_local_indices out of range")
-    std_eps32 = f32(max(float(std_eps), 1e-12))
-    # row standardisation (`rrblup_subset_or_validate_stats`, rrblup.rs:568-625)
-    if (row_mean is None) != (row_inv_sd is None):
-        raise RuntimeError("rrBLUP standardization requires row_mean and row_inv_sd together when overriding row stats.")
-    if row_mean is not None:
-        rm = _c(row_mean, f32).ravel()
-        ri = _c(row_inv_sd, f32).ravel()
-        if rm.shape[0] == eff_m and ri.shape[0] == eff_m:
-            pass
-        elif rm.shape[0] == m_total and ri.shape[0] == m_total and rows is not None:
-            rm, ri = rm[rows], ri[rows]
-        else:
-            raise RuntimeError(f"External row_mean/row_inv_sd length mismatch: mean={rm.shape[0]}, inv={ri.shape[0]}, "
-                               f"expected active={eff_m} or full={m_total}.")
-        m_effective = int(np.count_nonzero(np.isfinite(ri) & (ri > 0)))
-    else:
-        pq = np.clip(maf_keep, f32(0.0), f32(0.5)).astype(f32)
-        rm = (f32(2.0) * pq).astype(f32)
-        var = np.maximum((f32(2.0) * pq * (f32(1.0) - pq)).astype(f32), f32(0.0))
-        good = var > std_eps32
-        ri = np.zeros_like(var)
-        ri[good] = (f32(1.0) / np.sqrt(var[good])).astype(f32)
-        m_effective = int(np.count_nonzero(good))
+    te = _gs_test_idx(test_sample_indices, n_samples)
+    pick = _gs_pick_idx(train_pred_local_indices, n_train)
+    rm, ri, m_effective = _rrblup_row_stats(maf_keep, rows, m_total, row_mean, row_inv_sd, std_eps)
     if m_effective == 0:
         raise RuntimeError("rrblup_exact_snp_packed found zero effective markers after standardization.")
-    g0 = np.where(flip_keep, f32(2.0), f32(0.0)).astype(f32)
-    g2 = np.where(flip_keep, f32(0.0), f32(2.0)).astype(f32)
-    lut = np.zeros((eff_m, 4), dtype=f32)
-    lut[:, 0] = (g0 - rm) * ri
-    lut[:, 2] = (f32(1.0) - rm) * ri
-    lut[:, 3] = (g2 - rm) * ri
+    lut = st.grm_lut_from_mean_scale(rm, ri, flip_keep)
     beta = np.zeros(eff_m, dtype=f32)
     need_train = pick is None or pick.size > 0
     pred_tr_full = np.zeros(n_train, dtype=np.float64) if need_train else None
@@ -4593,17 +4544,13 @@ def he_pcg_bed(prefix, train_sample_indices, y_train, site_keep=None, trace_samp
     sigma_e2, h2, converged, iters, rel_res, m_effective, tr_k2, y_ky, y_y, lambda, tr_k2_solve).  The packed-payload
     form and the prefix form are built (the metadata-streaming form maps onto them: rows = row_source_indices)."""
     import math
+    from . import stats as st
     f32 = np.float32
     if int(trace_samples) == 0:
         raise RuntimeError("trace_samples must be > 0")
     if int(trace_probe_batch) == 0:
         raise RuntimeError("trace_probe_batch must be > 0")
-    if int(max_iter) == 0:
-        raise RuntimeError("max_iter must be > 0")
-    if not (math.isfinite(tol) and tol > 0.0):
-        raise RuntimeError("tol must be finite and > 0")
-    if not (math.isfinite(std_eps) and std_eps > 0.0):
-        raise RuntimeError("std_eps must be finite and > 0")
+    _gs_check_iter_opts(max_iter, tol, std_eps)
     ext = packed is not None or int(packed_n_samples) > 0
     meta = row_source_indices is not None
     if ext and meta:
@@ -4612,26 +4559,7 @@ def he_pcg_bed(prefix, train_sample_indices, y_train, site_keep=None, trace_samp
     if (not ext) and (not meta) and (maf is not None or row_flip is not None):
         raise RuntimeError("he_pcg_bed: external maf/row_flip without packed payload requires row_source_indices for "
                            "metadata streaming.")
-    rows = None
-    if ext:
-        if packed is None:
-            raise RuntimeError("he_pcg_bed: packed payload path requires `packed` argument.")
-        if maf is None:
-            raise RuntimeError("he_pcg_bed: packed payload path requires `maf` argument.")
-        if row_flip is None:
-            raise RuntimeError("he_pcg_bed: packed payload path requires `row_flip` argument.")
-        if int(packed_n_samples) == 0:
-            raise RuntimeError("he_pcg_bed: packed payload path requires packed_n_samples > 0.")
-        n_samples = int(packed_n_samples)
-        if _is_device_tensor(packed):        # a payload that already lives in HBM is used in place
-            if packed.dim() != 2:
-                raise RuntimeError("packed BED payload must be 2D (m, bytes_per_snp).")
-            pk = packed.contiguous()
-        else:
-            pk = _c(packed, np.uint8)
-            if pk.ndim != 2:
-                raise RuntimeError("packed BED payload must be 2D (m, bytes_per_snp).")
-    elif meta:
+    if meta:
         if site_keep is not None:
             raise RuntimeError("he_pcg_bed: metadata streaming path does not accept site_keep; subset rows via "
                                "row_source_indices instead.")
@@ -4647,48 +4575,19 @@ def he_pcg_bed(prefix, train_sample_indices, y_train, site_keep=None, trace_samp
         if rows.min() < 0:
             raise RuntimeError("row_source_indices must be non-negative.")
     else:
-        pk, _miss, maf, _std, n_samples = load_bed_2bit_packed(prefix)
-        row_flip = bed_packed_row_flip_mask(pk, n_samples)
+        pk, n_samples, maf, row_flip = _gs_payload("he_pcg_bed", prefix, packed, packed_n_samples, maf, row_flip)
+    _gs_check_payload_shape(pk, n_samples)
     m_total = int(pk.shape[0])
-    if m_total == 0:
-        raise RuntimeError("No SNP rows found in BED input.")
-    if pk.shape[1] != (n_samples + 3) // 4:
-        raise RuntimeError(f"packed second dimension mismatch: got {pk.shape[1]}, expected {(n_samples + 3) // 4}")
-    maf_in = _c(maf, f32).ravel()
-    flip_in = np.asarray(row_flip).astype(bool).ravel()
     if meta:
-        if maf_in.shape[0] != rows.shape[0] or flip_in.shape[0] != rows.shape[0]:
+        maf_keep, flip_keep = _c(maf, f32).ravel(), np.asarray(row_flip).astype(bool).ravel()
+        if maf_keep.shape[0] != rows.shape[0] or flip_keep.shape[0] != rows.shape[0]:
             raise RuntimeError("metadata length mismatch between row_source_indices, maf and row_flip")
         if rows.max() >= m_total:
             raise RuntimeError("row source index out of bounds")
-        maf_keep, flip_keep = maf_in, flip_in
     else:
-        if maf_in.shape[0] != m_total:
-            raise RuntimeError(f"maf length mismatch: got {maf_in.shape[0]}, expected {m_total}")
-        if flip_in.shape[0] != m_total:
-            raise RuntimeError(f"row_flip length mismatch: got {flip_in.shape[0]}, expected {m_total}")
-        maf_keep, flip_keep = maf_in, flip_in
-        if site_keep is not None:
-            mask = np.asarray(site_keep).astype(bool).ravel()
-            if mask.shape[0] != m_total:
-                raise RuntimeError(f"site_keep length mismatch: got {mask.shape[0]}, expected {m_total}")
-            keep_idx = np.nonzero(mask)[0].astype(np.int64)
-            if keep_idx.shape[0] == 0:
-                raise RuntimeError("No SNPs remained after applying site_keep mask.")
-            if keep_idx.shape[0] != m_total:
-                rows = keep_idx
-                maf_keep, flip_keep = maf_in[keep_idx], flip_in[keep_idx]
+        rows, maf_keep, flip_keep = _gs_kept_rows(m_total, maf, row_flip, site_keep)
     eff_m = int(maf_keep.shape[0])
-    tr = _c(train_sample_indices, np.int64).ravel()
-    if tr.size == 0:
-        raise RuntimeError("train_sample_indices must not be empty.")
-    if tr.min() < 0 or tr.max() >= n_samples:
-        raise RuntimeError("train_sample_indices out of range")
-    y = _c(y_train, np.float64).ravel()
-    if y.shape[0] != tr.shape[0]:
-        raise RuntimeError(f"y_train length mismatch: got {y.shape[0]}, expected {tr.shape[0]}")
-    if not np.all(np.isfinite(y)):
-        raise RuntimeError("y_train contains non-finite values.")
+    tr, y = _gs_train_y(train_sample_indices, y_train, n_samples)
     n = int(tr.shape[0])
     xc, p_cov = None, 0
     if x_cov is not None:
@@ -4726,21 +4625,10 @@ def he_pcg_bed(prefix, train_sample_indices, y_train, site_keep=None, trace_samp
         pt = np.zeros_like(pfr)
         pt[okc] = dos[okc].astype(f32) / (f32(2.0) * nm[okc].astype(f32))
         pfr = np.where(okc, pt, pfr).astype(f32)
-    pfr = np.clip(pfr, f32(0.0), f32(1.0))
-    rm = (f32(2.0) * pfr).astype(f32)
-    var = np.maximum((f32(2.0) * pfr * (f32(1.0) - pfr)).astype(f32), f32(0.0))
-    good = var > f32(max(float(std_eps), 1e-12))
-    ri = np.zeros_like(var)
-    ri[good] = (f32(1.0) / np.sqrt(var[good])).astype(f32)
-    m_effective = int(np.count_nonzero(good))
+    rm, ri, m_effective = _gs_standardise(np.clip(pfr, f32(0.0), f32(1.0)), std_eps)
     if m_effective == 0:
         raise RuntimeError("No effective SNPs after std_eps filtering")
-    g0 = np.where(flip_keep, f32(2.0), f32(0.0)).astype(f32)
-    g2 = np.where(flip_keep, f32(0.0), f32(2.0)).astype(f32)
-    lut = np.zeros((eff_m, 4), dtype=f32)
-    lut[:, 0] = (g0 - rm) * ri
-    lut[:, 2] = (f32(1.0) - rm) * ri
-    lut[:, 3] = (g2 - rm) * ri
+    lut = st.grm_lut_from_mean_scale(rm, ri, flip_keep)
     exact = bool(exact_trace_debug) and n <= max(int(exact_trace_max_n), 1)
     out5 = np.zeros(5, dtype=np.float64)
     check(lib().jx_he_traces_packed(_payload(pk, n_samples)[1], m_total, n_samples, _p(rows), eff_m, _p(lut), _p(tr), n, _p(y), _p(xc), p_cov,

@@ -2012,6 +2012,38 @@ def test_rrblup_pcg_bed(oracle, tmp_path, subset):
 
 
 @pytest.mark.gpu
+def test_gs_front_host_and_device_payload_agree(oracle):
+    """The shared argument front end of `rrblup_pcg_bed` / `he_pcg_bed` on its device-tensor branches (the payload used in
+    place, the row gather for the training samples' own frequencies): the same call with the payload as a numpy array and as a
+    CUDA uint8 tensor, under a `site_keep` that drops the first row, the last row and a few in between.  Both forms hand the
+    kernels the same bytes, so the returned tuples are identical bit for bit."""
+    import torch
+    from janusx_amd import janusx as jxrs
+    n, m = 70, 96
+    packed, g = bed.synth_panel_numpy(n, m, seed=19, missing_rate=0.02)
+    _miss, maf, _std, flip = oracle.load_bed_2bit_packed_stats(packed, n)
+    rng = np.random.default_rng(4)
+    perm = rng.permutation(n)
+    tr, te = np.sort(perm[:50]).astype(np.int64), np.sort(perm[50:]).astype(np.int64)
+    y = g[:10, tr].astype(np.float64).T @ rng.standard_normal(10) * 0.4 + rng.standard_normal(50)
+    keep = np.ones(m, dtype=bool)
+    keep[[0, 7, 8, 40, 63, 64, m - 1]] = False
+    pk_dev = torch.from_numpy(packed).cuda()
+
+    def same(a, b):
+        return len(a) == len(b) and all(np.asarray(u).dtype == np.asarray(v).dtype and
+                                        np.asarray(u).tobytes() == np.asarray(v).tobytes() for u, v in zip(a, b))
+    got = [jxrs.rrblup_pcg_bed("", tr, y, te, None, keep, lambda_value=30.0, tol=1e-7, max_iter=300, packed=pk,
+                               packed_n_samples=n, maf=maf, row_flip=flip) for pk in (packed, pk_dev)]
+    assert got[0][3] and got[0][6] > 0 and got[0][9].shape == (int(keep.sum()),) and got[0][1].shape == (20, 1)
+    assert same(got[0], got[1])
+    got = [jxrs.he_pcg_bed("", tr, y, site_keep=keep, packed=pk, packed_n_samples=n, maf=maf, row_flip=flip)
+           for pk in (packed, pk_dev)]
+    assert len(got[0]) == 12 and got[0][6] > 0
+    assert same(got[0], got[1])
+
+
+@pytest.mark.gpu
 def test_cli_gs_rrblup(oracle, tmp_path):
     """`jx gs -rrBLUP -lambda L -cv 2`: PCG marker effects on the phenotyped samples, predictions for the rest, against
     the restatement of `rrblup_pcg_bed` on the same kept-SNP mask; and the subsample-REML lambda runs end to end."""
