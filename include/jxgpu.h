@@ -508,6 +508,27 @@ int jxg_admx_em_step(const uint8_t *d_p32, int64_t m_total, int n, const int32_t
 int jxg_admx_loglik(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip, int k,
                     const float *d_p, const float *d_q, void *d_work, int64_t work_bytes, double *d_out, void *stream);
 
+/* Cross-validation error of `jx adamixture -cverror` (csrc/k_admx_cv.hip; `cv_fold_hash64`, src/stats/adamixture.rs:1641-1661).
+ * The called genotype of listed row j (its position in d_rows, NULL = 0 .. nrows - 1) and sample i < n belongs to fold
+ * splitmix(j n + i; seed) mod folds, 2 <= folds <= JXG_ADMX_CV_MAX_FOLDS; missing calls and padding samples to none.
+ *   jxg_admx_cv_fold_counts: d_counts (folds) = called genotypes per fold over the rows (integer atomics);
+ *   jxg_admx_cv_fold_image : d_out_p32 = compact P32 image (tiles, nrows, 32 bytes) of the rows in list order with the called
+ *                            genotypes of fold_id turned into code 01, everything else copied; d_row_stats (nrows, 3) = training
+ *                            calls, held-out calls, minor-allele sum of the training calls after the flip d_flip;
+ *   jxg_admx_cv_holdout_nll: over the FULL image, for the called genotypes g of fold_id: rec = f32 dot product of P_j and Q_i in
+ *                            k order, clamped in f64 to [1e-8, 1 - 1e-8]; d_ll[0] = sum [g == 1] ln 2 + g ln rec + (2 - g)
+ *                            ln(1 - rec) (f64, partials added in a fixed order), d_n_eval[0] = their number.  d_work holds
+ *                            JXG_ADMX_CV_WORK_BYTES. */
+#define JXG_ADMX_CV_MAX_FOLDS 256
+#define JXG_ADMX_CV_WORK_BYTES 32768
+int jxg_admx_cv_fold_counts(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, int folds, uint64_t seed,
+                            int64_t *d_counts, void *stream);
+int jxg_admx_cv_fold_image(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip,
+                           int folds, uint64_t seed, int fold_id, uint8_t *d_out_p32, int32_t *d_row_stats, void *stream);
+int jxg_admx_cv_holdout_nll(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip,
+                            int folds, uint64_t seed, int fold_id, int k, const float *d_p, const float *d_q, void *d_work,
+                            int64_t work_bytes, double *d_ll, int64_t *d_n_eval, void *stream);
+
 /* SparseLMM exact scan on rotated rows (`exact_scan_blocks_core`, src/stats/splmm.rs:2567-2880, with V = K + lambda I
  * handled spectrally): per row g~ = U'g the sums g~'Wg~, g~'(W X~), g~.(Py)~ of E2, then the score-form Wald test of
  * `splmm_wald_from_score_denom` (:2517-2538) with the NULL model's sigma2 = ypy / df (df = n - p): out (nrows, 3) =

@@ -104,6 +104,9 @@ SIGNATURES = {
     "jxg_admx_em_step": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p,
                          c_f, c_f, c_f, c_f, c_f, c_f, c_p],
     "jxg_admx_loglik": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_l, c_p, c_p],
+    "jxg_admx_cv_fold_counts": [c_p, c_l, c_i, c_p, c_i, c_i, C.c_uint64, c_p, c_p],
+    "jxg_admx_cv_fold_image": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, C.c_uint64, c_i, c_p, c_p, c_p],
+    "jxg_admx_cv_holdout_nll": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, C.c_uint64, c_i, c_i, c_p, c_p, c_p, c_l, c_p, c_p, c_p],
     "jxg_packed_dot": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "jxg_cross_dot": [c_p, c_i, c_l, c_p, c_i, c_p, c_i, c_p, c_d, c_p, c_p],
     "jxg_splmm_exact_scan_dev": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_p, c_p],

@@ -14,7 +14,8 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
-                                 [-solver adam-em|adam|auto] [-max-iter 500] [-check 5] [-tol 1e-5] [-snps-only]  (fastpop: same)
+                                 [-solver adam-em|adam|auto] [-max-iter 500] [-check 5] [-tol 1e-5] [-snps-only] [-cverror [N]]
+                                 (fastpop: same)
   python -m janusx_amd gformat -bfile PREFIX -prune WINDOW STEP R2 [-o OUT | -o DIR/ -prefix NAME]   (LD pruning; WINDOW: 50, 500kb, 100bp)
   python -m janusx_amd gstats -bfile PREFIX [-freq] [-miss] [-het] [-ldsc [WINDOW]] [-o OUT | -o DIR/ -prefix NAME]
                                  (site / sample QC tables and LD scores; WINDOW: 100, 100kb, 0.1mb, 100000b, 10cm; bare -ldsc: 100kb)
@@ -1477,6 +1478,22 @@ ADMX_DEFAULTS = dict(power=5, max_als=1000, reg_als=1e-5, lr=0.005, beta1=0.80, 
                      min_lr=1e-6)     # python/janusx/script/adamixture.py (the CLI's fixed optimiser settings)
 
 
+ADMX_CV_MAX_FOLDS = 256    # janusx.ADMX_CV_MAX_FOLDS (the argument checks run before that module and torch are imported)
+CVERROR_COLUMNS = ("K", "CVerror", "CVerror_SE", "CV_folds", "WallTime_sec", "Q_output", "P_npy_output", "P_site_output",
+                   "Structure_plot", "Log_file")
+
+
+def write_cverror_summary_tsv(path, rows):
+    """`_write_cverror_summary_tsv` (python/janusx/script/adamixture.py:1096-1135): one line per K of dicts with k, cverror,
+    cverror_se, cv_folds, wall, q_out, p_npy_out, p_site_out, log_path; the Structure_plot column stays empty (no plots)."""
+    with open(path, "w", encoding="utf-8") as fh:
+        fh.write("\t".join(CVERROR_COLUMNS) + "\n")
+        for r in rows:
+            fh.write("\t".join([str(int(r["k"])), f"{float(r['cverror']):.6f}", f"{float(r['cverror_se']):.6f}",
+                                str(int(r["cv_folds"])), f"{float(r['wall']):.3f}", str(r["q_out"]), str(r["p_npy_out"]),
+                                str(r["p_site_out"]), "", str(r["log_path"])]) + "\n")
+
+
 def _k_range(tok, lo_s, hi_s, step_s):
     lo, hi = int(lo_s), int(hi_s)
     step = abs(int(step_s)) if step_s is not None else 1
@@ -1532,9 +1549,14 @@ def _admx_check_args(args):
     if not args.bfile:
         raise SystemExit(f"{cmd} needs -bfile PREFIX")
     if args.cv is not None and int(args.cv) >= 2:
-        raise SystemExit(f"{cmd}: -cv {args.cv} (cross-validation error) is not built; use -cv 0 or leave it out")
+        raise SystemExit(f"{cmd}: -cv {args.cv} is not accepted; the cross-validation error is spelled -cverror {args.cv} on this "
+                         "build (use -cv 0 or leave it out)")
     if args.cv is not None and int(args.cv) < 0:
         raise SystemExit("-cv must be >= 0.")
+    cve = getattr(args, "cverror", None)
+    if cve is not None and int(cve) != 0 and not 2 <= int(cve) <= ADMX_CV_MAX_FOLDS:
+        raise SystemExit(f"{cmd}: -cverror {cve} is out of range: 0 (off) or 2 <= folds <= {ADMX_CV_MAX_FOLDS} (the limit of this "
+                         "build)")
     if not (0.0 <= float(args.maf) <= 0.5):
         raise SystemExit("-maf must be within [0, 0.5].")
     if not (0.0 <= float(args.geno) <= 1.0):
@@ -1562,7 +1584,9 @@ def _admx_check_args(args):
 def cmd_adamixture(args):
     """`jx adamixture` / `jx fastpop` (python/janusx/script/adamixture.py; fastpop.py is the same command): ancestry estimation
     by ALS + Adam-EM on the kept rows of a PLINK prefix (`AdmxBedTrainingSession.fit_k`), every K of the -k spec on one staged
-    session.  Per K: {prefix}.{K}.Q.txt, .P.npy, .P.site, .fastpop.log; then {prefix}.fastpop.summary.log."""
+    session.  Per K: {prefix}.{K}.Q.txt, .P.npy, .P.site, .fastpop.log; then {prefix}.fastpop.summary.log.  With -cverror N every K
+    is followed by its N-fold cross-validation error (`admx_evaluate_cverror`), and {prefix}.fastpop.cverror.summary.tsv and the
+    K of the smallest error close the scan."""
     ks = _admx_check_args(args)
     from . import janusx as jxrs
     from .bed import read_fam_ids, stage_bed_payload
@@ -1577,14 +1601,23 @@ def cmd_adamixture(args):
     del payload
     t_stage = time.perf_counter() - t0
     summary = []
+    cv_folds = int(args.cverror or 0)
+    cv_rows = []
+    fit_settings = (args.solver, ADMX_DEFAULTS["power"], float(args.tol), ADMX_DEFAULTS["max_als"], ADMX_DEFAULTS["reg_als"],
+                    ADMX_DEFAULTS["lr"], ADMX_DEFAULTS["beta1"], ADMX_DEFAULTS["beta2"], ADMX_DEFAULTS["epsilon"],
+                    int(args.max_iter), int(args.check), ADMX_DEFAULTS["lr_decay"], ADMX_DEFAULTS["min_lr"])
     for idx, k in enumerate(ks, 1):
         t1 = time.perf_counter()
-        p, q, ll, it, init_ll, als_it = sess.fit_k(k, int(args.seed), args.solver, ADMX_DEFAULTS["power"], float(args.tol),
-                                                   ADMX_DEFAULTS["max_als"], ADMX_DEFAULTS["reg_als"], ADMX_DEFAULTS["lr"],
-                                                   ADMX_DEFAULTS["beta1"], ADMX_DEFAULTS["beta2"], ADMX_DEFAULTS["epsilon"],
-                                                   int(args.max_iter), int(args.check), ADMX_DEFAULTS["lr_decay"],
-                                                   ADMX_DEFAULTS["min_lr"])
+        p, q, ll, it, init_ll, als_it = sess.fit_k(k, int(args.seed), *fit_settings)
         dt = time.perf_counter() - t1
+        cv = None
+        if cv_folds:
+            t2 = time.perf_counter()
+            try:
+                cv = jxrs.admx_evaluate_cverror(sess, k, cv_folds, int(args.seed), *fit_settings)
+            except ValueError as e:
+                raise SystemExit(f"{args.cmd}: {e}") from None
+            dt_cv = time.perf_counter() - t2
         base = os.path.join(outdir, f"{prefix}.{k}")
         with open(f"{base}.Q.txt", "w") as fh:
             for sid, row in zip(ids, q.astype(np.float64)):
@@ -1601,16 +1634,38 @@ def cmd_adamixture(args):
             fh.write(f"ALS rounds: {als_it}  init log-likelihood: {init_ll:.6f}\n")
             fh.write(f"Adam-EM iterations: {it}  final log-likelihood: {ll:.6f}\n")
             fh.write(f"time: {dt:.3f} s (staging {t_stage:.3f} s, shared by the K scan)\n")
+            if cv is not None:
+                fh.write(f"CVerror: estimating from {cv_folds} folds (observed={cv['cv_observed']}, SNPs={sess.n_snps}, "
+                         f"samples={sess.n_samples})\n")
+                fh.write("CV fold sizes: " + ", ".join(f"F{i + 1}={int(c)}" for i, c in enumerate(cv["fold_counts"])) + "\n")
+                fh.write(f"CVerror: {cv['cverror']:.6f} (SE={cv['cverror_se']:.6f}, folds={cv_folds})\n")
+                fh.write("CV eval counts: " + ", ".join(f"F{i + 1}={int(c)}" for i, c in enumerate(cv["fold_eval_counts"])) + "\n")
+                fh.write(f"CV time: {dt_cv:.3f} s\n")
             fh.write("structure plot: not drawn (plots are not built)\n")
             fh.write(f"outputs: {base}.Q.txt {base}.P.npy {base}.P.site\n")
         summary.append((k, ll, init_ll, it, als_it, dt))
         print(f"{args.cmd}: K={k} ll={ll:.3f} iterations={it} ALS={als_it} ({dt:.2f}s) -> {base}.Q.txt")
+        if cv is not None:
+            cv_rows.append(dict(k=k, cverror=cv["cverror"], cverror_se=cv["cverror_se"], cv_folds=cv_folds, wall=dt + dt_cv,
+                                q_out=f"{base}.Q.txt", p_npy_out=f"{base}.P.npy", p_site_out=f"{base}.P.site",
+                                log_path=f"{base}.fastpop.log"))
+            print(f"{args.cmd}: K={k} CVerror={cv['cverror']:.6f} (SE={cv['cverror_se']:.6f}, folds={cv_folds}) ({dt_cv:.2f}s)")
     with open(os.path.join(outdir, f"{prefix}.fastpop.summary.log"), "w") as fh:
         fh.write(f"genotype: {prefix_in}\nsamples: {sess.n_samples}\nkept SNPs: {sess.n_snps}\nK spec: {args.k}\n")
         fh.write("K\tll_final\tinit_ll\tadam_iter\tals_iter\tseconds\n")
         for k, ll, init_ll, it, als_it, dt in summary:
             fh.write(f"{k}\t{ll:.6f}\t{init_ll:.6f}\t{it}\t{als_it}\t{dt:.3f}\n")
+        if cv_rows:
+            best = min(cv_rows, key=lambda r: r["cverror"])
+            fh.write("K\tCVerror\tSE\tCVfolds\tseconds\n")
+            for r in cv_rows:
+                fh.write(f"{r['k']}\t{r['cverror']:.6f}\t{r['cverror_se']:.6f}\t{r['cv_folds']}\t{r['wall']:.3f}\n")
+            fh.write(f"Best K by CVerror: K={best['k']} (CVerror={best['cverror']:.6f}, SE={best['cverror_se']:.6f})\n")
         fh.write(f"total seconds: {time.perf_counter() - t0:.3f}\n")
+    if cv_rows:
+        tsv = os.path.join(outdir, f"{prefix}.fastpop.cverror.summary.tsv")
+        write_cverror_summary_tsv(tsv, cv_rows)
+        print(f"{args.cmd}: Best K by CVerror: K={best['k']} (CVerror={best['cverror']:.6f}, SE={best['cverror_se']:.6f}) -> {tsv}")
     return 0
 
 
@@ -1633,7 +1688,9 @@ def _add_admixture_parser(sub, name):
     a.add_argument("-max-iter", "--max-iter", dest="max_iter", type=int, default=500)
     a.add_argument("-check", "--check", type=int, default=5)
     a.add_argument("-tol", "--tol", type=float, default=1e-5)
-    a.add_argument("-cv", "--cv", type=int, default=None, help="cross-validation folds: not built (0 accepted)")
+    a.add_argument("-cv", "--cv", type=int, default=None, help="the reference's spelling: refused for N >= 2, see -cverror")
+    a.add_argument("-cverror", "--cverror", type=int, nargs="?", const=5, default=None, metavar="N",
+                   help="choose K by N-fold cross-validation error (bare: 5 folds; 2 <= N <= 256; 0 = off)")
     a.add_argument("--no-plot", dest="no_plot", action="store_true", default=False, help="accepted; plots are never drawn")
     a.add_argument("-tag", "--tag", default=None, help="accepted and unused (plots are not built)")
     a.add_argument("-t", "--thread", "-threads", "--threads", dest="thread", type=int, default=None,

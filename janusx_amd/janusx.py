@@ -5259,23 +5259,9 @@ def _admx_p32_check(packed, n):
                    f"the genotype image ({m} SNPs x {int(n)} samples)")
 
 
-class AdmxBedTrainingSession:
-    """`AdmxBedTrainingSession` (src/stats/adamixture.rs:1526, 5950-6140): the kept rows of a PLINK prefix (QC on the minor
-    allele, `missing_rate`, `snps_only`) staged once as a P32 image in HBM with their flips and the per-sample called counts;
-    every `fit_k` of a K scan reuses them.  `memory_mb` is accepted and unused."""
-
-    def __init__(self, genotype_path, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0, payload=None):
-        import torch
-        _admx_check_qc(maf, missing_rate)
-        self.snps_only, self.maf, self.missing_rate = bool(snps_only), float(maf), float(missing_rate)
-        panel, _c, rows, flip, freq, bim, prefix = _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload,
-                                                                   "AdmxBedTrainingSession", "BED training session",
-                                                                   before_panel=_admx_p32_check)
-        self.prefix = prefix if prefix is not None else str(genotype_path)
-        self._panel, self._rows, self._flip, self._freq, self._bim = panel, rows, flip, freq, bim
-        self._eng = _AdmxEngine(panel, rows, flip)
-        self._freq_t = torch.from_numpy(freq).to(panel.device)
-        self._op = None
+class _AdmxFit:
+    """What a training session and a CV fold backend share: a P32 image with the rows `_op_rows` of it (None = all, in order),
+    the flips and frequencies of those rows, the engine of the EM passes and, on first use, the operator of the randomized SVD."""
 
     @property
     def n_samples(self):
@@ -5303,15 +5289,11 @@ class AdmxBedTrainingSession:
                 ref, alt = (b.a1[r], b.a0[r]) if f else (b.a0[r], b.a1[r])
                 fh.write(f"{b.chrom[r]}\t{b.pos[r]}\t{ref}\t{alt}\n")
 
-    def __repr__(self):
-        return (f"AdmxBedTrainingSession(prefix='{self.prefix}', n_snps={self.n_snps}, n_samples={self.n_samples}, "
-                f"snps_only={self.snps_only}, maf={self.maf}, missing_rate={self.missing_rate})")
-
     def _operator(self):
         if self._op is None:
             from . import pipeline as pl
             _admx_need_hbm(int(lib().jxg_t32_bytes(self._panel.n, self.n_snps)), "the sample-major image of the randomized SVD")
-            self._op = _RsvdOperator(self._panel, self._rows.astype(np.int32), _rsvd_row_design(self._freq, self._flip))
+            self._op = _RsvdOperator(self._panel, self._op_rows, _rsvd_row_design(self._freq, self._flip))
             del pl
         return self._op
 
@@ -5367,6 +5349,203 @@ class AdmxBedTrainingSession:
         p, q, ll, it = _admx_adam_loop(self._eng, p, q, lr, beta1, beta2, epsilon, max_iter, check_every, lr_decay, min_lr,
                                        trace)
         return p, q, ll, it, init_ll, als_it
+
+
+class AdmxBedTrainingSession(_AdmxFit):
+    """`AdmxBedTrainingSession` (src/stats/adamixture.rs:1526, 5950-6140): the kept rows of a PLINK prefix (QC on the minor
+    allele, `missing_rate`, `snps_only`) staged once as a P32 image in HBM with their flips and the per-sample called counts;
+    every `fit_k` of a K scan reuses them.  `memory_mb` is accepted and unused."""
+
+    def __init__(self, genotype_path, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0, payload=None):
+        import torch
+        _admx_check_qc(maf, missing_rate)
+        self.snps_only, self.maf, self.missing_rate = bool(snps_only), float(maf), float(missing_rate)
+        panel, _c, rows, flip, freq, bim, prefix = _admx_kept_rows(genotype_path, snps_only, maf, missing_rate, payload,
+                                                                   "AdmxBedTrainingSession", "BED training session",
+                                                                   before_panel=_admx_p32_check)
+        self.prefix = prefix if prefix is not None else str(genotype_path)
+        self._panel, self._rows, self._flip, self._freq, self._bim = panel, rows, flip, freq, bim
+        self._eng = _AdmxEngine(panel, rows, flip)
+        self._freq_t = torch.from_numpy(freq).to(panel.device)
+        self._op, self._op_rows = None, rows.astype(np.int32)
+
+    def __repr__(self):
+        return (f"AdmxBedTrainingSession(prefix='{self.prefix}', n_snps={self.n_snps}, n_samples={self.n_samples}, "
+                f"snps_only={self.snps_only}, maf={self.maf}, missing_rate={self.missing_rate})")
+
+    def cv_observed_fold_counts(self, folds, seed):
+        """`cv_observed_fold_counts_packed_impl` (src/stats/adamixture.rs:3056-3128) -> (observed, int64 (folds)): the called
+        genotypes of the kept rows per fold of `admx_cv_fold_ids`."""
+        import torch
+        from . import pipeline as pl
+        folds = _admx_cv_check(folds)
+        eng = self._eng
+        counts = torch.empty(folds, dtype=torch.int64, device=eng.dev)
+        check(lib().jxg_admx_cv_fold_counts(eng.panel.p32.data_ptr(), eng.panel.m, eng.n, pl._ptr(eng.rows_t), eng.m, folds,
+                                            _admx_cv_seed(seed), counts.data_ptr(), pl._stream()))
+        counts = counts.cpu().numpy()
+        return int(counts.sum()), counts
+
+    def make_cv_fold_backend(self, fold_id, folds, seed):
+        """`make_cv_fold_backend` (src/stats/adamixture.rs:6262-6284) -> `AdmxBedFoldBackend`."""
+        return AdmxBedFoldBackend(self, fold_id, folds, seed)
+
+
+ADMX_CV_MAX_FOLDS = 256                # JXG_ADMX_CV_MAX_FOLDS: the fold histogram of a workgroup lives in LDS
+_ADMX_CV_WORK_BYTES = 32768            # JXG_ADMX_CV_WORK_BYTES
+_ADMX_CV_GOLDEN = 0x9E3779B97F4A7C15
+_U64 = (1 << 64) - 1
+
+
+def _admx_cv_seed(seed):
+    return int(seed) & _U64
+
+
+def _admx_cv_check(folds, fold_id=None):
+    folds = int(folds)
+    if folds < 2:
+        raise RuntimeError(f"CVerror requires folds >= 2, got {folds}.")
+    if folds > ADMX_CV_MAX_FOLDS:
+        raise RuntimeError(f"CVerror folds must be at most {ADMX_CV_MAX_FOLDS} on this build (got {folds})")
+    if fold_id is not None and not 0 <= int(fold_id) < folds:
+        raise RuntimeError(f"fold_id must be within [0, {folds}), got {int(fold_id)}")
+    return folds
+
+
+def admx_cv_fold_ids(flat_idx, folds, seed):
+    """`cv_fold_id` (src/stats/adamixture.rs:1641-1653; python/janusx/adamixture/core.py:208-223) on the host: the fold of the
+    genotypes with the flat indices kept_row * n_samples + sample, a SplitMix64 step of flat ^ (seed ^ golden) in wrapping
+    u64 arithmetic (the seed taken mod 2^64), mod folds -> int64 array of the shape of `flat_idx`."""
+    x = np.asarray(flat_idx).astype(np.uint64) ^ np.uint64(_admx_cv_seed(seed) ^ _ADMX_CV_GOLDEN)
+    with np.errstate(over="ignore"):
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    x = x ^ (x >> np.uint64(31))
+    return (x % np.uint64(max(int(folds), 1))).astype(np.int64)
+
+
+class _AdmxImage:
+    """A P32 image that is already in HBM, with the four attributes the engine and the RSVD operator read of a Panel."""
+
+    def __init__(self, p32, m, n):
+        self.p32, self.m, self.n, self.device = p32, int(m), int(n), p32.device
+
+
+class AdmxBedFoldBackend(_AdmxFit):
+    """`AdmxBedFoldBackend` (src/stats/adamixture.rs:6409-6640): one CV fold of a training session.  The reference masks the
+    fold's calls in every pass over the shared payload; here the kept rows are copied once into a compact P32 image with those
+    calls turned missing (`jxg_admx_cv_fold_image`), and the fold's fit is the session's fit on that image: training-only
+    likelihood and called counts, `row_freq()` = the training frequencies in the SVD design, the full session's flips.
+    `holdout_nll_f32` scores the held-out calls on the session's own image."""
+
+    def __init__(self, session, fold_id, folds, seed):
+        import torch
+        from . import pipeline as pl
+        folds = _admx_cv_check(folds, fold_id)
+        full = session._eng
+        self.prefix, self.snps_only, self.maf, self.missing_rate = session.prefix, session.snps_only, session.maf, session.missing_rate
+        self.fold_id, self.folds, self.cv_seed = int(fold_id), folds, _admx_cv_seed(seed)
+        self._full, self._rows, self._flip, self._bim = full, session._rows, session._flip, session._bim
+        nt = (full.n + 127) // 128
+        _admx_need_hbm(32 * nt * full.m + 12 * full.m, f"the image of CV fold {self.fold_id + 1}/{folds} ({full.m} SNPs x "
+                                                       f"{full.n} samples)")
+        p32 = torch.empty((nt, full.m, 32), dtype=torch.uint8, device=full.dev)
+        stats = torch.empty((full.m, 3), dtype=torch.int32, device=full.dev)
+        check(lib().jxg_admx_cv_fold_image(full.panel.p32.data_ptr(), full.panel.m, full.n, pl._ptr(full.rows_t), full.m,
+                                           full.flip_t.data_ptr(), folds, self.cv_seed, self.fold_id, p32.data_ptr(),
+                                           stats.data_ptr(), pl._stream()))
+        self._row_stats = stats.cpu().numpy()
+        train = self._row_stats[:, 0].astype(np.float64)
+        # `cv_training_row_freq_packed_impl` (:3198-3202): the f64 quotient rounded to f32, 0 for a row without training calls
+        self._freq = np.where(train > 0, self._row_stats[:, 2] / (2.0 * np.maximum(train, 1.0)), 0.0).astype(np.float32)
+        self.train_observed = int(self._row_stats[:, 0].sum(dtype=np.int64))
+        self.holdout_observed = int(self._row_stats[:, 1].sum(dtype=np.int64))
+        self._panel = _AdmxImage(p32, full.m, full.n)
+        self._eng = _AdmxEngine(self._panel, None, self._flip)
+        self._freq_t = torch.from_numpy(self._freq).to(full.dev)
+        self._op, self._op_rows = None, None
+        self._work = torch.empty(_ADMX_CV_WORK_BYTES, dtype=torch.uint8, device=full.dev)
+
+    def close(self):
+        """Release the fold image and everything built on it."""
+        self._panel = self._eng = self._op = self._freq_t = self._work = None
+
+    def __repr__(self):
+        return (f"AdmxBedFoldBackend(prefix='{self.prefix}', n_snps={self.n_snps}, n_samples={self._full.n}, "
+                f"fold={self.fold_id + 1}/{self.folds}, cv_seed={self.cv_seed})")
+
+    def loglikelihood_f32(self, p, q):
+        """The training-only log-likelihood (`loglikelihood_packed_train_fold_f32_impl`, :4486-4549)."""
+        pt, qt = _admx_pq_host(self._eng, p, q)
+        return self._eng.loglik(pt, qt)
+
+    def _holdout(self, p, q):
+        """-> (ll_sum, n_eval) of device tensors P (m, K), Q (n, K)."""
+        import torch
+        from . import pipeline as pl
+        full = self._full
+        k = full._pq(p, q)
+        out_ll = torch.empty(1, dtype=torch.float64, device=full.dev)
+        out_n = torch.empty(1, dtype=torch.int64, device=full.dev)
+        check(lib().jxg_admx_cv_holdout_nll(full.panel.p32.data_ptr(), full.panel.m, full.n, pl._ptr(full.rows_t), full.m,
+                                            full.flip_t.data_ptr(), self.folds, self.cv_seed, self.fold_id, k, p.data_ptr(),
+                                            q.data_ptr(), self._work.data_ptr(), int(self._work.numel()), out_ll.data_ptr(),
+                                            out_n.data_ptr(), pl._stream()))
+        return float(out_ll.item()), int(out_n.item())
+
+    def holdout_nll_f32(self, p, q):
+        """`holdout_nll_f32` (:6527-6563) -> (mean_nll, deviance, n_eval) = (-ll / n, -2 ll, n) over the held-out calls, with the
+        reconstruction clamped in f64 (README, Known differences); (NaN, NaN, 0) without held-out calls."""
+        pt, qt = _admx_pq_host(self._full, p, q)
+        ll, n_eval = self._holdout(pt.contiguous(), qt.contiguous())
+        if n_eval == 0:
+            return float("nan"), float("nan"), 0
+        return -ll / n_eval, -2.0 * ll, n_eval
+
+
+def admx_evaluate_cverror(session, k, folds, seed=42, solver="adam-em", power=5, tol=1e-5, max_als=1000, reg_als=1e-5, lr=0.005,
+                          beta1=0.80, beta2=0.88, epsilon=1e-8, max_iter=500, check_every=5, lr_decay=0.5, min_lr=1e-6,
+                          keep_fits=False):
+    """`evaluate_adamixture_cverror_bed` (python/janusx/adamixture/core.py:1662-1794): K-fold cross-validation error of one K on
+    a staged session.  Fold i holds out the called genotypes of fold i, is fitted with the seed `seed + i + 1` and scored by the
+    mean binomial negative log-likelihood of its held-out calls -> dict(cverror = mean of the fold means, cverror_se =
+    std(ddof=1) / sqrt(folds), cv_folds, cv_observed, fold_counts, fold_mean_nll, fold_eval_counts[, fold_p, fold_q])."""
+    folds = int(folds)
+    if folds < 2:
+        raise ValueError(f"CVerror requires folds >= 2, got {folds}. Use -cverror N with N>=2.")
+    if folds > ADMX_CV_MAX_FOLDS:
+        raise ValueError(f"CVerror folds must be at most {ADMX_CV_MAX_FOLDS} on this build (got {folds})")
+    n_obs, fold_counts = session.cv_observed_fold_counts(folds, seed)
+    if n_obs < folds:
+        raise ValueError(f"Not enough observed genotypes for CVerror: observed={n_obs}, folds={folds}.")
+    if np.any(fold_counts <= 0):
+        bad = [str(i + 1) for i in np.flatnonzero(fold_counts <= 0)]
+        raise ValueError(f"Failed to build non-empty CV folds in BED foldmask assignment; empty folds={','.join(bad)}.")
+    means, evals, fits_p, fits_q = [], [], [], []
+    for i in range(folds):
+        fb = session.make_cv_fold_backend(i, folds, seed)
+        try:
+            if fb.holdout_observed <= 0:
+                raise ValueError(f"Fold {i + 1} has no held-out genotypes.")
+            p, q, _ll, _it, _init_ll, _als = fb._fit(k, int(seed) + i + 1, solver, power, tol, max_als, reg_als, lr, beta1, beta2,
+                                                     epsilon, max_iter, check_every, lr_decay, min_lr)
+            ll, n_eval = fb._holdout(p.contiguous(), q.contiguous())
+            if n_eval <= 0:
+                raise ValueError(f"Fold {i + 1} produced no held-out evaluation genotypes.")
+            means.append(-ll / n_eval)
+            evals.append(n_eval)
+            if keep_fits:
+                fits_p.append(p.cpu().numpy())
+                fits_q.append(q.cpu().numpy())
+        finally:
+            fb.close()
+    arr = np.asarray(means, dtype=np.float64)
+    out = {"cverror": float(np.mean(arr)), "cverror_se": float(np.std(arr, ddof=1) / np.sqrt(arr.size)), "cv_folds": folds,
+           "cv_observed": int(n_obs), "fold_counts": fold_counts, "fold_mean_nll": arr,
+           "fold_eval_counts": np.asarray(evals, dtype=np.int64)}
+    if keep_fits:
+        out["fold_p"], out["fold_q"] = fits_p, fits_q
+    return out
 
 
 def admx_bed_training_meta(genotype_path, snps_only=True, maf=0.02, missing_rate=0.05, memory_mb=0):
