@@ -19,6 +19,7 @@
 namespace jx {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr int DG_BK = 16;
 constexpr int DG_THREADS = 512;   // 8 waves = 4 (M) x 2 (N): <= 128 VGPRs per lane, two workgroups per CU
@@ -36,6 +37,8 @@ struct DgemmArgs {
     int ksplit;        // > 1: blockIdx.z owns a K range and writes its partial product to ws[z] (m x n, ld = m); a second
                        // kernel sums the slices in a fixed order (bit-reproducible, unlike f64 atomics)
     double *ws;
+    int wide;          // every 16-byte access of the wide forms is aligned (dg_wide_ok: bases, even leading dimensions; tile and K
+                       // origins are even by construction) and JXGPU_DGEMM_WIDE is not 0; bit 0: operands, bit 1: C
 };
 
 // Branch-free: every lane always issues its NL loads from a clamped (valid) address and zeroes the out-of-range elements
@@ -70,17 +73,31 @@ __device__ __forceinline__ unsigned dg_load_tile(const double *__restrict__ p, i
     return okmask;
 }
 
-template <int BX, int NT = DG_THREADS>
+// W = 2: the registers of the wide stream (DgStream<.., 2>): r[2 i], r[2 i + 1] are two adjacent x of one k row (x-fast) or two
+// adjacent k of one x (k-fast), bit i of the mask covers the pair.  The image [k][x] is the same; its odd pitch leaves every other k
+// row off a 16-byte boundary, so a pair goes as two 8-byte stores (in the x-fast form one ds_write2_b64).
+template <int BX, int NT = DG_THREADS, int W = 1>
 __device__ __forceinline__ void dg_store_tile(double *__restrict__ s, bool kfast, const double (&r)[BX * DG_BK / NT],
                                               unsigned okmask) {
     constexpr int NL = BX * DG_BK / NT;
     constexpr int PITCH = BX + 17;
     const int t = threadIdx.x;
+    if constexpr (W == 1) {
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        const int idx = i * NT + t;
-        const int pos = kfast ? (idx % DG_BK) * PITCH + idx / DG_BK : (idx / BX) * PITCH + idx % BX;
-        s[pos] = ((okmask >> i) & 1u) ? r[i] : 0.0;
+        for (int i = 0; i < NL; ++i) {
+            const int idx = i * NT + t;
+            const int pos = kfast ? (idx % DG_BK) * PITCH + idx / DG_BK : (idx / BX) * PITCH + idx % BX;
+            s[pos] = ((okmask >> i) & 1u) ? r[i] : 0.0;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NL / 2; ++i) {
+            const int idx = i * NT + t;
+            const int pos = kfast ? 2 * (idx % (DG_BK / 2)) * PITCH + idx / (DG_BK / 2) : (idx / (BX / 2)) * PITCH + 2 * (idx % (BX / 2));
+            const bool ok = (okmask >> i) & 1u;
+            s[pos] = ok ? r[2 * i] : 0.0;
+            s[pos + (kfast ? PITCH : 1)] = ok ? r[2 * i + 1] : 0.0;
+        }
     }
 }
 
@@ -88,11 +105,16 @@ __device__ __forceinline__ void dg_store_tile(double *__restrict__ s, bool kfast
 // address of element i of step t + 1 is the address of step t plus a constant, and the in-range mask of x does not change:
 // one 64-bit add per element and step instead of the clamps and the 64-bit index product of dg_load_tile (by ablation --
 // scripts/probes/dgemm_probe.hip -- the loop skeleton reaches 69 TFLOP/s, the general loader held the kernel at 52).
-template <int BX, int NT>
+// W = 2 (wide form): a lane takes two adjacent elements with one 16-byte load -- two x of one k row in the x-fast regime, two k of one
+// x in the k-fast one -- so half the loads and half the offset registers.  The caller guarantees that every such pair is 16-byte
+// aligned (DgemmArgs::wide) and, in the x-fast regime, that the whole tile lies inside the matrix (a pair never straddles xmax).
+template <int BX, int NT, int W = 1>
 struct DgStream {
     static constexpr int NL = BX * DG_BK / NT;
+    static constexpr int NV = NL / W;
+    static_assert(NL % W == 0 && BX % W == 0, "whole pairs");
     const char *base;        // wave-uniform: origin of the current step's tile (an SGPR pair, advanced by `step` per K step)
-    unsigned off[NL];        // byte offset of this lane's elements from it (< 128 ld doubles: 32 bits)
+    unsigned off[NV];        // byte offset of this lane's elements from it (< 128 ld doubles: 32 bits)
     int64_t step;            // bytes per K step (uniform)
     unsigned xmask;
     __device__ __forceinline__ void init(const double *__restrict__ mat, int64_t ld, bool kfast, int x0, int xmax, int k0) {
@@ -100,10 +122,10 @@ struct DgStream {
         xmask = 0;
         base = reinterpret_cast<const char *>(mat + (kfast ? (int64_t)k0 + (int64_t)x0 * ld : (int64_t)x0 + (int64_t)k0 * ld));
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
+        for (int i = 0; i < NV; ++i) {
             const int idx = i * NT + t;
-            const int xo = kfast ? idx / DG_BK : idx % BX;
-            const int ko = kfast ? idx % DG_BK : idx / BX;
+            const int xo = kfast ? idx / (DG_BK / W) : W * (idx % (BX / W));
+            const int ko = kfast ? W * (idx % (DG_BK / W)) : idx / (BX / W);
             const int xoc = min(x0 + xo, xmax - 1) - x0;                  // clamped: always a valid address
             off[i] = (unsigned)(8 * (kfast ? (int64_t)ko + (int64_t)xoc * ld : (int64_t)xoc + (int64_t)ko * ld));
             xmask |= (x0 + xo < xmax) ? (1u << i) : 0u;
@@ -111,10 +133,24 @@ struct DgStream {
         step = 8 * (kfast ? (int64_t)DG_BK : (int64_t)DG_BK * ld);
     }
     __device__ __forceinline__ void load(double (&r)[NL]) {
+        if constexpr (W == 1) {
 #pragma unroll
-        for (int i = 0; i < NL; ++i) r[i] = *reinterpret_cast<const double *>(base + off[i]);
+            for (int i = 0; i < NL; ++i) r[i] = *reinterpret_cast<const double *>(base + off[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const d2 v = *reinterpret_cast<const d2 *>(base + off[i]);
+                r[2 * i] = v.x;
+                r[2 * i + 1] = v.y;
+            }
+        }
         base += step;
     }
+};
+
+template <int W>
+struct DgWidth {
+    static constexpr int value = W;
 };
 
 // STREAM: K loop split into runs of steady-state steps (DgStream) and general steps; it wants ~230 registers (two waves per
@@ -172,8 +208,6 @@ __global__ __launch_bounds__(NT, STREAM ? 2 : (NT == 512 ? 4 : 2)) void dgemm_ke
         return ta;
     };
     unsigned oka = 0, okb = 0;
-    DgStream<BM, NT> sa;
-    DgStream<BN, NT> sb;
     static_assert(BM >= DG_BK, "tile rows");
     // regime of the K step that starts at k: 0 = A stored as (x, k) (plain, or symmetric left of the tile's rows), 1 = A read
     // transposed (ta, or symmetric right of the tile's rows), 2 = general loader (K tail, symmetric step crossing the diagonal)
@@ -236,18 +270,27 @@ __global__ __launch_bounds__(NT, STREAM ? 2 : (NT == 512 ? 4 : 2)) void dgemm_ke
         // the MFMAs and the staging stores inside this loop)
         int k_hi = kbeg + ((kend - kbeg) / DG_BK - 1) * DG_BK;     // last step that lies inside the K range
         if (symm && md == 0) k_hi = min(k_hi, m0 - DG_BK);
-        sa.init(g.a, g.lda, md == 1, m0, g.m, kn);
-        sb.init(g.b, g.ldb, g.tb == 0, n0, g.n, kn);
         const bool akf = md == 1;
-        for (; k0 + DG_BK <= k_hi; k0 += DG_BK) {
-            sa.load(ra);
-            sb.load(rb);
-            multiply();
-            dg_store_tile<BM, NT>(as + (buf ^ 1) * DG_BK * PA, akf, ra, sa.xmask);
-            dg_store_tile<BN, NT>(bs + (buf ^ 1) * DG_BK * PB, tb_kfast, rb, sb.xmask);
-            __syncthreads();
-            buf ^= 1;
-        }
+        auto run = [&](auto wtag) {
+            constexpr int W = decltype(wtag)::value;
+            DgStream<BM, NT, W> sa;
+            DgStream<BN, NT, W> sb;
+            sa.init(g.a, g.lda, akf, m0, g.m, kn);
+            sb.init(g.b, g.ldb, tb_kfast, n0, g.n, kn);
+            for (; k0 + DG_BK <= k_hi; k0 += DG_BK) {
+                sa.load(ra);
+                sb.load(rb);
+                multiply();
+                dg_store_tile<BM, NT, W>(as + (buf ^ 1) * DG_BK * PA, akf, ra, sa.xmask);
+                dg_store_tile<BN, NT, W>(bs + (buf ^ 1) * DG_BK * PB, tb_kfast, rb, sb.xmask);
+                __syncthreads();
+                buf ^= 1;
+            }
+        };
+        // 16-byte loads where the call is eligible and no x-fast pair can straddle the edge of its matrix (ragged last tiles of an
+        // x-fast operand keep the 8-byte form; k-fast pairs lie along K, inside the range by the choice of k_hi)
+        if ((g.wide & 1) && (akf || m0 + BM <= g.m) && (tb_kfast || n0 + BN <= g.n)) run(DgWidth<2>{});
+        else run(DgWidth<1>{});
     }
     // epilogue: acc[j][i][r] = C[m0 + wm + 16 i + lx][n0 + wn + 16 j + lk + 4 r]
     const bool split = g.ksplit > 1;
@@ -296,6 +339,10 @@ __global__ __launch_bounds__(NT, STREAM ? 2 : (NT == 512 ? 4 : 2)) void dgemm_ke
 // (the loads of a wave return in order: all of them in front of the first step put the next step's operands behind 128 KB of C) and
 // consumed behind its last, the stores of the finished tile drain behind the next tile's products.  Same products in the same order,
 // same alpha acc + beta c expression: the same bits as dgemm_kernel.
+// WIDE: operands and C travel in 16-byte pieces (two adjacent rows per lane and access).  The host selects it when A, B and C are
+// 16-byte aligned with even leading dimensions AND m is even: every pair then lies wholly inside or wholly outside the matrix, so the
+// clamps and masks act on pairs and the kernel has no 8-byte path beside the wide one (both in one kernel cost 40 registers: scratch).
+template <bool WIDE>
 __global__ __launch_bounds__(512, 2) void dsyr2k_pipe_kernel(DgemmArgs g) {
     constexpr int BM = 128, BN = 128, NT = 512;
     constexpr int PA = BM + 17, PB = BN + 17;
@@ -339,31 +386,53 @@ __global__ __launch_bounds__(512, 2) void dsyr2k_pipe_kernel(DgemmArgs g) {
     const int nks = g.k / DG_BK;
     // operand element i of this thread at a step: x = t % 128 (clamped), k = 4 i + t / 128.  Addresses: a per-thread origin per
     // tile (row x of the panel), the same four 32-bit byte offsets for every step and tile (k rows 4 i + t / 128), and a
-    // wave-uniform byte offset of the step
-    const int xo = t & 127, ko = t >> 7;
-    unsigned offa[NL], offb[NL];
+    // wave-uniform byte offset of the step.
+    // WIDE: pair i of this thread is x = 2 (t % 64) and the next (clamped as a pair) of k row 8 i + t / 64 -- one 16-byte load per
+    // pair, half the loads and offsets; ra[2 i], ra[2 i + 1] hold it.  The LDS image is the same.
+    constexpr int NV = WIDE ? NL / 2 : NL;
+    const int xo = WIDE ? 2 * (t & 63) : t & 127, ko = WIDE ? t >> 6 : t >> 7;
+    unsigned offa[NV], offb[NV];
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-        offa[i] = (unsigned)(8 * (int64_t)(4 * i + ko) * g.lda);
-        offb[i] = (unsigned)(8 * (int64_t)(4 * i + ko) * g.ldb);
+    for (int i = 0; i < NV; ++i) {
+        offa[i] = (unsigned)(8 * (int64_t)((NL / NV) * 4 * i + ko) * g.lda);
+        offb[i] = (unsigned)(8 * (int64_t)((NL / NV) * 4 * i + ko) * g.ldb);
     }
     const int64_t stepa = 8 * (int64_t)DG_BK * g.lda, stepb = 8 * (int64_t)DG_BK * g.ldb;
     auto load_step = [&](int m0, int n0, int k0, double (&ra)[NL], double (&rb)[NL]) {
-        const int xa = min(m0 + xo, g.m - 1), xb = min(n0 + xo, g.n - 1);
+        // (WIDE: m = n is even, so m - 2 is the last whole pair)
+        const int xa = min(m0 + xo, WIDE ? g.m - 2 : g.m - 1), xb = min(n0 + xo, WIDE ? g.n - 2 : g.n - 1);
         const char *pa = reinterpret_cast<const char *>(g.a + xa) + (int64_t)(k0 / DG_BK) * stepa;
         const char *pb = reinterpret_cast<const char *>(g.b + xb) + (int64_t)(k0 / DG_BK) * stepb;
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            ra[i] = *reinterpret_cast<const double *>(pa + offa[i]);
-            rb[i] = *reinterpret_cast<const double *>(pb + offb[i]);
+        for (int i = 0; i < NV; ++i) {
+            if constexpr (WIDE) {
+                const d2 va = *reinterpret_cast<const d2 *>(pa + offa[i]);
+                const d2 vb = *reinterpret_cast<const d2 *>(pb + offb[i]);
+                ra[2 * i] = va.x;
+                ra[2 * i + 1] = va.y;
+                rb[2 * i] = vb.x;
+                rb[2 * i + 1] = vb.y;
+            } else {
+                ra[i] = *reinterpret_cast<const double *>(pa + offa[i]);
+                rb[i] = *reinterpret_cast<const double *>(pb + offb[i]);
+            }
         }
     };
     auto store_step = [&](int m0, int n0, int buf, const double (&ra)[NL], const double (&rb)[NL]) {
         const bool oka = m0 + xo < g.m, okb = n0 + xo < g.n;
 #pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            as[buf * DG_BK * PA + (4 * i + ko) * PA + xo] = oka ? ra[i] : 0.0;
-            bs[buf * DG_BK * PB + (4 * i + ko) * PB + xo] = okb ? rb[i] : 0.0;
+        for (int i = 0; i < NV; ++i) {
+            double *qa = as + buf * DG_BK * PA + ((NL / NV) * 4 * i + ko) * PA + xo;
+            double *qb = bs + buf * DG_BK * PB + ((NL / NV) * 4 * i + ko) * PB + xo;
+            if constexpr (WIDE) {
+                qa[0] = oka ? ra[2 * i] : 0.0;
+                qa[1] = oka ? ra[2 * i + 1] : 0.0;
+                qb[0] = okb ? rb[2 * i] : 0.0;
+                qb[1] = okb ? rb[2 * i + 1] : 0.0;
+            } else {
+                qa[0] = oka ? ra[i] : 0.0;
+                qb[0] = okb ? rb[i] : 0.0;
+            }
         }
     };
     double ra[NL], rb[NL];
@@ -380,16 +449,21 @@ __global__ __launch_bounds__(512, 2) void dsyr2k_pipe_kernel(DgemmArgs g) {
         for (int j = 0; j < NB; ++j)
 #pragma unroll
             for (int i = 0; i < MB; ++i) acc[j][i] = (d4){0.0, 0.0, 0.0, 0.0};
-        double cv[NB][4][MB];
+        // acc[j][i][r] = C[m0 + wm + 2 lx + i][n0 + wn + 16 j + lk + 4 r]: MFMA lane lx of block i is fed LDS row wm + 2 lx + i (not
+        // wm + 16 i + lx as in dgemm_kernel -- which lane holds an element does not change its sum), so a lane owns the row PAIR
+        // 2 lx, 2 lx + 1 of every column it touches: WIDE moves it with one 16-byte access each way, otherwise two 8-byte ones.
+        d2 cv[NB][4];
         const bool rmw = g.beta != 0.0;
+        const int row0 = m0 + wm + 2 * lx;
         auto c_load = [&](int j) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int col = min(n0 + wn + 16 * j + lk + 4 * r, g.n - 1);
-#pragma unroll
-                for (int i = 0; i < MB; ++i) {
-                    const int row = min(m0 + wm + 16 * i + lx, g.m - 1);
-                    cv[j][r][i] = g.c[row + (int64_t)col * g.ldc];
+                if constexpr (WIDE) {
+                    cv[j][r] = *reinterpret_cast<const d2 *>(g.c + min(row0, g.m - 2) + (int64_t)col * g.ldc);
+                } else {
+                    cv[j][r].x = g.c[min(row0, g.m - 1) + (int64_t)col * g.ldc];
+                    cv[j][r].y = g.c[min(row0 + 1, g.m - 1) + (int64_t)col * g.ldc];
                 }
             }
         };
@@ -405,13 +479,13 @@ __global__ __launch_bounds__(512, 2) void dsyr2k_pipe_kernel(DgemmArgs g) {
                     if (ks == j || (last && j > ks)) c_load(j);
             }
             {
-                const double *ap = as + buf * DG_BK * PA + wm + lx;
+                const double *ap = as + buf * DG_BK * PA + wm + 2 * lx;
                 const double *bp = bs + buf * DG_BK * PB + wn + lx;
 #pragma unroll
                 for (int k4 = 0; k4 < DG_BK; k4 += 4) {
                     double fa[MB], fb[NB];
 #pragma unroll
-                    for (int i = 0; i < MB; ++i) fa[i] = ap[(k4 + lk) * PA + i * 16];
+                    for (int i = 0; i < MB; ++i) fa[i] = ap[(k4 + lk) * PA + i];
 #pragma unroll
                     for (int j = 0; j < NB; ++j) fb[j] = bp[(k4 + lk) * PB + j * 16];
 #pragma unroll
@@ -432,13 +506,27 @@ __global__ __launch_bounds__(512, 2) void dsyr2k_pipe_kernel(DgemmArgs g) {
             for (int r = 0; r < 4; ++r) {
                 const int col = n0 + wn + 16 * j + lk + 4 * r;
                 if (col >= g.n) continue;
+                double o[MB];
 #pragma unroll
                 for (int i = 0; i < MB; ++i) {
-                    const int row = m0 + wm + 16 * i + lx;
-                    if (row >= g.m) continue;
-                    if (row < col) continue;                  // diagonal tiles: the strict upper part is not referenced
                     const double v = g.alpha * acc[j][i][r];
-                    g.c[row + (int64_t)col * g.ldc] = rmw ? (v + g.beta * cv[j][r][i]) : v;
+                    o[i] = rmw ? (v + g.beta * cv[j][r][i]) : v;
+                }
+                // diagonal tiles: the strict upper part is not referenced -- a pair that straddles the diagonal (row0 + 1 == col) stores
+                // its lower-triangle element alone
+                if constexpr (WIDE) {
+                    if (row0 >= g.m) continue;                // m even: the whole pair is outside
+                    if (row0 >= col) {
+                        *reinterpret_cast<d2 *>(g.c + row0 + (int64_t)col * g.ldc) = (d2){o[0], o[1]};
+                        continue;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < MB; ++i) {
+                    const int row = row0 + i;
+                    if (row >= g.m) continue;
+                    if (row < col) continue;
+                    g.c[row + (int64_t)col * g.ldc] = o[i];
                 }
             }
         if (!has_next) break;
@@ -500,6 +588,16 @@ __global__ void dg_scale_kernel(double *c, int64_t ldc, int m, int n, double bet
     *p = (beta == 0.0) ? 0.0 : beta * *p;
 }
 
+// Eligibility of the 16-byte forms, once per call: base pointers on 16-byte boundaries and even leading dimensions (tile origins and
+// K-slice origins are multiples of 16 elements).  Bit 0: the operand streams, bit 1: the C tile of the rank-2k update.
+// JXGPU_DGEMM_WIDE=0 (read per call: the tests compare both forms inside one process) restores the 8-byte accesses everywhere.
+static int dg_wide_ok(const DgemmArgs &g) {
+    const char *e = getenv("JXGPU_DGEMM_WIDE");
+    if (e && atoi(e) == 0) return 0;
+    auto al = [](const void *p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 1) == 0; };
+    return (al(g.a, g.lda) && al(g.b, g.ldb) ? 1 : 0) | (al(g.c, g.ldc) ? 2 : 0);
+}
+
 static int dg_fit_split(int ksplit, int m, int n, size_t ws_doubles) {
     const size_t per = (size_t)m * (size_t)n;
     if (ksplit > 1 && per * (size_t)ksplit > ws_doubles) ksplit = (int)(ws_doubles / per);
@@ -553,6 +651,7 @@ int dgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, double alpha, c
     const int tm = ceil_div(m, bm), tn = ceil_div(n, bn);
     if (ksplit <= 0) ksplit = dgemm_auto_split(m, n, k, ws ? ws_doubles : 0);
     g.ksplit = dg_fit_split(ksplit, m, n, ws ? ws_doubles : 0);
+    g.wide = dg_wide_ok(g);
     dim3 grid(tm, tn, g.ksplit);
     int rc;
     if (bm == 128 && bn == 128) rc = dg_launch<128, 128>(g, grid, st);
@@ -594,6 +693,7 @@ int dsymm_lower(hipStream_t st, int m, int n, double alpha, const double *a, int
         if (ksplit > maxsplit) ksplit = maxsplit;
     }
     g.ksplit = dg_fit_split(ksplit, m, n, ws ? ws_doubles : 0);
+    g.wide = dg_wide_ok(g);
     dim3 grid(tm, tn, g.ksplit);
     const int rc = wide ? dg_launch<128, 128>(g, grid, st) : dg_launch<128, 64>(g, grid, st);
     if (rc) return rc;
@@ -606,6 +706,7 @@ int dsyr2k_lower_nt(hipStream_t st, int m, int k, double alpha, const double *a,
                     double beta, double *c, int64_t ldc) {
     if (m <= 0) return 0;
     DgemmArgs g{a, b, c, lda, ldb, ldc, m, m, k, alpha, beta, 0, 1, 0, 1, 1, nullptr};
+    g.wide = dg_wide_ok(g);
     const int t = ceil_div(m, 128);
     // one stream of K steps over a workgroup's tiles (dsyr2k_pipe_kernel) from two tiles per workgroup on; JXGPU_SYR2K_PIPE=0: one
     // tile per workgroup (dgemm_kernel)
@@ -614,27 +715,28 @@ int dsyr2k_lower_nt(hipStream_t st, int m, int k, double alpha, const double *a,
     // its workgroups stay for the whole launch (one per CU: 216 registers), so the panel chain of the NEXT panel -- on the other
     // stream, the critical path -- only finds the CUs this kernel leaves alone: 7 / 8 of them measured best at n = 20 000 (band
     // reduction, pipe on 256 / 248 / 240 / 232 CUs: 372 - 382 ms, on 224: 336, 216: 339, 208: 342, 192: 352; dgemm_kernel: 355)
-    static const int pipe_wgs = [] {
-        const char *e = getenv("JXGPU_SYR2K_PIPE_WGS");
-        int v = e ? atoi(e) : 0;
-        if (v < 8) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            v = 224;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 16)
-                v = prop.multiProcessorCount * 7 / 8;
-        }
+    // (the variable is read per call, like JXGPU_SYR2K_PIPE: a test selects the pipe form at a small size inside one process)
+    static const int default_wgs = [] {
+        int dev = 0, v = 224;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 16)
+            v = prop.multiProcessorCount * 7 / 8;
         return v >= 8 ? (v / 8) * 8 : 224;
     }();
+    const char *we = getenv("JXGPU_SYR2K_PIPE_WGS");
+    const int wv = we ? atoi(we) : 0;
+    const int pipe_wgs = wv >= 8 ? (wv / 8) * 8 : default_wgs;
     const int64_t ntl = (int64_t)t * (t + 1) / 2;
     if (pipe && k > 0 && k % DG_BK == 0 && ntl >= 2 * (int64_t)pipe_wgs) {
         constexpr size_t smem = sizeof(double) * 2 * DG_BK * ((128 + 17) + (128 + 17));
         static bool attr_set = false;
         if (!attr_set) {
-            JX_HIP(hipFuncSetAttribute((const void *)dsyr2k_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            JX_HIP(hipFuncSetAttribute((const void *)dsyr2k_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            JX_HIP(hipFuncSetAttribute((const void *)dsyr2k_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             attr_set = true;
         }
-        hipLaunchKernelGGL(dsyr2k_pipe_kernel, dim3((unsigned)pipe_wgs), dim3(512), smem, st, g);
+        if (g.wide == 3 && m % 2 == 0) hipLaunchKernelGGL(dsyr2k_pipe_kernel<true>, dim3((unsigned)pipe_wgs), dim3(512), smem, st, g);
+        else hipLaunchKernelGGL(dsyr2k_pipe_kernel<false>, dim3((unsigned)pipe_wgs), dim3(512), smem, st, g);
         JX_LAUNCH_CHECK();
         return 0;
     }

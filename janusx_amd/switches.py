@@ -97,6 +97,7 @@ SWITCHES = {
         "JXGPU_SCAN_CHAIN_SPLIT": "test_warm_start_chain_kernels_on_rotated_rows_with_invalid_rows",
         "JXGPU_REPACK_WINDOW": "test_repack_of_a_sample_subset_window_form",
         "JXGPU_SYR2K_PIPE": "test_rank_2k_update_forms_give_the_same_bits",
+        "JXGPU_DGEMM_WIDE": "tests/test_gpu_dgemm_wide.py (0: 8-byte operand and C accesses in the f64 GEMM family, bit for bit)",
         "JXGPU_KING_TILE": "test_fused_path_finds_every_finite_pair"}.items()},
     # ---- ablation masks (wrong results by design: timing experiments only) --------------------------------------------------------
     "JXGPU_QB_SKIP": ("test", "unset", "skips parts of the Q2 kernel (timing ablation; results are WRONG)", "test_q2_staggered_units_equal_lockstep (the lockstep value 64 only)"),
