@@ -174,7 +174,20 @@ int jxg_eigh_last_dc_windowed(void);
  *   jxg_dsymm_lower_f64:      C = alpha A B + beta C, A (m,m) symmetric with only its lower triangle stored
  *   jxg_dsyr2k_lower_nt_f64:  lower tiles of C (m,m) = alpha A B' + beta C, A, B (m,k)
  *   jxg_sy2st_f64:            dense symmetric -> band (half bandwidth 64) -> tridiagonal (d_d, d_e); d_ab_out (optional,
- *                             128 x n) = the band after stage 1; h_flags[0] / [1] = stage-1 failure / stage-2 abort flag */
+ *                             128 x n) = the band after stage 1; h_flags[0] / [1] = stage-1 failure / stage-2 abort flag
+ *   jxg_sy2st_reflectors_f64: the same, and the reflectors of both stages: d_tau (n) with the columns of d_a below the band
+ *                             (reflector j = [0 (j + 64 rows); 1; A(j + 65 : n, j)], tau = 0: identity), d_v2 (n x n: column s =
+ *                             the reflectors of sweep s by matrix row, unit entry explicit, step k on the rows
+ *                             [s + 1 + 64 k, + min(64, n - that)); only those entries are written) and d_tau2
+ *                             (n x jxg_sb2st_steps(n): [s ks + k], zero where no step exists)
+ *   jxg_sb2st_steps / jxg_eigh_bandwidth: the stride ks of d_tau2 for n rows / the half bandwidth (64)
+ *   jxg_sbback_apply_f64:     C (n x ncols, ld = n) <- Q2 C from reflectors in that layout (n >= 131).  form = -1: the product's
+ *                             own plan; 0 / 1 / 2 / 3: the three-waves-per-unit / one-wave / two-groups-per-pass / balanced kernel
+ *                             with nu 16-column units per slab (1..5 / 4..11 / 4..7 / 4..7; a plan that leaves a slab fewer than
+ *                             nu - 1 units is refused); groups_per_launch = 0: the product's choice.  h_info (optional, 4 ints):
+ *                             form, nu, slabs, apply launches
+ *   jxg_ormtr_apply_f64:      C (n x ncols, ld = n) <- Q1 C, Q1 = H_0 .. H_(nref-1), reflector j = [0 (j + off rows); 1;
+ *                             A(j + off + 1 : n, j)] with d_tau[j] (the eigensolver's call; JXGPU_ORMTR_NB is read per call) */
 int jxg_dgemm_f64(int ta, int tb, int m, int n, int k, double alpha, const double *d_a, int64_t lda, const double *d_b,
                   int64_t ldb, double beta, double *d_c, int64_t ldc, int ksplit, void *stream);
 int jxg_oz_dgemm_f64(int ta, int tb, int m, int n, int k, double alpha, const double *d_a, int64_t lda, const double *d_b,
@@ -190,6 +203,13 @@ int jxg_dsymm_lower_f64(int m, int n, double alpha, const double *d_a, int64_t l
 int jxg_dsyr2k_lower_nt_f64(int m, int k, double alpha, const double *d_a, int64_t lda, const double *d_b, int64_t ldb,
                             double beta, double *d_c, int64_t ldc, void *stream);
 int jxg_sy2st_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, void *stream);
+int jxg_sy2st_reflectors_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, double *d_tau,
+                             double *d_v2, double *d_tau2, void *stream);
+int jxg_sb2st_steps(int n);
+int jxg_eigh_bandwidth(void);
+int jxg_sbback_apply_f64(const double *d_v2, const double *d_tau2, int n, double *d_c, int ncols, int form, int nu,
+                         int groups_per_launch, int *h_info, void *stream);
+int jxg_ormtr_apply_f64(const double *d_a, const double *d_tau, int n, int off, int nref, double *d_c, int ncols, void *stream);
 
 /* Multi-GPU reduce of the partial GRMs (no counterpart in the single-process reference): the lower-triangle
  * tiles (ti >= tj, 128 x 128) of the (npad, npad) f64 accumulator <-> a packed buffer of jxg_tri_tiles_doubles(npad)

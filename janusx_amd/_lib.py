@@ -58,6 +58,11 @@ SIGNATURES = {
     "jxg_dsymm_lower_f64": [c_i, c_i, c_d, c_p, c_l, c_p, c_l, c_d, c_p, c_l, c_p],
     "jxg_dsyr2k_lower_nt_f64": [c_i, c_i, c_d, c_p, c_l, c_p, c_l, c_d, c_p, c_l, c_p],
     "jxg_sy2st_f64": [c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    "jxg_sy2st_reflectors_f64": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "jxg_sb2st_steps": [c_i],
+    "jxg_eigh_bandwidth": [],
+    "jxg_sbback_apply_f64": [c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
+    "jxg_ormtr_apply_f64": [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p],
     "jxg_tri_tiles_doubles": [c_i],
     "jxg_tri_tiles_pack_f64": [c_p, c_i, c_p, c_i, c_p],
     "jxg_symmetrize_f64": [c_p, c_i, c_p],

@@ -1,6 +1,7 @@
 // Symmetric eigendecomposition on the device, replacing LAPACK dsyevd/dsyevr behind src/math/eigh.rs:1422-1528
 // (`symmetric_eigh_f64_row_major_with_driver`): own tridiagonalisation (k_sytrd.hip), divide and conquer (k_stedc.hip)
 // and back-transformation (k_ormtr.hip); rocSOLVER dsyevd below n = 256 or with JXGPU_EIGH=rocsolver.
+// Stage entries at the end of the file: jxg_sy2st_f64 / jxg_sy2st_reflectors_f64, jxg_sbback_apply_f64, jxg_ormtr_apply_f64.
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
@@ -48,6 +49,8 @@ int sb2st_chase(hipStream_t st, double *d_ab, int n, double *d_d, double *d_e, d
 size_t sbback_tq_doubles(int n, int ks);
 int sbback_apply_q2(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols,
                     double *d_tq, hipEvent_t ev_start, hipEvent_t ev_stop);
+int sbback_apply_form(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols, int form,
+                      int nu, int groups_per_launch, int *h_info);
 extern float g_last_ms[24];   // [4] Q2 apply kernel ms, [5] its algorithmic GFLOP, [6] band reduction ms (with the Q1 blocks prepared
                               // beside its last panels), [7] bulge chasing ms, [8] divide and conquer ms, [9] Q1 back-transformation ms
                               // (with the blocks prepared in line only), [10] 1 = two-stage path taken
@@ -587,8 +590,9 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
 // Diagnostic entry (tests, timing scripts): the two reduction stages alone.  d_a (n,n) symmetric f64 is overwritten
 // (band + stage-1 reflectors); d_d / d_e receive the tridiagonal matrix; d_ab_out (optional, 2 SB x n doubles) the band
 // matrix after stage 1; h_flags[0] = stage-1 failure flag, h_flags[1] = stage-2 abort flag.
-extern "C" int jxg_sy2st_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, void *stream) {
-    if (n <= 0) return fail("jxg_sy2st_f64: n must be > 0");
+// (sy2st_run: its body, with the reflectors of both stages as further optional outputs for jxg_sy2st_reflectors_f64)
+static int sy2st_run(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, double *d_tau_out,
+                     double *d_v2_out, double *d_tau2_out, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int ldab = sb2st_ldab(), ks = sb2st_steps(n);
     DevBuf work, ab, tau, v2, tau2, ctrl, flags;
@@ -625,5 +629,52 @@ extern "C" int jxg_sy2st_f64(double *d_a, int n, double *d_d, double *d_e, doubl
         h_flags[0] = hf[0];
         h_flags[1] = habort;
     }
+    if (d_tau_out) JX_HIP(hipMemcpyAsync(d_tau_out, tau.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    if (d_v2_out) JX_HIP(hipMemcpyAsync(d_v2_out, v2.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, st));
+    if (d_tau2_out) JX_HIP(hipMemcpyAsync(d_tau2_out, tau2.p, sizeof(double) * (size_t)n * ks, hipMemcpyDeviceToDevice, st));
+    if (d_tau_out || d_v2_out || d_tau2_out) JX_HIP(hipStreamSynchronize(st));   // the sources are released on return
     return 0;
+}
+
+extern "C" int jxg_sy2st_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, void *stream) {
+    if (n <= 0) return fail("jxg_sy2st_f64: n must be > 0");
+    return sy2st_run(d_a, n, d_d, d_e, d_ab_out, h_flags, nullptr, nullptr, nullptr, stream);
+}
+
+// ---- stage entries of the two back-transformations (tests, timing scripts; tests/test_gpu_backtransform.py) ----------------
+// The reflectors come from the caller, so a stage can be compared with a per-reflector reference without a reduction in
+// front of it.  They hold g_eigh_mu: the Q1 products run in the scratch leases of jxg_eigh_f64.
+
+// jxg_sy2st_f64 that also hands back the reflectors: stage-1 factors d_tau (n; with d_a's columns below the band: reflector j =
+// [0 (j + 64 rows); 1; A(j + 65 : n, j)]), stage-2 vectors d_v2 (n x n, column s = sweep s by matrix row) and factors
+// d_tau2 (n x jxg_sb2st_steps(n): [s ks + k]).
+extern "C" int jxg_sy2st_reflectors_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, double *d_tau,
+                                        double *d_v2, double *d_tau2, void *stream) {
+    if (n <= 0) return fail("jxg_sy2st_reflectors_f64: n must be > 0");
+    if (!d_tau || !d_v2 || !d_tau2) return fail("jxg_sy2st_reflectors_f64: d_tau, d_v2 and d_tau2 are required");
+    std::lock_guard<std::mutex> eigh_lock(g_eigh_mu);
+    return sy2st_run(d_a, n, d_d, d_e, d_ab_out, h_flags, d_tau, d_v2, d_tau2, stream);
+}
+
+extern "C" int jxg_sb2st_steps(int n) { return sb2st_steps(n); }
+extern "C" int jxg_eigh_bandwidth(void) { return sy2sb_bandwidth(); }
+
+// C (n x ncols, ld = n) <- Q2 C from d_v2 / d_tau2 in the layout above.  form = -1: the product's plan; 0 .. 3: the three-waves,
+// one-wave, two-groups or balanced kernel with nu units per slab; groups_per_launch = 0: the product's choice.
+extern "C" int jxg_sbback_apply_f64(const double *d_v2, const double *d_tau2, int n, double *d_c, int ncols, int form, int nu,
+                                    int groups_per_launch, int *h_info, void *stream) {
+    if (!d_v2 || !d_tau2 || !d_c) return fail("jxg_sbback_apply_f64: null pointer");
+    std::lock_guard<std::mutex> eigh_lock(g_eigh_mu);
+    return sbback_apply_form((hipStream_t)stream, d_v2, d_tau2, n, sb2st_steps(n), d_c, ncols, form, nu, groups_per_launch, h_info);
+}
+
+// C (n x ncols, ld = n) <- H_0 H_1 ... H_(nref-1) C, reflector j = [0 (j + off rows); 1; A(j + off + 1 : n, j)] with d_tau[j]
+// (tau = 0: identity): ormtr_lower_off as the eigensolver calls it.
+extern "C" int jxg_ormtr_apply_f64(const double *d_a, const double *d_tau, int n, int off, int nref, double *d_c, int ncols,
+                                   void *stream) {
+    if (!d_a || !d_tau || !d_c) return fail("jxg_ormtr_apply_f64: null pointer");
+    if (n < 2 || off < 1 || nref < 1 || nref + off > n || ncols < 1)
+        return fail("jxg_ormtr_apply_f64: need n >= 2, off >= 1, 1 <= nref <= n - off, ncols >= 1");
+    std::lock_guard<std::mutex> eigh_lock(g_eigh_mu);
+    return ormtr_lower_off((hipStream_t)stream, d_a, n, off, nref, d_tau, d_c, ncols);
 }

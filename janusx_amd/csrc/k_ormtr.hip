@@ -11,6 +11,7 @@
 // base-254 digit planes, exact i32 digit products, f64 combination; 160 - 170 TFLOP/s-equivalent against the 78.6 TFLOP/s f64
 // MFMA roof; V and V T are sliced once per block, C once per block); below, and for the small triangular inverse, the own f64
 // MFMA GEMM (k_dgemm.hip).  No vendor BLAS (rounds 1 - 3: rocBLAS dgemm / dtrsm, 284 ms of the 1.40 s at n = 20 000).
+// Stage entry: jxg_ormtr_apply_f64 (eigh.cpp) is ormtr_lower_off on caller-supplied reflectors (tests/test_gpu_backtransform.py).
 #include <stdlib.h>
 
 #include <algorithm>

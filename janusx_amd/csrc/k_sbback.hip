@@ -7,6 +7,7 @@
 // in scripts/proto_twostage.py): groups descending, inside a group the steps k = 0, 1, ... ascending.  Every row of C is
 // read and written once per group.  (The first version of this round kept the slab rows in an LDS ring and multiplied
 // by T in the kernel: 806 ms at n = 20000 against 588 ms for the register-resident form below; git history.)
+// Stage entry: jxg_sbback_apply_f64 (eigh.cpp) runs every form below on caller-supplied reflectors (tests/test_gpu_backtransform.py).
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 
@@ -1556,13 +1557,20 @@ static int device_cus() {
     return cus;
 }
 
-// register form: launches of <= qr_groups_per_launch groups, from the last group down; ev_start / ev_stop bracket the
-// apply kernels (first / last launch)
 extern float g_last_ms[24];   // [16] apply launches of the last back-transformation, [17] its form: 0 three waves per unit, 1 one
                               // wave per unit, 2 one wave per unit and two groups per pass, 3 balanced (five / four units per CU)
-static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols,
-                               double *d_vu, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    const int ngroups = (n - 2 + QB_G - 1) / QB_G;
+// What one back-transformation launches.  The product computes it from qr_plan, qr_groups_per_launch and the environment
+// (qr_product_form); the stage entry jxg_sbback_apply_f64 can force it (qr_forced_form).
+struct QrForm {
+    int form;               // 0 three waves per unit, 1 one wave per unit, 2 one wave per unit and two groups per pass, 3 balanced
+    int nu;                 // units per slab (the template argument of the apply kernel)
+    int slabs;              // workgroups
+    int units;              // 16-column units dealt over the slabs
+    int gpl;                // groups per launch
+    size_t ct_cols;         // columns of slab storage between the V / U images and the balanced form's third image
+};
+
+static int qr_product_form(int n, int ks, int ncols, QrForm &F) {
     const int gpl = qr_groups_per_launch(n, ks);
     int units = ceil_div(ncols, 16);
     int nu, gslabs;
@@ -1572,26 +1580,52 @@ static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double 
         gslabs = ceil_div(units, nu);
         units = gslabs * nu;
     }
-    {
-        int gn, nun;                                           // the workspace was sized for ncols = n (sbback_tq_doubles)
-        qr_plan(n, &gn, &nun);
-        if ((size_t)gslabs * nu * 16 > std::max((size_t)gn * nun * 16, (size_t)n + 96))
-            return fail("sbback_apply_q2: slab plan exceeds the workspace");
-    }
+    int gn, nun;                                               // the workspace was sized for ncols = n (sbback_tq_doubles)
+    qr_plan(n, &gn, &nun);
+    const size_t ct_cols = std::max((size_t)gn * nun * 16, (size_t)n + 96);
+    if ((size_t)gslabs * nu * 16 > ct_cols) return fail("sbback_apply_q2: slab plan exceeds the workspace");
     const bool bal = qr_bal(ncols) && qr_bal(n) && nu == qr_bal_nu(ncols) && !(getenv("JXGPU_SBBACK_BAL") && atoi(getenv("JXGPU_SBBACK_BAL")) == 0);
     const bool solo = !bal && qr_solo(ncols) && !(getenv("JXGPU_SBBACK_BAL") && atoi(getenv("JXGPU_SBBACK_BAL")) == 0);
+    F = QrForm{bal ? 3 : (solo ? (qr_pair() ? 2 : 1) : 0), nu, gslabs, units, gpl, ct_cols};
+    return 0;
+}
+
+// doubles of workspace the form needs: V / U images of one launch | slabs | third image per block (balanced, five units and more)
+static size_t qr_form_doubles(const QrForm &F, int n, int ks) {
+    return (size_t)F.gpl * ks * (2 + ((F.form == 3 && F.nu >= 5) ? 1 : 0)) * QR_BLK + F.ct_cols * (size_t)(n + 1);
+}
+
+// A forced form: `nu` units per slab over ceil(units / nu) slabs, units dealt evenly as qr_plan deals them.  Refused: whatever
+// the product's plans cannot produce (an instantiation that does not exist, a slab with fewer than nu - 1 units).
+static int qr_forced_form(int n, int ks, int ncols, int form, int nu, int gpl_forced, QrForm &F) {
+    static const int lo[4] = {1, 4, 4, 4}, hi[4] = {5, QR_SOLO_MAX, QR_PAIR_MAX, 7};
+    if (form < 0 || form > 3) return fail("sbback_apply: form must be -1 (the product's plan) or 0 .. 3");
+    if (nu < lo[form] || nu > hi[form])
+        return fail("sbback_apply: form " + std::to_string(form) + " has no kernel for " + std::to_string(nu) + " units per slab");
+    const int units = ceil_div(ncols, 16);
+    const int slabs = ceil_div(units, nu);
+    if (units / slabs < nu - 1)
+        return fail("sbback_apply: " + std::to_string(units) + " units over " + std::to_string(slabs) + " slabs leave a slab with fewer than " +
+                    std::to_string(nu - 1) + " units");
+    const int ngroups = (n - 2 + QB_G - 1) / QB_G;
+    const int gpl = gpl_forced > 0 ? std::min(gpl_forced, ngroups) : qr_groups_per_launch(n, ks);
+    F = QrForm{form, nu, slabs, units, gpl, std::max((size_t)slabs * nu * 16, (size_t)n + 96)};
+    return 0;
+}
+
+// launches of <= F.gpl groups, from the last group down; ev_start / ev_stop bracket the apply kernels (first / last launch)
+static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols,
+                               double *d_vu, hipEvent_t ev_start, hipEvent_t ev_stop, const QrForm &F) {
+    const int ngroups = (n - 2 + QB_G - 1) / QB_G;
+    const int gpl = F.gpl, units = F.units, nu = F.nu, gslabs = F.slabs;
+    const bool bal = F.form == 3, solo = F.form == 1 || F.form == 2, pair = F.form == 2;
     const size_t lds = bal ? sizeof(double) * (6 * (size_t)QR_BLK + 128)
                            : (solo ? sizeof(double) * 4 * (size_t)QR_BLK : sizeof(double) * (4 * (size_t)QR_BLK + (size_t)nu * 3 * 8 * 64));
     const dim3 grid(gslabs);
     const int skip = getenv("JXGPU_QB_SKIP") ? atoi(getenv("JXGPU_QB_SKIP")) : 0;
     const int w = nu * 16;
     double *d_ct = d_vu + (size_t)gpl * ks * 2 * QR_BLK;
-    double *d_um = nullptr;                                    // third image per block of the balanced form: behind the slabs
-    {
-        int gn, nun;
-        qr_plan(n, &gn, &nun);
-        d_um = d_ct + std::max((size_t)gn * nun * 16, (size_t)n + 96) * (size_t)(n + 1);
-    }
+    double *d_um = d_ct + F.ct_cols * (size_t)(n + 1);         // third image per block of the balanced form: behind the slabs
     const dim3 sgrid(ceil_div(n, 64), grid.x);
     const size_t slds = sizeof(double) * 64 * (w + 1);
     {
@@ -1607,7 +1641,7 @@ static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double 
     hipLaunchKernelGGL(sbback_slab_kernel<true>, sgrid, dim3(256), slds, st, d_c, d_ct, n, ncols, w, units);
     JX_LAUNCH_CHECK();
     g_last_ms[16] = (float)ceil_div(ngroups, gpl);
-    g_last_ms[17] = bal ? 3.f : (solo ? (qr_pair() ? 2.f : 1.f) : 0.f);
+    g_last_ms[17] = (float)F.form;
     for (int g_hi = ngroups; g_hi > 0; g_hi -= gpl) {
         const int g_lo = g_hi > gpl ? g_hi - gpl : 0;
         QrParams P{d_v2, d_tau2, d_vu, d_ct, n, ks, ncols, units, g_lo, g_hi, skip, (bal && nu >= 5) ? d_um : nullptr};
@@ -1650,7 +1684,7 @@ static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double 
                 case 7: hipExtLaunchKernelGGL(sbback_apply_bal_kernel<112>, grid, dim3(512), lds, st, e0, e1, 0, P); break;
                 default: return fail("sbback_apply_q2: balanced slab width out of range");
             }
-        } else if (solo && qr_pair()) {
+        } else if (pair) {
 #define JX_QR_PAIR(NWV)                                                                                                \
     do {                                                                                                               \
         static bool attr_set = false;                                                                                  \
@@ -1703,7 +1737,38 @@ static int sbback_apply_q2_reg(hipStream_t st, const double *d_v2, const double 
 int sbback_apply_q2(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols,
                     double *d_tq, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (n <= 2 || ncols <= 0) return 0;
-    return sbback_apply_q2_reg(st, d_v2, d_tau2, n, ks, d_c, ncols, d_tq, ev_start, ev_stop);
+    QrForm F;
+    if (qr_product_form(n, ks, ncols, F)) return 1;
+    return sbback_apply_q2_reg(st, d_v2, d_tau2, n, ks, d_c, ncols, d_tq, ev_start, ev_stop, F);
+}
+
+// Stage entry behind jxg_sbback_apply_f64 (tests, timing scripts): the same launches from caller-supplied reflectors, with the
+// product's own form (form = -1) or a forced one, in a workspace of its own.  Synchronises `st`.
+// h_info (optional, 4 ints): form, units per slab, slabs, apply launches.
+int sbback_apply_form(hipStream_t st, const double *d_v2, const double *d_tau2, int n, int ks, double *d_c, int ncols, int form,
+                      int nu, int groups_per_launch, int *h_info) {
+    if (n < 2 * QB_SB + 3) return fail("sbback_apply: n must be at least " + std::to_string(2 * QB_SB + 3) + " (the smallest two-stage size)");
+    if (ncols < 1 || ncols > n) return fail("sbback_apply: ncols must be in 1 .. n");
+    if (groups_per_launch < 0) return fail("sbback_apply: groups_per_launch must be >= 0");
+    QrForm F;
+    if (form == -1) {
+        if (qr_product_form(n, ks, ncols, F)) return 1;
+        const int ngroups = (n - 2 + QB_G - 1) / QB_G;
+        if (groups_per_launch > 0) F.gpl = std::min(groups_per_launch, ngroups);
+    } else if (qr_forced_form(n, ks, ncols, form, nu, groups_per_launch, F)) {
+        return 1;
+    }
+    DevBuf tq;
+    if (tq.alloc(sizeof(double) * qr_form_doubles(F, n, ks))) return 1;
+    if (sbback_apply_q2_reg(st, d_v2, d_tau2, n, ks, d_c, ncols, tq.as<double>(), nullptr, nullptr, F)) return 1;
+    JX_HIP(hipStreamSynchronize(st));                          // the workspace is released on return
+    if (h_info) {
+        h_info[0] = F.form;
+        h_info[1] = F.nu;
+        h_info[2] = F.slabs;
+        h_info[3] = ceil_div((n - 2 + QB_G - 1) / QB_G, F.gpl);
+    }
+    return 0;
 }
 
 }  // namespace jx

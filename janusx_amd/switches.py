@@ -87,12 +87,12 @@ SWITCHES = {
         "JXGPU_BC_OWNED": "test_bulge_chasing_position_owned_equals_sweep_owned", "JXGPU_SB2ST_WGS": "untested", "JXGPU_GRM_I8_TILE": "test_sparse_grm_row_panels_write_the_same_file, test_clean_rows / test_row_panels / test_rows_with_missing_calls "
                              "of test_gpu_grm_exact.py (128 and 256, the byte-LUT kernel included, bit for bit against numpy)",
         "JXGPU_GRM_TILE": "untested", "JXGPU_GRM_EXACT_BK": "untested", "JXGPU_ROT256": "untested", "JXGPU_SCAN_NOLDS": "untested",
-        "JXGPU_SCAN_NOTILE": "untested", "JXGPU_SBBACK_BAL": "untested", "JXGPU_SBBACK_BAL5": "test_eigh_balanced_q2_forms",
-        "JXGPU_SBBACK_BAL_MIN": "untested", "JXGPU_SBBACK_BAL_PER": "untested", "JXGPU_SBBACK_GROUPS": "untested", "JXGPU_SBBACK_NW": "untested",
-        "JXGPU_SBBACK_PAIR": "untested", "JXGPU_SBBACK_SOLO": "untested", "JXGPU_STEDC_LEAF": "test_eigh_own_divide_and_conquer",
+        "JXGPU_SCAN_NOTILE": "untested", "JXGPU_SBBACK_BAL": "form covered through jxg_sbback_apply_f64 (whole slabs of the three-waves form: test_q2_every_instantiation[reg1..reg5]); the switch itself unread", "JXGPU_SBBACK_BAL5": "test_eigh_balanced_q2_forms; the balanced kernels at small sizes: test_q2_every_instantiation[bal4..bal7], test_q2_balanced_four_column_waves",
+        "JXGPU_SBBACK_BAL_MIN": "form covered through jxg_sbback_apply_f64 (test_q2_every_instantiation[bal4..bal7]); the switch itself unread", "JXGPU_SBBACK_BAL_PER": "form covered through jxg_sbback_apply_f64 (units per slab forced: test_q2_every_instantiation[bal4..bal7], test_q2_balanced_four_column_waves); the switch itself unread", "JXGPU_SBBACK_GROUPS": "form covered through jxg_sbback_apply_f64 (groups per launch forced: test_q2_launch_boundaries); the switch itself unread", "JXGPU_SBBACK_NW": "form covered through jxg_sbback_apply_f64 (test_q2_every_instantiation[reg1..reg5], test_q2_size_edges); the switch itself unread",
+        "JXGPU_SBBACK_PAIR": "form covered through jxg_sbback_apply_f64 (both values: test_q2_every_instantiation[pair4..pair7] and [solo4..solo11]); the switch itself unread", "JXGPU_SBBACK_SOLO": "form covered through jxg_sbback_apply_f64 (test_q2_every_instantiation[solo4..solo11], test_q2_size_edges); the switch itself unread", "JXGPU_STEDC_LEAF": "test_eigh_own_divide_and_conquer",
         "JXGPU_STEDC_OWNLEAF": "untested", "JXGPU_STEDC_PAR": "untested", "JXGPU_STEDC_PARMIN": "untested", "JXGPU_SY2SB_LOOKAHEAD": "untested",
         "JXGPU_SYTRD_KT": "untested", "JXGPU_SYTRD_SYR2K": "untested", "JXGPU_SYTRD_TAIL": "untested", "JXGPU_SYTRD_TARGET": "untested",
-        "JXGPU_DSYMM_SLOTS": "untested", "JXGPU_DSYMM_SPLIT": "untested", "JXGPU_ORMTR_NB": "untested",
+        "JXGPU_DSYMM_SLOTS": "untested", "JXGPU_DSYMM_SPLIT": "untested", "JXGPU_ORMTR_NB": "test_q1_random_reflectors (unset, 64, 256 through jxg_ormtr_apply_f64, against a per-reflector reference)",
         "JXGPU_ROT_I8_DMA": "test_int8_rotation_forms_give_the_same_bits",
         "JXGPU_SCAN_CHAIN_SPLIT": "test_warm_start_chain_kernels_on_rotated_rows_with_invalid_rows",
         "JXGPU_REPACK_WINDOW": "test_repack_of_a_sample_subset_window_form",
@@ -100,7 +100,7 @@ SWITCHES = {
         "JXGPU_DGEMM_WIDE": "tests/test_gpu_dgemm_wide.py (0: 8-byte operand and C accesses in the f64 GEMM family, bit for bit)",
         "JXGPU_KING_TILE": "test_fused_path_finds_every_finite_pair"}.items()},
     # ---- ablation masks (wrong results by design: timing experiments only) --------------------------------------------------------
-    "JXGPU_QB_SKIP": ("test", "unset", "skips parts of the Q2 kernel (timing ablation; results are WRONG)", "test_q2_staggered_units_equal_lockstep (the lockstep value 64 only)"),
+    "JXGPU_QB_SKIP": ("test", "unset", "skips parts of the Q2 kernel (timing ablation; results are WRONG)", "test_q2_staggered_units_equal_lockstep, test_q2_lockstep_units_give_the_bits_of_staggered_units (the lockstep value 64 only)"),
     "JXGPU_BC_SKIP": ("test", "unset", "bulge-chasing ablation (results WRONG)", "untested"),
     "JXGPU_BO_SLEEP": ("test", "unset", "hand-off delay of the bulge chasing (timing)", "untested"),
     # ---- traces, test hooks -------------------------------------------------------------------------------------------------
