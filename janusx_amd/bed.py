@@ -22,6 +22,16 @@ class Bim:
     a0: list  # column 5 (ref_allele -> allele0)
     a1: list  # column 6 (alt_allele -> allele1)
 
+    def columns(self, rows):
+        """(chrom, pos, snp, a0, a1) lists of the rows `rows`, in that order: the leading columns every result-table writer
+        takes."""
+        return tuple([col[j] for j in rows] for col in (self.chrom, self.pos, self.snp, self.a0, self.a1))
+
+    def take(self, rows) -> "Bim":
+        """The table restricted to the rows `rows`, in their order."""
+        chrom, pos, snp, a0, a1 = self.columns(rows)
+        return Bim(chrom, snp, pos, a0, a1)
+
 
 def read_fam_ids(prefix):
     """Sample IDs = FAM column 2 (src/io/gfcore.rs:307-323)."""

@@ -431,8 +431,7 @@ def _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, a
     counts = panel.counts()
     keep, af, _miss = st.gwas_scan_row_stats(counts, n, args.maf, args.geno, args.het)
     rows = np.nonzero(keep)[0]
-    meta = ([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows], [bim.snp[j] for j in rows], [bim.a0[j] for j in rows],
-            [bim.a1[j] for j in rows])
+    meta = bim.columns(rows)
     miss_cnt = counts[rows, 0]
     if run_lm:
         t1 = time.perf_counter()
@@ -487,9 +486,8 @@ def _run_lm_trait_level(packed_t, n_fam, traits, names, samples_of, design_of, y
             counts = panel.counts()
             keep, af, _miss = st.gwas_scan_row_stats(counts, n, args.maf, args.geno, args.het)
             rows = np.nonzero(keep)[0]
-            prefixes = trait_site_prefixes([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows],
-                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in rows],
-                                           [bim.a0[j] for j in rows], [bim.a1[j] for j in rows], af[rows],
+            chrom, pos, snp, a0, a1 = bim.columns(rows)
+            prefixes = trait_site_prefixes(chrom, pos, [resolve_snp_name(*spc) for spc in zip(snp, chrom, pos)], a0, a1, af[rows],
                                            counts[rows, 0].astype(np.float32), as_rate=False)
             y = np.stack([y_of(keep_idx, ti) for ti in members])
             jxrs._lm_traits_group(writer, panel, rows, np.zeros(len(rows), dtype=bool), af[rows], design_of(keep_idx), y,
@@ -535,9 +533,9 @@ def _run_lmm_trait_level(packed_t, n_fam, k, traits, names, samples_of, design_o
                       f"stat={stat:.4g}, p={pv:.4g} >= 0.05); this group goes trait by trait")
                 continue
             rows = np.nonzero(res.keep)[0]
-            prefixes = trait_site_prefixes([bim.chrom[j] for j in rows], [bim.pos[j] for j in rows],
-                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in rows],
-                                           [bim.a0[j] for j in rows], [bim.a1[j] for j in rows], res.af, res.miss, as_rate=True)
+            chrom, pos, snp, a0, a1 = bim.columns(rows)
+            prefixes = trait_site_prefixes(chrom, pos, [resolve_snp_name(*spc) for spc in zip(snp, chrom, pos)], a0, a1, res.af,
+                                           res.miss, as_rate=True)
             for pos_t, ti in enumerate(members):
                 st4 = assoc_trait_stats(res.stats[pos_t])
                 if pmax is None:
@@ -611,13 +609,12 @@ def cmd_gwas(args):
     if getattr(args, "snps_only", False):
         # -snps-only: sites whose two alleles are not single A/C/G/T leave the run altogether -- GRM, QC and scan
         # (`snps_only` of the reference's BED routes, src/io/gfreader.rs:7013-7019)
-        from .bed import Bim, snps_only_mask
+        from .bed import snps_only_mask
         mask = snps_only_mask(bim)
         if not mask.all():
             sel = np.nonzero(mask)[0]
             packed_t = packed_t[torch.from_numpy(sel).to(packed_t.device)]
-            bim = Bim([bim.chrom[j] for j in sel], [bim.snp[j] for j in sel], [bim.pos[j] for j in sel],
-                      [bim.a0[j] for j in sel], [bim.a1[j] for j in sel])
+            bim = bim.take(sel)
             print(f"-snps-only: {len(sel)} of {len(mask)} sites kept")
     packed = packed_t
     fam = read_fam_ids(args.bfile)
@@ -806,9 +803,8 @@ def cmd_gwas(args):
             def open_writer(keep_mask, af_k, miss_k, ncol, model_tag):
                 kept_rows = np.nonzero(keep_mask)[0]
                 wr["path"] = f"{out}.{name}.{model_tag}.tsv"
-                wr["w"] = AsyncAssocTsvWriter(wr["path"], ncol, [bim.chrom[j] for j in kept_rows], [bim.pos[j] for j in kept_rows],
-                                              [bim.snp[j] for j in kept_rows], [bim.a0[j] for j in kept_rows],
-                                              [bim.a1[j] for j in kept_rows], af_k, miss_k, miss_count=(model_tag == "lm"))
+                wr["w"] = AsyncAssocTsvWriter(wr["path"], ncol, *bim.columns(kept_rows), af_k, miss_k,
+                                              miss_count=(model_tag == "lm"))
                 return wr["w"].put
 
             try:
@@ -854,8 +850,7 @@ def cmd_gwas(args):
                 grm_idx = np.array([sparse_pos[fam[j]] for j in keep_idx], dtype=np.int64)
             xc = x[:, 1:] if x.shape[1] > 1 else None
             sidx = keep_idx if (grm_idx is not None or not full) else None
-            meta = ([bim.chrom[j] for j in kept], [bim.pos[j] for j in kept], [bim.snp[j] for j in kept],
-                    [bim.a0[j] for j in kept], [bim.a1[j] for j in kept])
+            meta = bim.columns(kept)
             for stem in sp_stems:
                 t2 = time.perf_counter()
                 path = f"{out}.{name}.{stem}.tsv"
@@ -1258,7 +1253,7 @@ def cmd_gformat(args):
     if rank != 0:                                             # one GPU does the work
         return 0
     from . import janusx as jxrs
-    from .bed import Bim, read_bed_payload, read_fam_ids, write_bed
+    from .bed import read_bed_payload, read_fam_ids, write_bed
     src = jxrs._bed_prefix(args.bfile)
     out = _resolve_out(args, src)
     if os.path.abspath(out) == os.path.abspath(src):
@@ -1273,8 +1268,7 @@ def cmd_gformat(args):
         bim_lines = [ln for ln in fh if len(ln.split()) >= 6]    # the rows `read_bim` keeps
     if len(bim_lines) != len(keep):
         raise SystemExit(f"gformat: {src}.bim has {len(bim_lines)} variant lines, the keep mask {len(keep)} rows")
-    pick = lambda col: [col[i] for i in rows]   # noqa: E731
-    write_bed(out, packed[rows], read_fam_ids(src), Bim(pick(bim.chrom), pick(bim.snp), pick(bim.pos), pick(bim.a0), pick(bim.a1)))
+    write_bed(out, packed[rows], read_fam_ids(src), bim.take(rows))
     # `write_bed` makes the .fam from ids alone and the .bim with a zero map distance: put the input's own lines back
     with open(f"{out}.bim", "w") as fh:
         fh.writelines(bim_lines[i] for i in rows)

@@ -323,8 +323,7 @@ def load_bim_columns(path_or_prefix, row_indices=None):
                 raise ValueError(f"row_indices must be non-negative, got {v}")
             if v >= len(bim.chrom):
                 raise RuntimeError(f"BIM row index out of range: {v} >= {len(bim.chrom)}")
-    return ([bim.chrom[j] for j in sel], [int(bim.pos[j]) for j in sel], [bim.snp[j] for j in sel],
-            [bim.a0[j] for j in sel], [bim.a1[j] for j in sel])
+    return bim.columns(sel)
 
 
 def spgrm_bed_to_jxgrm(prefix, out_prefix=None, sample_indices=None, method=1, threshold=0.05, abs_threshold=False,
@@ -1884,13 +1883,7 @@ def splmm_assoc_pcg_bed_to_tsv(prefix, y, lbd, chrom, pos, snp, allele0, allele1
     m = out.shape[0]
     if not len(chrom):
         from .bed import read_bim
-        bim = read_bim(_bed_prefix(prefix))
-        sel = inp["rows"]
-        chrom = [bim.chrom[j] for j in sel]
-        pos = [bim.pos[j] for j in sel]
-        snp = [bim.snp[j] for j in sel]
-        allele0 = [bim.a0[j] for j in sel]
-        allele1 = [bim.a1[j] for j in sel]
+        chrom, pos, snp, allele0, allele1 = read_bim(_bed_prefix(prefix)).columns(inp["rows"])
     elif not (len(chrom) == len(pos) == len(snp) == len(allele0) == len(allele1) == m):
         raise RuntimeError(f"SparseLMM TSV metadata length mismatch: rows={m}")
     t2 = time.perf_counter()
@@ -2261,6 +2254,77 @@ def rust_blas_set_num_threads(n):
 
 
 # ------------------------------------------------------------------------------------------------
+# argument front end of the association mirrors (LMM, fvLMM, LMM2, LM): each check of the reference written once, the caller
+# passes its name or its message where the reference words a refusal differently
+# ------------------------------------------------------------------------------------------------
+
+def _assoc_check_bounds(low, high):
+    if low >= high:
+        raise RuntimeError("low must be < high")
+
+
+def _assoc_check_tol(tol):
+    if not (np.isfinite(tol) and tol > 0.0):
+        raise RuntimeError("tol must be positive and finite")
+
+
+def _assoc_start(init_log10_lbd, low, high):
+    """Brent's start of the exact scans: a finite `init_log10_lbd` clamped to [low, high], else None (the interval midpoint)."""
+    if init_log10_lbd is not None and np.isfinite(init_log10_lbd):
+        return float(min(max(init_log10_lbd, low), high))
+    return None
+
+
+def _assoc_u_t(u_t, n, msg="u_t must be (n, n) and row-major U^T"):
+    u_t = _c(u_t, np.float32)
+    if u_t.shape != (n, n):
+        raise RuntimeError(msg)
+    return u_t
+
+
+def _assoc_dense_chunk(chunk, n, msg):
+    """A dense SNP-major f32 chunk (rows, n)."""
+    g = _c(chunk, np.float32)
+    if g.ndim != 2 or g.shape[1] != n:
+        raise RuntimeError(msg)
+    return g
+
+
+def _assoc_chunk_args(s, xcov, y_rot, chunk, u_t, what):
+    """The opening of the chunk functions: null model, the chunk `what` against n, U^T against n when the rows are still to be
+    rotated (u_t None: they are rotated already).  -> (s, xcov, y, n, p, chunk f32, u_t f32 | None)."""
+    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
+    g = _assoc_dense_chunk(chunk, n, f"{what} must be (m_chunk, n)")
+    return s, xcov, y, n, p, g, None if u_t is None else _assoc_u_t(u_t, n)
+
+
+def _assoc_fam_positions(fam, sample_ids, shown):
+    """Sample ids -> their positions in the FAM order `fam` (int64); `shown` renders the first id that is not there."""
+    pos = {sid: i for i, sid in enumerate(fam)}
+    for x in sample_ids:
+        if str(x) not in pos:
+            raise RuntimeError(f"sample id not found in FAM: {shown(str(x))}")
+    return np.array([pos[str(x)] for x in sample_ids], dtype=np.int64)
+
+
+def _assoc_prepared_given(row_indices, row_flip, row_missing, row_maf):
+    """Prepared row metadata arrives as all four arrays or none -> whether it is given."""
+    given = [a is not None for a in (row_indices, row_flip, row_missing, row_maf)]
+    if any(given) and not all(given):
+        raise RuntimeError("prepared row metadata must provide all or none of: row_indices, row_flip, row_missing, row_maf")
+    return all(given)
+
+
+def _assoc_check_qc(maf_threshold, max_missing_rate, het_threshold):
+    if not (0.0 <= maf_threshold <= 0.5):
+        raise ValueError("maf_threshold must be within [0, 0.5]")
+    if not (0.0 <= max_missing_rate <= 1.0):
+        raise ValueError("max_missing_rate must be within [0, 1.0]")
+    if not (0.0 <= het_threshold <= 1.0):
+        raise ValueError("het_threshold must be within [0, 1.0]")
+
+
+# ------------------------------------------------------------------------------------------------
 # null model helpers  (src/stats/reml.rs)
 # ------------------------------------------------------------------------------------------------
 
@@ -2275,9 +2339,7 @@ def lmm_rotate_x_y_with_ut_f64(u_t, x, y, threads=0):
         raise RuntimeError("x must be 2D (n, q)")
     if x.shape[0] != n:
         raise RuntimeError(f"x rows must equal len(y): rows={x.shape[0]}, len(y)={n}")
-    u_t = _c(u_t, np.float32)
-    if u_t.ndim != 2 or u_t.shape != (n, n):
-        raise RuntimeError("u_t must be shape (n, n) and row-major U^T")
+    u_t = _assoc_u_t(u_t, n, "u_t must be shape (n, n) and row-major U^T")
     q = int(x.shape[1])
     ox = np.empty((n, q), dtype=np.float64)
     oy = np.empty((n, 1), dtype=np.float64)
@@ -2295,8 +2357,7 @@ def lmm_rotate_y_with_ut_f64(u_t, y, threads=0):
     u_t = _c(u_t, np.float32)
     if u_t.ndim != 2:
         raise RuntimeError("u_t must be 2D (n, n)")
-    if u_t.shape != (n, n):
-        raise RuntimeError("u_t must be shape (n, n) and row-major U^T")
+    u_t = _assoc_u_t(u_t, n, "u_t must be shape (n, n) and row-major U^T")
     x = np.zeros((n, 1), dtype=np.float64)
     ox = np.empty((n, 1), dtype=np.float64)
     oy = np.empty((n, 1), dtype=np.float64)
@@ -2319,8 +2380,7 @@ def _null_args(s, xcov, y_rot):
 def lmm_reml_null_f32(s, xcov, y_rot, low, high, max_iter=50, tol=1e-2):
     """src/stats/reml.rs:570-616 -> (lbd, ml, reml)."""
     s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    if low >= high:
-        raise RuntimeError("low must be < high")
+    _assoc_check_bounds(low, high)
     out = np.zeros(3, dtype=np.float64)
     check(lib().jx_lmm_reml_null(_p(s), _p(xcov), _p(y), n, p, float(low), float(high), int(max_iter), float(tol),
                                  _p(out)))
@@ -2353,16 +2413,8 @@ def _loglike_null(s, xcov, y_rot, log10_lbd):
 # ------------------------------------------------------------------------------------------------
 
 def _chunk(s, xcov, y_rot, low, high, chunk, u_t, max_iter, tol, nullml, what):
-    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    g = _c(chunk, np.float32)
-    if g.ndim != 2 or g.shape[1] != n:
-        raise RuntimeError(f"{what} must be (m_chunk, n)")
-    if u_t is not None:
-        u_t = _c(u_t, np.float32)
-        if u_t.shape != (n, n):
-            raise RuntimeError("u_t must be (n, n) and row-major U^T")
-    if low >= high:
-        raise RuntimeError("low must be < high")
+    s, xcov, y, n, p, g, u_t = _assoc_chunk_args(s, xcov, y_rot, chunk, u_t, what)
+    _assoc_check_bounds(low, high)
     m = int(g.shape[0])
     cols = 4 if nullml is not None else 3
     out = np.zeros((m, cols), dtype=np.float64)
@@ -2399,14 +2451,18 @@ def _resolve_warm_start(warm_start, route_env=None):
     raise RuntimeError("warm_start must be 'chain' or 'none'")
 
 
-def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, model,
-                  low, high, max_iter, tol, warm, init, nullml=None, progress_callback=None, progress_every=0,
-                  genetic_model="add", chain_off=None):
-    """The packed scans of the mirror: model 0 exact per-SNP REML (along `chain_off` when given), 1 fixed lambda at
-    log10 lambda = `low`, 2 LMM2 (needs `nullml`) -> f64 (m, 3 | 4 with nullml | 6 for LMM2).  `pipeline.scan_rows` over a
-    `Panel` of the (row-subsetted) payload with the caller's rotated null model, in blocks of 8192 rows."""
+def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, mode, *,
+                  low=None, high=None, max_iter=0, tol=1e-2, init_log10_lbd=None, log10_lbd=None, nullml=None,
+                  progress_callback=None, progress_every=0, genetic_model="add", chain_off=None):
+    """The packed scans of the mirror: mode "lmm" exact per-SNP REML on [low, high] from `init_log10_lbd` (along `chain_off`
+    when given), "fvlmm" fixed lambda at `log10_lbd`, "lmm2" as "lmm" plus the ML ratio test (needs `nullml`)
+    -> f64 (m, 3 | 4 with nullml | 6 for LMM2).  `pipeline.scan_rows` over a `Panel` of the (row-subsetted) payload with the
+    caller's rotated null model, in blocks of 8192 rows."""
     from . import pipeline as pl
     from .stats import genetic_model_code, scan_lut_from_counts
+    fixed = mode == "fvlmm"
+    if fixed:           # no search: the interval's lower end carries the lambda to the kernel, which starts and stays there
+        low, high, max_iter, tol = float(log10_lbd), float(log10_lbd) + 1.0, 0, 1e-2
     genetic_model_code(genetic_model)               # `PackedGeneticModel::parse` (src/decode/decode.rs:107-119)
     s, xcov, y, n, p = _null_args(s, xcov, y_rot)
     if row_indices is not None:
@@ -2419,15 +2475,12 @@ def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sam
     packed, _pk_ptr, m = _payload(packed, n_samples)           # host array or device tensor
     flip = np.asarray(row_flip).astype(bool).ravel()
     maf = _c(row_maf, np.float32).ravel()
-    u_t = _c(u_t, np.float32)
-    if u_t.shape != (n, n):
-        raise RuntimeError("u_t must be (n, n) and row-major U^T")
+    u_t = _assoc_u_t(u_t, n)
     idx, n_sel = _opt_idx(sample_indices)
     n_eff = n_sel if idx is not None else int(n_samples)
     if n_eff != n:
         raise RuntimeError(f"selected sample count {n_eff} != len(y_rot) {n}")
-    model = int(model)
-    chain = chain_off is not None and model == 0
+    chain = chain_off is not None and mode == "lmm"
     if chain and m > 0:
         co = np.ascontiguousarray(chain_off, dtype=np.int64)
         if co.ndim != 1 or len(co) < 2:
@@ -2436,25 +2489,23 @@ def _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sam
             raise RuntimeError("chain offsets must run from 0 to m")
         if np.any(np.diff(co) < 0):
             raise RuntimeError("chain offsets must ascend")
-    if model not in (0, 1, 2):
-        raise RuntimeError("model must be 0 (lmm), 1 (fvlmm) or 2 (lmm2)")
-    if model == 2 and not (nullml is not None and np.isfinite(nullml)):
+    if mode not in ("lmm", "fvlmm", "lmm2"):
+        raise RuntimeError("mode must be 'lmm', 'fvlmm' or 'lmm2'")
+    if mode == "lmm2" and not (nullml is not None and np.isfinite(nullml)):
         raise RuntimeError("nullml must be finite")
     if int(n_samples) <= 0:
         raise RuntimeError("n_samples must be > 0")
-    if model != 1 and low >= high:
-        raise RuntimeError("low must be < high")
-    if model != 1 and not (np.isfinite(tol) and tol > 0.0):
-        raise RuntimeError("tol must be positive and finite")
+    if not fixed:
+        _assoc_check_bounds(low, high)
+        _assoc_check_tol(tol)
     if m == 0:
-        return np.zeros((0, 6 if model == 2 else (4 if nullml is not None else 3)), dtype=np.float64)
+        return np.zeros((0, 6 if mode == "lmm2" else (4 if nullml is not None else 3)), dtype=np.float64)
     panel = _panel(packed, n_samples, idx)       # of the rows handed: its mean missing-call count picks the rotation path
     sm = pl.SpectralModel.rotated(s, u_t, xcov, y, panel.device)
     lut = scan_lut_from_counts(maf, flip, panel.counts(), n, model=genetic_model)
-    start = float(low) if model == 1 else (float(init) if warm else None)       # fixed lambda: 10 ** low
-    out = pl.scan_rows(panel, sm, np.arange(m), lut, ("lmm", "fvlmm", "lmm2")[model], low=float(low), high=float(high),
-                       max_iter=int(max_iter), tol=float(tol), init_log10_lbd=start, block_rows=8192,
-                       nullml=None if nullml is None else float(nullml), chain_off=co if chain else None,
+    out = pl.scan_rows(panel, sm, np.arange(m), lut, mode, low=float(low), high=float(high), max_iter=int(max_iter),
+                       tol=float(tol), init_log10_lbd=low if fixed else _assoc_start(init_log10_lbd, low, high),
+                       block_rows=8192, nullml=None if nullml is None else float(nullml), chain_off=co if chain else None,
                        progress=progress_callback, progress_every=progress_every)
     return out.cpu().numpy()
 
@@ -2475,21 +2526,17 @@ def lmm_reml_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_r
     warm_start="none": every SNP starts from `init_log10_lbd` when given, else from the midpoint (the core-API contract,
     lmm.rs:1577-1579; what JX_LMM_UNIFIED_NO_WARM_START selects on the BED route)."""
     from .stats import warm_chain_blocks_packed, warm_chain_offsets
-    if low >= high:
-        raise RuntimeError("low must be < high")
-    if not (np.isfinite(tol) and tol > 0):
-        raise RuntimeError("tol must be positive and finite")
-    warm, init = 0, 0.0
-    if init_log10_lbd is not None and np.isfinite(init_log10_lbd):
-        warm, init = 1, float(min(max(init_log10_lbd, low), high))
+    _assoc_check_bounds(low, high)
+    _assoc_check_tol(tol)
     chain_off = None
     if _resolve_warm_start(warm_start, "JX_LMM_UNIFIED_NO_WARM_START") == "chain":
         m_rows = int(len(row_indices)) if row_indices is not None else int(packed.shape[0])
         chain_off = warm_chain_offsets(warm_chain_blocks_packed(m_rows, rotate_block_rows, progress_every), m_rows,
                                        warm_chain_pieces)
-    return _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, 0,
-                         low, high, max_iter, tol, warm, init, nullml, progress_callback, progress_every,
-                         genetic_model=model, chain_off=chain_off)
+    return _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, "lmm",
+                         low=low, high=high, max_iter=max_iter, tol=tol, init_log10_lbd=init_log10_lbd, nullml=nullml,
+                         progress_callback=progress_callback, progress_every=progress_every, genetic_model=model,
+                         chain_off=chain_off)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2497,14 +2544,7 @@ def lmm_reml_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_r
 # ------------------------------------------------------------------------------------------------
 
 def _fv_chunk(s, xcov, y_rot, log10_lbd, chunk, u_t, nullml, what):
-    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    g = _c(chunk, np.float32)
-    if g.ndim != 2 or g.shape[1] != n:
-        raise RuntimeError(f"{what} must be (m_chunk, n)")
-    if u_t is not None:
-        u_t = _c(u_t, np.float32)
-        if u_t.shape != (n, n):
-            raise RuntimeError("u_t must be (n, n) and row-major U^T")
+    s, xcov, y, n, p, g, u_t = _assoc_chunk_args(s, xcov, y_rot, chunk, u_t, what)
     m = int(g.shape[0])
     out = np.zeros((m, 4 if nullml is not None else 3), dtype=np.float64)
     check(lib().jx_fvlmm_assoc_chunk(_p(s), _p(xcov), _p(y), n, p, float(log10_lbd), _p(g), m, _p(u_t),
@@ -2600,9 +2640,7 @@ def fvlmm_assoc_chunk_from_snp_to_tsv_f32(s, xcov, y_rot, log10_lbd, snp_chunk, 
     import tempfile
     from .tsv import _native_rows
     n, _p_cov = _fixed_lambda_checks(s, xcov, y_rot, log10_lbd)
-    g = _c(snp_chunk, np.float32)
-    if g.ndim != 2 or g.shape[1] != n:
-        raise RuntimeError("snp_chunk must be (m, n)")
+    g = _assoc_dense_chunk(snp_chunk, n, "snp_chunk must be (m, n)")
     m = int(g.shape[0])
     if m == 0:
         return [], 0
@@ -2638,9 +2676,9 @@ def fvlmm_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_rot,
                            progress_every=0, rotate_block_rows=512, nullml=None):
     """Array-returning core of `fvlmm_assoc_packed_f32_to_tsv` (src/stats/fvlmm.rs:4958-5190) with a
     caller-rotated null model -> f64 (m, 3 or 4)."""
-    return _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, 1,
-                         float(log10_lbd), float(log10_lbd) + 1.0, 0, 1e-2, 0, 0.0, nullml, progress_callback,
-                         progress_every)
+    return _assoc_packed(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices, row_indices, "fvlmm",
+                         log10_lbd=log10_lbd, nullml=nullml, progress_callback=progress_callback,
+                         progress_every=progress_every)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2658,9 +2696,10 @@ def bed_row_counts(packed, n_samples, sample_indices=None):
 
 
 def _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr, genetic_model, snps_only,
-                     sample_ids, row_indices, row_flip, row_missing, row_maf, mode, low, high, max_iter, tol, nullml,
-                     init_log10_lbd, progress_callback, progress_every=0, mmap_window_mb=None, warm_chain=None):
+                     sample_ids, row_indices, row_flip, row_missing, row_maf, mode, nullml, progress_callback,
+                     progress_every=0, mmap_window_mb=None, warm_chain=None, **scan):
     # warm_chain: None, or (rotate_block_rows, pieces) -- the exact scan along the reference's warm-start chains
+    # scan: the options of `mode` as `_assoc_packed` takes them (low, high, max_iter, tol, init_log10_lbd | log10_lbd)
     import torch
     from . import stats as st
     from .bed import read_fam_ids, snps_only_mask, stage_bed_payload
@@ -2674,23 +2713,12 @@ def _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr
     # payload staged to HBM in windows of `mmap_window_mb` MiB (the reference's WindowedBedMatrix role); the counts, the row
     # gather and the scan below take the device tensor in place
     packed, n_fam, bim = stage_bed_payload(_bed_prefix(bed_prefix), mmap_window_mb)
-    if sample_ids is not None:
-        fam = read_fam_ids(_bed_prefix(bed_prefix))
-        pos = {sid: i for i, sid in enumerate(fam)}
-        try:
-            sidx = np.array([pos[str(x)] for x in sample_ids], dtype=np.int64)
-        except KeyError as e:
-            raise RuntimeError(f"sample id not found in FAM: {e}") from None
-    else:
-        sidx = None
+    sidx = None if sample_ids is None else _assoc_fam_positions(read_fam_ids(_bed_prefix(bed_prefix)), sample_ids, repr)
     n_sel = n_fam if sidx is None else int(sidx.shape[0])
     if n_sel != n:
         raise RuntimeError(f"selected sample count {n_sel} != len(y_rot) {n}")
-    prepared = [row_indices, row_flip, row_missing, row_maf]
-    if any(v is not None for v in prepared) and not all(v is not None for v in prepared):
-        raise RuntimeError("prepared row metadata must provide all or none of: row_indices, row_flip, row_missing, row_maf")
     m = int(packed.shape[0])
-    if row_indices is not None:
+    if _assoc_prepared_given(row_indices, row_flip, row_missing, row_maf):
         rows = np.asarray(row_indices, dtype=np.int64)
         flip = np.asarray(row_flip).astype(bool)
         af = np.asarray(row_maf, dtype=np.float32)
@@ -2707,35 +2735,17 @@ def _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr
     pk = packed if len(rows) == m and np.array_equal(rows, np.arange(m)) else \
         packed[torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(packed.device)]
     del packed
-    if mode == "lmm":
-        warm, init = 0, 0.0
-        if init_log10_lbd is not None and np.isfinite(init_log10_lbd):
-            warm, init = 1, float(min(max(init_log10_lbd, low), high))
-        chain_off = None
-        if warm_chain is not None:
-            from .stats import warm_chain_blocks_bed, warm_chain_offsets
-            # scan units: the prepared row list, or every SNP row of the file (src/stats/lmm.rs:1103-1106, 1121-1145)
-            units = np.arange(len(rows), dtype=np.int64) if row_indices is not None else rows
-            n_units = len(rows) if row_indices is not None else m
-            chain_off = warm_chain_offsets(warm_chain_blocks_bed(units, n_units, warm_chain[0]), len(rows), warm_chain[1])
-        res = _assoc_packed(pk, n_fam, flip, af, s_, xcov_, y_, u_t, sidx, None, 0, low, high, max_iter, tol, warm, init,
-                            nullml, progress_callback, progress_every, genetic_model=genetic_model, chain_off=chain_off)
-    elif mode == "lmm2":
-        warm, init = 0, 0.0
-        if init_log10_lbd is not None and np.isfinite(init_log10_lbd):
-            warm, init = 1, float(min(max(init_log10_lbd, low), high))
-        res = _assoc_packed(pk, n_fam, flip, af, s_, xcov_, y_, u_t, sidx, None, 2, low, high, max_iter, tol, warm, init,
-                            nullml, progress_callback, progress_every, genetic_model=genetic_model)
-    else:
-        res = _assoc_packed(pk, n_fam, flip, af, s_, xcov_, y_, u_t, sidx, None, 1, float(low), float(low) + 1.0, 0,
-                            1e-2, 0, 0.0, nullml, progress_callback, progress_every, genetic_model=genetic_model)
-    chrom = [bim.chrom[j] for j in rows]
-    posv = [bim.pos[j] for j in rows]
-    snp = [bim.snp[j] for j in rows]
-    a0 = [bim.a0[j] for j in rows]
-    a1 = [bim.a1[j] for j in rows]
-    written = write_assoc_tsv(out_tsv, chrom, posv, snp, a0, a1, af, miss, res)
-    return written
+    chain_off = None
+    if warm_chain is not None:
+        from .stats import warm_chain_blocks_bed, warm_chain_offsets
+        # scan units: the prepared row list, or every SNP row of the file (src/stats/lmm.rs:1103-1106, 1121-1145)
+        units = np.arange(len(rows), dtype=np.int64) if row_indices is not None else rows
+        n_units = len(rows) if row_indices is not None else m
+        chain_off = warm_chain_offsets(warm_chain_blocks_bed(units, n_units, warm_chain[0]), len(rows), warm_chain[1])
+    res = _assoc_packed(pk, n_fam, flip, af, s_, xcov_, y_, u_t, sidx, None, mode, nullml=nullml,
+                        progress_callback=progress_callback, progress_every=progress_every, genetic_model=genetic_model,
+                        chain_off=chain_off, **scan)
+    return write_assoc_tsv(out_tsv, *bim.columns(rows), af, miss, res)
 
 
 def lmm_reml_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr,
@@ -2748,15 +2758,14 @@ def lmm_reml_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_
     Warm start: as the reference, the chain is ON unless JX_LMM_UNIFIED_NO_WARM_START is truthy (:2627) or
     warm_start="none"; a chain is the kept rows of one chunk of `rotate_block_rows` scan units (:1121-1145), see
     `lmm_reml_assoc_packed_f32` for the semantics and `warm_chain_pieces`."""
-    if low >= high:
-        raise RuntimeError("low must be < high")
-    if not (np.isfinite(tol) and tol > 0):
-        raise RuntimeError("tol must be positive and finite")
+    _assoc_check_bounds(low, high)
+    _assoc_check_tol(tol)
     chain = _resolve_warm_start(warm_start, "JX_LMM_UNIFIED_NO_WARM_START") == "chain"
     return _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr, genetic_model,
-                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "lmm", low, high,
-                            max_iter, tol, nullml, init_log10_lbd, progress_callback, progress_every, mmap_window_mb,
-                            warm_chain=(int(rotate_block_rows), int(warm_chain_pieces)) if chain else None)
+                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "lmm", nullml,
+                            progress_callback, progress_every, mmap_window_mb,
+                            warm_chain=(int(rotate_block_rows), int(warm_chain_pieces)) if chain else None,
+                            low=low, high=high, max_iter=max_iter, tol=tol, init_log10_lbd=init_log10_lbd)
 
 
 def lmm_reml_lmm2_chunk_from_snp_f32(s, xcov, y_rot, low, high, snp_chunk, u_t, nullml, max_iter=50, tol=1e-2,
@@ -2764,14 +2773,9 @@ def lmm_reml_lmm2_chunk_from_snp_f32(s, xcov, y_rot, low, high, snp_chunk, u_t, 
     """src/stats/lmm.rs:1632-1760 -> f64 (m, 6) = [beta, se, pwald, lambda_reml, ml_alt, plrt] (LMM2: REML Wald test
     plus an ML likelihood-ratio test from a second Brent on `ml_loglike`, lmm.rs:202-330); no warm start."""
     s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    g = _c(snp_chunk, np.float32)
-    if g.ndim != 2 or g.shape[1] != n:
-        raise RuntimeError("snp_chunk must be (m_chunk, n)")
-    u_t = _c(u_t, np.float32)
-    if u_t.shape != (n, n):
-        raise RuntimeError("u_t must be (n, n) and row-major U^T")
-    if low >= high:
-        raise RuntimeError("low must be < high")
+    g = _assoc_dense_chunk(snp_chunk, n, "snp_chunk must be (m_chunk, n)")
+    u_t = _assoc_u_t(u_t, n)                      # required here: LMM2 has no form for rows rotated already
+    _assoc_check_bounds(low, high)
     if not np.isfinite(nullml):
         raise RuntimeError("nullml must be finite")
     m = int(g.shape[0])
@@ -2791,10 +2795,8 @@ def lmm_reml_lmm2_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t,
     (`... pwald lambda ml plrt`, src/io/assoc2tsv.rs:54-56).  Without `nullml` the null ML is fitted first by Brent
     on -ml_loglike seeded with init_log10_lbd_ml or init_log10_lbd_reml (lmm.rs:2902-2921).  Deterministic start per
     SNP: init_log10_lbd_reml, else init_log10_lbd_ml, else the interval midpoint (see `lmm_reml_assoc_packed_f32`)."""
-    if low >= high:
-        raise RuntimeError("low must be < high")
-    if not (np.isfinite(tol) and tol > 0):
-        raise RuntimeError("tol must be positive and finite")
+    _assoc_check_bounds(low, high)
+    _assoc_check_tol(tol)
     if nullml is not None:
         if not np.isfinite(nullml):
             raise RuntimeError("nullml must be finite when provided")
@@ -2810,8 +2812,9 @@ def lmm_reml_lmm2_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t,
             raise RuntimeError("failed to optimize null ML for LMM2 unified scan")
     init_scan = init_log10_lbd_reml if init_log10_lbd_reml is not None else init_log10_lbd_ml
     return _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr, genetic_model,
-                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "lmm2", low, high,
-                            max_iter, tol, nullml_val, init_scan, progress_callback, progress_every, mmap_window_mb)
+                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "lmm2", nullml_val,
+                            progress_callback, progress_every, mmap_window_mb, low=low, high=high, max_iter=max_iter, tol=tol,
+                            init_log10_lbd=init_scan)
 
 
 def fvlmm_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, log10_lbd, u_t, maf_thr, miss_thr, het_thr,
@@ -2820,8 +2823,8 @@ def fvlmm_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, log10_lbd, u
                                rotate_block_rows=512, progress_callback=None, progress_every=0, mmap_window_mb=None):
     """src/stats/fvlmm.rs:2482-2526 (the default `jx gwas -fvlmm` kernel call) -> (rows, pve, log_det_v)."""
     rows = _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr, genetic_model,
-                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "fvlmm",
-                            float(log10_lbd), None, 0, 1e-2, nullml, None, progress_callback, progress_every, mmap_window_mb)
+                            snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "fvlmm", nullml,
+                            progress_callback, progress_every, mmap_window_mb, log10_lbd=float(log10_lbd))
     s_ = np.asarray(s, dtype=np.float64).ravel()
     lbd = 10.0 ** float(log10_lbd)
     vg = float(np.mean(np.clip(s_, 0.0, None)))
@@ -2841,21 +2844,10 @@ def lmm_reml_assoc_packed_f32_to_tsv(packed, n_samples, row_flip, row_maf, row_m
     out = lmm_reml_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_rot, u_t, sample_indices,
                                     row_indices, low, high, max_iter, tol, threads, model, progress_callback,
                                     progress_every, nullml, init_log10_lbd, rotate_block_rows, warm_start, warm_chain_pieces)
-    m = out.shape[0]
     if not len(chrom):
-        if not bed_prefix:
-            raise RuntimeError("metadata lists are empty and bed_prefix is not set")
-        from .bed import read_bim
-        bim = read_bim(bed_prefix)
-        sel = np.arange(m) if row_indices is None else np.asarray(row_indices, dtype=np.int64)
-        chrom = [bim.chrom[j] for j in sel]
-        pos = [bim.pos[j] for j in sel]
-        snp = [bim.snp[j] for j in sel]
-        allele0 = [bim.a0[j] for j in sel]
-        allele1 = [bim.a1[j] for j in sel]
-    written = write_assoc_tsv(out_tsv, chrom, pos, snp, allele0, allele1, np.asarray(row_maf, dtype=np.float32),
-                              np.asarray(row_missing, dtype=np.float32), out, resolve=False)
-    return written
+        chrom, pos, snp, allele0, allele1 = _packed_tsv_bim_columns(bed_prefix, row_indices, out.shape[0])
+    return write_assoc_tsv(out_tsv, chrom, pos, snp, allele0, allele1, np.asarray(row_maf, dtype=np.float32),
+                           np.asarray(row_missing, dtype=np.float32), out, resolve=False)
 
 
 def fvlmm_assoc_packed_f32_to_tsv(packed, n_samples, row_flip, row_maf, row_missing, u, s, y, x, sample_indices,
@@ -2870,22 +2862,17 @@ def fvlmm_assoc_packed_f32_to_tsv(packed, n_samples, row_flip, row_maf, row_miss
     and scans every row at that lambda.  `fixed_ml0` switches the plrt column on."""
     import math
     from .tsv import write_assoc_tsv
-    if fixed_lbd is None and low >= high:
-        raise RuntimeError("low must be < high")
-    if not (np.isfinite(tol) and tol > 0):
-        raise RuntimeError("tol must be positive and finite")
+    if fixed_lbd is None:
+        _assoc_check_bounds(low, high)
+    _assoc_check_tol(tol)
     if not (np.isfinite(tau) and tau >= 0):
         raise RuntimeError("tau must be finite and >= 0")
     if int(n_samples) <= 0:
         raise RuntimeError("n_samples must be > 0")
     from .stats import genetic_model_code
     genetic_model_code(model)                        # add / dom / rec / het (src/decode/decode.rs:100-147); anything else raises
-    packed = _c(packed, np.uint8)
-    if packed.ndim != 2:
-        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
-    if packed.shape[1] != (int(n_samples) + 3) // 4:
-        raise RuntimeError(f"packed second dimension mismatch: got {packed.shape[1]}, expected {(int(n_samples) + 3) // 4}")
-    m = int(packed.shape[0]) if row_indices is None else int(len(row_indices))
+    packed, _pk_ptr, m_all = _payload(packed, n_samples)
+    m = m_all if row_indices is None else int(len(row_indices))
     for name, arr in (("row_flip", row_flip), ("row_maf", row_maf), ("row_missing", row_missing)):
         if len(arr) != m:
             raise RuntimeError(f"{name} length mismatch: got {len(arr)}, expected {m}")
@@ -2951,20 +2938,11 @@ def fvlmm_assoc_packed_f32_to_tsv(packed, n_samples, row_flip, row_maf, row_miss
     if not (np.isfinite(lbd) and lbd > 0):
         raise RuntimeError("invalid fixed lambda in packed fvlmm")
     out = _assoc_packed(packed, n_samples, row_flip, row_maf, s_vec, x_rot, y_rot, u_t,
-                        None if sample_indices is None else sidx, row_indices, 1, math.log10(lbd),
-                        math.log10(lbd) + 1.0, 0, 1e-2, 0, 0.0, float(fixed_ml0) if with_plrt else None,
-                        progress_callback, progress_every, genetic_model=model)
+                        None if sample_indices is None else sidx, row_indices, "fvlmm", log10_lbd=math.log10(lbd),
+                        nullml=float(fixed_ml0) if with_plrt else None, progress_callback=progress_callback,
+                        progress_every=progress_every, genetic_model=model)
     if not len(chrom):
-        if not bed_prefix:
-            raise RuntimeError("metadata lists are empty and bed_prefix is not set")
-        from .bed import read_bim
-        bim = read_bim(bed_prefix)
-        sel = np.arange(m) if row_indices is None else np.asarray(row_indices, dtype=np.int64)
-        chrom = [bim.chrom[j] for j in sel]
-        pos = [bim.pos[j] for j in sel]
-        snp = [bim.snp[j] for j in sel]
-        allele0 = [bim.a0[j] for j in sel]
-        allele1 = [bim.a1[j] for j in sel]
+        chrom, pos, snp, allele0, allele1 = _packed_tsv_bim_columns(bed_prefix, row_indices, m)
     write_assoc_tsv(out_tsv, chrom, pos, snp, allele0, allele1, np.asarray(row_maf, dtype=np.float32),
                     np.asarray(row_missing, dtype=np.float32), out, resolve=False)
     return float(lbd), float(ml0), float(reml0)
@@ -3050,12 +3028,7 @@ def lm_block_assoc_packed(y, x, ixx, packed, n_samples, row_flip, row_maf, sampl
     y = _c(y, np.float64).ravel()
     x = _c(x, np.float64)
     ixx = _c(ixx, np.float64)
-    packed = _c(packed, np.uint8)
-    if packed.ndim != 2:
-        raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
-    m, bps = int(packed.shape[0]), int(packed.shape[1])
-    if bps != (int(n_samples) + 3) // 4:
-        raise RuntimeError(f"packed second dimension mismatch: got {bps}, expected {(int(n_samples) + 3) // 4}")
+    packed, _pk_ptr, m = _payload(packed, n_samples)
     flip = _c(np.asarray(row_flip).astype(np.uint8), np.uint8).ravel()
     maf = _c(row_maf, np.float32).ravel()
     if flip.shape[0] != m:
@@ -3082,18 +3055,19 @@ def lm_block_assoc_packed(y, x, ixx, packed, n_samples, row_flip, row_maf, sampl
     return out.cpu().numpy()
 
 
-def _resolve_assoc_tsv_metadata(bed_prefix, chrom, pos, snp, allele0, allele1, row_indices, expected_len):
+def _resolve_assoc_tsv_metadata(bed_prefix, chrom, pos, snp, allele0, allele1, row_indices, expected_len,
+                                empty_msg="empty TSV metadata requires non-empty bed_prefix"):
     """`resolve_assoc_tsv_metadata` (src/io/assoc2tsv.rs:139-195): all five lists empty -> the BIM columns of `bed_prefix`
-    (rows `row_indices` when given); otherwise every list must have `expected_len` entries."""
+    (rows `row_indices` when given; `empty_msg` when there is no prefix); otherwise every list must have `expected_len`
+    entries."""
     if not any(len(a) for a in (chrom, pos, snp, allele0, allele1)):
-        prefix = (bed_prefix or "").strip()
+        prefix = str(bed_prefix or "").strip()
         if not prefix:
-            raise RuntimeError("empty TSV metadata requires non-empty bed_prefix")
+            raise RuntimeError(empty_msg)
         from .bed import read_bim
         bim = read_bim(_bed_prefix(prefix))
-        sel = range(len(bim.chrom)) if row_indices is None else [int(j) for j in row_indices]
-        chrom, pos, snp = [bim.chrom[j] for j in sel], [int(bim.pos[j]) for j in sel], [bim.snp[j] for j in sel]
-        allele0, allele1 = [bim.a0[j] for j in sel], [bim.a1[j] for j in sel]
+        chrom, pos, snp, allele0, allele1 = bim.columns(range(len(bim.chrom)) if row_indices is None else
+                                                        [int(j) for j in row_indices])
         if len(chrom) != expected_len:
             raise RuntimeError(f"BIM metadata length mismatch: expected={expected_len}, chrom={len(chrom)}, pos={len(pos)}, "
                                f"snp={len(snp)}, allele0={len(allele0)}, allele1={len(allele1)}")
@@ -3104,6 +3078,13 @@ def _resolve_assoc_tsv_metadata(bed_prefix, chrom, pos, snp, allele0, allele1, r
     return chrom, pos, snp, allele0, allele1
 
 
+def _packed_tsv_bim_columns(bed_prefix, row_indices, m):
+    """The empty metadata lists of the packed LMM / fvLMM `_to_tsv` routes: the BIM rows `row_indices`, else the first m."""
+    sel = np.arange(m) if row_indices is None else np.asarray(row_indices, dtype=np.int64)
+    return _resolve_assoc_tsv_metadata(bed_prefix, [], [], [], [], [], sel, m,
+                                       "metadata lists are empty and bed_prefix is not set")
+
+
 def lm_block_assoc_f32(y, x, ixx, g, chunk_size=10000, threads=0):
     """src/stats/glm.rs:4313-4497: the LM formulas of `lm_block_assoc_packed` on an already decoded SNP-major f32 block
     `g` (m, n) (the `LM.gwas` wrapper of python/janusx/pyBLUP/assoc.py:613) -> f64 (m, 4) = beta, se, pwald, plrt."""
@@ -3112,15 +3093,13 @@ def lm_block_assoc_f32(y, x, ixx, g, chunk_size=10000, threads=0):
     y = _c(y, np.float64).ravel()
     x = _c(x, np.float64)
     ixx = _c(ixx, np.float64)
-    g = _c(g, np.float32)
     n = int(y.shape[0])
     if x.ndim != 2 or x.shape[0] != n:
         raise RuntimeError("X.n_rows must equal len(y)")
     q0 = int(x.shape[1])
     if ixx.shape != (q0, q0):
         raise RuntimeError("ixx must be (q0,q0)")
-    if g.ndim != 2 or g.shape[1] != n:
-        raise RuntimeError("g must be shape (m, n)")
+    g = _assoc_dense_chunk(g, n, "g must be shape (m, n)")
     if n <= q0 + 1:
         raise RuntimeError(f"n too small: require n > q0+1, got n={n}, q0={q0}")
     m = int(g.shape[0])
@@ -3141,12 +3120,7 @@ def lm_block_assoc_packed_to_tsv(y, x, ixx, packed, n_samples, row_flip, row_maf
         raise RuntimeError("n_samples must be > 0")
     if int(chunk_size) <= 0:
         raise RuntimeError("chunk_size must be > 0")
-    if not (0.0 <= maf_threshold <= 0.5):
-        raise ValueError("maf_threshold must be within [0, 0.5]")
-    if not (0.0 <= max_missing_rate <= 1.0):
-        raise ValueError("max_missing_rate must be within [0, 1.0]")
-    if not (0.0 <= het_threshold <= 1.0):
-        raise ValueError("het_threshold must be within [0, 1.0]")
+    _assoc_check_qc(maf_threshold, max_missing_rate, het_threshold)
     packed = _c(packed, np.uint8)
     if packed.ndim != 2:
         raise RuntimeError("packed must be 2D (m, bytes_per_snp)")
@@ -3181,12 +3155,7 @@ def _lm_stream_checks(y, x, maf_threshold, max_missing_rate, genetic_model, het_
     (src/stats/glm2.rs:412-440), in the reference's order, before any device call.  -> (y, x)."""
     if int(chunk_size) <= 0:
         raise ValueError("chunk_size must be > 0")
-    if not (0.0 <= maf_threshold <= 0.5):
-        raise ValueError("maf_threshold must be within [0, 0.5]")
-    if not (0.0 <= max_missing_rate <= 1.0):
-        raise ValueError("max_missing_rate must be within [0, 1.0]")
-    if not (0.0 <= het_threshold <= 1.0):
-        raise ValueError("het_threshold must be within [0, 1.0]")
+    _assoc_check_qc(maf_threshold, max_missing_rate, het_threshold)
     model = str(genetic_model).strip().lower()
     if model not in ("add", "dom", "rec", "het"):
         raise ValueError("genetic_model must be one of: add, dom, rec, het")
@@ -3204,11 +3173,8 @@ def _lm_stream_checks(y, x, maf_threshold, max_missing_rate, genetic_model, het_
 def _lm_prepared_meta(row_indices, row_flip, row_missing, row_maf):
     """The prepared row metadata of the LM streaming routes (glm2.rs:487-510, 539-567): all four arrays or none, equal
     lengths, `row_indices` ascending.  -> (row_indices i64, row_flip bool, row_missing f32, row_maf f32) or None."""
-    given = [a is not None for a in (row_indices, row_flip, row_missing, row_maf)]
-    if not any(given):
+    if not _assoc_prepared_given(row_indices, row_flip, row_missing, row_maf):
         return None
-    if not all(given):
-        raise RuntimeError("prepared row metadata must provide all or none of: row_indices, row_flip, row_missing, row_maf")
     ri = _c(row_indices, np.int64).ravel()
     fl = np.asarray(row_flip).astype(bool).ravel()
     mi = _c(row_missing, np.float32).ravel()
@@ -3231,14 +3197,7 @@ def _lm_stream_rows(prefix, n, sample_ids, meta, maf_threshold, max_missing_rate
     from . import lm2
     bed_prefix = _bed_prefix(prefix)
     fam = _bed.read_fam_ids(bed_prefix)
-    if sample_ids is None:
-        idx = None
-    else:
-        pos = {s: i for i, s in enumerate(fam)}
-        missing = [s for s in sample_ids if str(s) not in pos]
-        if missing:
-            raise RuntimeError(f"sample id not found in FAM: {missing[0]}")
-        idx = np.array([pos[str(s)] for s in sample_ids], dtype=np.int64)
+    idx = None if sample_ids is None else _assoc_fam_positions(fam, sample_ids, str)
     n_sel = len(fam) if idx is None else int(idx.shape[0])
     if n_sel != n:
         raise RuntimeError(f"sample_ids length mismatch: selected n={n_sel} but len(y)={n}")
@@ -3268,9 +3227,7 @@ def _lm_stream_rows(prefix, n, sample_ids, meta, maf_threshold, max_missing_rate
     if snps_only:
         ok = _bed.snps_only_mask(bim)[rows]
         rows, flip, af, miss = rows[ok], flip[ok], af[ok], miss[ok]
-    cols = ([bim.chrom[j] for j in rows], [int(bim.pos[j]) for j in rows], [bim.snp[j] for j in rows],
-            [bim.a0[j] for j in rows], [bim.a1[j] for j in rows])
-    return panel, rows, flip, af, miss, cols, total
+    return panel, rows, flip, af, miss, bim.columns(rows), total
 
 
 def lm_stream_bed_to_tsv(prefix, y, x, ixx, out_tsv, sample_ids=None, row_indices=None, row_flip=None, row_missing=None,
@@ -3441,10 +3398,9 @@ def _lmt_run(bed_prefix, n_fam, jobs, out_tsv, progress_callback, mmap_window_mb
                 panel = None                         # one image at a time
                 panel, panel_key = _panel(pk, n_fam, j0["sidx"]), j0["sidx"]
             rows = j0["ri"]
-            sel = [int(j) for j in rows]
-            prefixes = trait_site_prefixes([bim.chrom[j] for j in sel], [bim.pos[j] for j in sel],
-                                           [resolve_snp_name(bim.snp[j], bim.chrom[j], bim.pos[j]) for j in sel],
-                                           [bim.a0[j] for j in sel], [bim.a1[j] for j in sel], j0["mf"], j0["mi"])
+            chrom, pos, snp, a0, a1 = bim.columns(rows)
+            prefixes = trait_site_prefixes(chrom, pos, [resolve_snp_name(*spc) for spc in zip(snp, chrom, pos)], a0, a1,
+                                           j0["mf"], j0["mi"])
             order = iter(grp)
 
             def on_trait(_name):

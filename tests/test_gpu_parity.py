@@ -1658,6 +1658,135 @@ def test_lmm2_routes(oracle, oracle_c, null_case, tmp_path):
         assert abs(float(f[13]) - ref2[i, 5]) <= 3e-4 * ref2[i, 5] + 1e-300
 
 
+def test_packed_scans_and_their_tsv_routes_are_one_scan(tmp_path):
+    """The packed scans, their `_to_tsv` forms and the BED route are one scan behind one argument front end: on a fileset of 41
+    samples (37 selected: the last payload byte is partial either way), 70 variants with a few missing calls and one
+    monomorphic row inside a chain, two covariates and chains of 16 rows, the tables written equal `tsv.write_assoc_tsv` of the
+    arrays returned byte for byte, a device tensor as payload gives the array of the host payload, and the refusals behind the
+    staging of the .bed keep their text."""
+    import torch
+    from janusx_amd import janusx as jxrs
+    from janusx_amd.tsv import write_assoc_tsv
+    rng = np.random.default_rng(41)
+    n_all, m = 41, 70
+    g = rng.binomial(2, rng.uniform(0.1, 0.5, size=(m, 1)), size=(m, n_all)).astype(np.int8)
+    g[[3, 17, 17, 40, 69], [2, 5, 11, 30, 40]] = -1
+    g[33] = 0
+    packed = bed.pack_dosage(g)
+    sidx = np.delete(np.arange(n_all), [4, 13, 22, 36])
+    n = len(sidx)
+    assert (n, packed.shape) == (37, (70, 11))
+    ids = [f"s{i}" for i in range(n_all)]
+    prefix = str(tmp_path / "front")
+    meta = ([str(1 + j // 30) for j in range(m)], [100 + 7 * j for j in range(m)], [f"rs{j}" for j in range(m)],
+            ["A"] * m, ["G"] * m)
+    bed.write_bed(prefix, packed, ids, bed.Bim(meta[0], meta[2], meta[1], meta[3], meta[4]))
+    # eigenpairs of a GRM of the selected samples, descending, as columns of (n_all, n) with the unused samples' rows zero
+    z = g[:, sidx].astype(np.float64)
+    z[z < 0] = np.nan
+    z = np.nan_to_num(z - np.nanmean(z, axis=1, keepdims=True))
+    s_asc, u_cols = np.linalg.eigh(z.T @ z / m + 1e-3 * np.eye(n))
+    s32 = np.ascontiguousarray(s_asc[::-1], dtype=np.float32)
+    u = np.zeros((n_all, n), dtype=np.float32)
+    u[sidx] = u_cols[:, ::-1].astype(np.float32)
+    x0 = rng.standard_normal((n, 2))
+    y = 0.4 * z[5] + 0.3 * x0[:, 0] + rng.standard_normal(n)
+    u_t = np.ascontiguousarray(u[sidx, :n].T)
+    s64 = s32.astype(np.float64)
+    x_rot, y_rot = jxrs.lmm_rotate_x_y_with_ut_f64(u_t, np.concatenate([np.ones((n, 1)), x0], axis=1), y)
+    y_rot = y_rot.ravel()
+    counts = jxrs.bed_row_counts(packed, n_all, sidx).astype(np.float64)
+    called = n - counts[:, 0]
+    maf = ((counts[:, 1] + 2.0 * counts[:, 2]) / (2.0 * called)).astype(np.float32)
+    miss = (counts[:, 0] / n).astype(np.float32)
+    flip = np.zeros(m, dtype=bool)
+    empty = ([], [], [], [], [])
+    null = (s64, x_rot, y_rot, u_t)
+
+    # exact scan along the chains: array, table with the metadata given, table with the metadata read from the BIM
+    chain = dict(low=-4.0, high=4.0, max_iter=40, tol=1e-3, warm_start="chain", rotate_block_rows=16, init_log10_lbd=0.5)
+    arr = jxrs.lmm_reml_assoc_packed_f32(packed, n_all, flip, maf, *null, sample_indices=sidx, warm_chain_pieces=2,
+                                         progress_every=40, **chain)
+    assert arr.shape == (m, 3) and np.isnan(arr[33, 0]) and not np.isnan(np.delete(arr[:, 0], 33)).any()
+    want = str(tmp_path / "lmm.want.tsv")
+    write_assoc_tsv(want, *meta, maf, miss, arr, resolve=False)
+    want = open(want, "rb").read()
+    assert len(want.splitlines()) == m + 1
+    for tag, lists, pfx in (("lists", meta, None), ("bim", empty, prefix)):
+        out = str(tmp_path / f"lmm.{tag}.tsv")
+        rows = jxrs.lmm_reml_assoc_packed_f32_to_tsv(packed, n_all, flip, maf, miss, *null, *lists, out, sample_indices=sidx,
+                                                     warm_chain_pieces=2, progress_every=40, bed_prefix=pfx, **chain)
+        assert rows == m and open(out, "rb").read() == want
+    with pytest.raises(RuntimeError, match="^metadata lists are empty and bed_prefix is not set$"):
+        jxrs.lmm_reml_assoc_packed_f32_to_tsv(packed, n_all, flip, maf, miss, *null, *empty, str(tmp_path / "no.tsv"),
+                                              sample_indices=sidx, **chain)
+    # a row selection (out of order, one row twice): the BIM rows of the selection
+    sel = np.array([69, 3, 33, 3, 40, 17, 0])
+    arr_sel = jxrs.lmm_reml_assoc_packed_f32(packed, n_all, flip[sel], maf[sel], *null, sample_indices=sidx, row_indices=sel,
+                                             **chain)
+    want_sel = str(tmp_path / "sel.want.tsv")
+    write_assoc_tsv(want_sel, *([c[j] for j in sel] for c in meta), maf[sel], miss[sel], arr_sel, resolve=False)
+    out = str(tmp_path / "sel.tsv")
+    assert jxrs.lmm_reml_assoc_packed_f32_to_tsv(packed, n_all, flip[sel], maf[sel], miss[sel], *null, *empty, out,
+                                                 sample_indices=sidx, row_indices=sel, bed_prefix=prefix, **chain) == len(sel)
+    assert open(out, "rb").read() == open(want_sel, "rb").read()
+
+    # the BED route with prepared row metadata: the packed route's bytes on the same rows with the same chains
+    arr1 = jxrs.lmm_reml_assoc_packed_f32(packed, n_all, flip, maf, *null, sample_indices=sidx, **chain)
+    want1 = str(tmp_path / "bed.want.tsv")
+    write_assoc_tsv(want1, *meta, maf, miss, arr1, resolve=False)
+    prepared = dict(row_indices=np.arange(m), row_flip=flip, row_missing=miss, row_maf=maf)
+    out = str(tmp_path / "bed.tsv")
+    picked = [ids[i] for i in sidx]
+    assert jxrs.lmm_reml_assoc_bed_to_tsv_f32(prefix, out, *null[:3], u_t, 0.02, 0.05, 1.0, sample_ids=picked, **prepared,
+                                              **chain) == m
+    assert open(out, "rb").read() == open(want1, "rb").read()
+
+    # fixed lambda: the table of `fvlmm_assoc_packed_f32_to_tsv` is the array of `fvlmm_assoc_packed_f32` at log10(fixed_lbd)
+    lbd, ml0 = 0.37, -61.25
+    for fixed_ml0, cols in ((None, 3), (ml0, 4)):
+        arr_fv = jxrs.fvlmm_assoc_packed_f32(packed, n_all, flip, maf, *null, math.log10(lbd), sample_indices=sidx,
+                                             nullml=fixed_ml0)
+        assert arr_fv.shape == (m, cols) and np.isnan(arr_fv[33, 0])
+        want_fv = str(tmp_path / f"fv{cols}.want.tsv")
+        write_assoc_tsv(want_fv, *meta, maf, miss, arr_fv, resolve=False)
+        for tag, lists, pfx in (("lists", meta, None), ("bim", empty, prefix)):
+            out = str(tmp_path / f"fv{cols}.{tag}.tsv")
+            got = jxrs.fvlmm_assoc_packed_f32_to_tsv(packed, n_all, flip, maf, miss, u, s32, y, x0, sidx, -5.0, 5.0, 50, 1e-3,
+                                                     0.0, 0, "add", *lists, out, fixed_lbd=lbd, fixed_ml0=fixed_ml0,
+                                                     bed_prefix=pfx)
+            assert got[0] == lbd and open(out, "rb").read() == open(want_fv, "rb").read()
+        dev_fv = jxrs.fvlmm_assoc_packed_f32(torch.from_numpy(packed).cuda(), n_all, flip, maf, *null, math.log10(lbd),
+                                             sample_indices=sidx, nullml=fixed_ml0)
+        assert np.array_equal(dev_fv, arr_fv, equal_nan=True)
+    with pytest.raises(RuntimeError, match="^metadata lists are empty and bed_prefix is not set$"):
+        jxrs.fvlmm_assoc_packed_f32_to_tsv(packed, n_all, flip, maf, miss, u, s32, y, x0, sidx, -5.0, 5.0, 50, 1e-3, 0.0, 0,
+                                           "add", *empty, str(tmp_path / "no.tsv"), fixed_lbd=lbd)
+
+    # a payload that is already on the device gives the array of the host payload
+    dev = jxrs.lmm_reml_assoc_packed_f32(torch.from_numpy(packed).cuda(), n_all, flip, maf, *null, sample_indices=sidx,
+                                         warm_chain_pieces=2, progress_every=40, **chain)
+    assert np.array_equal(dev, arr, equal_nan=True)
+    dev_sel = jxrs.lmm_reml_assoc_packed_f32(torch.from_numpy(packed).cuda(), n_all, flip[sel], maf[sel], *null,
+                                             sample_indices=sidx, row_indices=sel, **chain)
+    assert np.array_equal(dev_sel, arr_sel, equal_nan=True)
+
+    # the refusals behind the staging of the .bed
+    def bed_route(**kw):
+        return jxrs.lmm_reml_assoc_bed_to_tsv_f32(prefix, str(tmp_path / "no.tsv"), *null[:3], u_t, 0.02, 0.05, 1.0, **kw)
+
+    for kw, msg in ((dict(sample_ids=picked[:-1]), "selected sample count 36 != len(y_rot) 37"),
+                    (dict(), "selected sample count 41 != len(y_rot) 37"),
+                    (dict(sample_ids=picked[:-1] + ["nobody"]), "sample id not found in FAM: 'nobody'"),
+                    (dict(sample_ids=picked, row_indices=np.arange(m), row_maf=maf),
+                     "prepared row metadata must provide all or none of: row_indices, row_flip, row_missing, row_maf"),
+                    (dict(sample_ids=picked[:-1], row_flip=flip), "selected sample count 36 != len(y_rot) 37")):
+        with pytest.raises(RuntimeError) as info:
+            bed_route(**kw)
+        assert type(info.value) is RuntimeError and str(info.value) == msg
+    assert not os.path.exists(str(tmp_path / "no.tsv"))
+
+
 def test_cli_gs_blup(oracle, tmp_path):
     """`jx gs -bfile ... -BLUP -cv 3`: GRM of all samples, GBLUP per trait on the phenotyped samples, predictions for
     the unphenotyped ones, cross-validated predictions per fold -- against the oracle's `gblup_reml_grm`."""
