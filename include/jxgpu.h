@@ -907,6 +907,29 @@ int jxg_lmt_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq, int ra
                   int trait0, int row0, int32_t *d_hit_trait, int32_t *d_hit_row, double *d_hit_vals, uint64_t *d_count,
                   void *stream);
 
+/* ---- Neighbour-joining tree (`jx tree -nj`; csrc/k_tree.hip; src/stats/tree.rs).
+ *   jxg_tree_counts_p32 : dense n x n int32 pair counts (both triangles, the diagonal included) of a P32 image of biallelic sites, as
+ *                         `pair_mismatch_stats_bitset` (:377-403) counts an alignment whose letters are the two homozygous codes:
+ *                         valid = sites where both samples carry 00 or 11, mismatch = sites where one carries 00 and the other 11
+ *                         (10 = het and 01 = missing are unknown).  Two int8 Grams on the matrix pipes, mismatch = (valid - S) / 2
+ *                         exactly.  same_base != 0: the rows are sites whose two letters are equal: every called sample (00, 10, 11) is
+ *                         known there (`het_iupac` of equal letters is that letter), the site adds to valid alone and mismatch gets 0.  accumulate != 0: add to the stored counts (the second image of one panel).  m <= 2^29 rows.
+ *   jxg_nj_work_bytes   : bytes of d_work for n leaves.
+ *   jxg_nj_run          : exact neighbour joining on the symmetric n x n f64 matrix d_dist (row-major, zero diagonal; consumed), all on
+ *                         the device in stream order.  Join t = 0 .. n - 3 creates node n + t from the nodes d_log_ij[2 t] <
+ *                         d_log_ij[2 t + 1]: the least (q, i, j), q = ((m - 2) d_ij - r_i) - r_j with m active nodes, the row sums
+ *                         r added in ascending node id from 0.0, nothing fused, NaN never the least (no q below +inf: the first two
+ *                         active nodes).  d_log_vals[3 t ..] = d_ij, r_i, r_j.  New distances 0.5 ((d_ik + d_jk) - d_ij), made 0.0 when
+ *                         not finite or not > 0 (keep_negzero = 0, `nj_newick_from_alignment_u8` :7709-7710 with a canonical +0.0) or
+ *                         when not finite or < 0 (keep_negzero != 0, `nj_newick_from_distance_exact` :7134-7137).  The last two nodes:
+ *                         d_log_ij[2 (n - 2) ..] (ascending) and their distance d_last[0].  d_log_ij holds 2 (n - 1) int32,
+ *                         d_log_vals 3 (n - 2) doubles.  Branch lengths and the Newick text are the caller's. */
+int jxg_tree_counts_p32(const uint8_t *d_p32, int64_t m, int n, int same_base, int accumulate, int32_t *d_valid, int32_t *d_mismatch,
+                        void *stream);
+int64_t jxg_nj_work_bytes(int n);
+int jxg_nj_run(double *d_dist, int n, int keep_negzero, int32_t *d_log_ij, double *d_log_vals, double *d_last, void *d_work,
+               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

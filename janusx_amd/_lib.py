@@ -186,12 +186,15 @@ SIGNATURES = {
     "jxg_lmt_prepare": [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     "jxg_lmt_sums_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_l, c_p],
     "jxg_lmt_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_l, c_d, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "jxg_tree_counts_p32": [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p],
+    "jxg_nj_work_bytes": [c_i],
+    "jxg_nj_run": [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,
              "jxg_spgrm_work_bytes": C.c_int64, "jxg_admx_work_bytes": C.c_int64, "jxg_tri_tiles_doubles": C.c_int64, "jx_assoc_tsv_write": C.c_int64,
              "jx_assoc_tsv_append": C.c_int64, "jx_pcg_dist_count": C.c_int64, "jxg_scratch_trim": C.c_int64,
-             "jxg_lmm_series_doubles": C.c_int64, "jxg_sps_work_doubles": C.c_int64}
+             "jxg_lmm_series_doubles": C.c_int64, "jxg_sps_work_doubles": C.c_int64, "jxg_nj_work_bytes": C.c_int64}
 
 
 def lib():

@@ -19,6 +19,8 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
   python -m janusx_amd gformat -bfile PREFIX -prune WINDOW STEP R2 [-o OUT | -o DIR/ -prefix NAME]   (LD pruning; WINDOW: 50, 500kb, 100bp)
   python -m janusx_amd gstats -bfile PREFIX [-freq] [-miss] [-het] [-ldsc [WINDOW]] [-o OUT | -o DIR/ -prefix NAME]
                                  (site / sample QC tables and LD scores; WINDOW: 100, 100kb, 0.1mb, 100000b, 10cm; bare -ldsc: 100kb)
+  python -m janusx_amd tree -bfile PREFIX -nj [exact] [-maf 0.02] [-geno 0.05] [-het 0.02] [-snps-only] [-o OUT | -o DIR/ -prefix NAME]
+                                 [--write-phylip] [--no-fasta]   (neighbour-joining tree: {out}.nwk, {out}.fasta, {out}.phy)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
@@ -1663,6 +1665,45 @@ def cmd_adamixture(args):
     return 0
 
 
+_TREE_NJ_UNBUILT = ("bionj", "bionj-dist", "bionj-jc", "bionj-binom", "bionj-auto", "approx")
+
+
+def cmd_tree(args):
+    """`jx tree -bfile PREFIX -nj [exact]` (python/janusx/script/tree.py:585-720): the sites the chunk loader keeps, their DNA
+    alignment, JC69 distances and the exact neighbour-joining tree -> `{out}.nwk`, `{out}.fasta` (unless --no-fasta, an extension:
+    the alignment is n x sites bytes) and `{out}.phy` with --write-phylip.  The reference's `.log` and `--profile` files are not
+    written; the other NJ modes, -ml and non-BED input are refused."""
+    for flag, what in (("fasta", "-fa"), ("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"tree: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    if args.ml:
+        raise SystemExit("tree: -ml (FastTree maximum likelihood) is not built on this build; use -nj")
+    if not args.bfile:
+        raise SystemExit("tree needs -bfile PREFIX")
+    mode = "exact" if args.nj is None else str(args.nj).strip().lower()
+    if mode in _TREE_NJ_UNBUILT:
+        raise SystemExit(f"tree: -nj {mode} is not built on this build; exact neighbour joining only (-nj or -nj exact)")
+    if mode != "exact":
+        raise SystemExit(f"tree: unknown -nj mode '{args.nj}' (exact; the reference also has {', '.join(_TREE_NJ_UNBUILT)})")
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    from . import janusx as jxrs
+    src = jxrs._bed_prefix(args.bfile)
+    out = _resolve_out(args, src)
+    t0 = time.perf_counter()
+    try:
+        res = jxrs.tree_from_bed(src, args.maf, args.geno, args.het, bool(args.snps_only), out=out,
+                                 write_phylip_file=bool(args.write_phylip), write_fasta_file=not args.no_fasta)
+    except (RuntimeError, ValueError, OSError) as e:
+        raise SystemExit(f"tree: {e}") from None
+    print(f"tree: samples={len(res['sample_ids'])}, sites={res['n_sites']}, NJ mode exact, finished in "
+          f"{time.perf_counter() - t0:.2f} s (the reference's .log and --profile files are not written on this build)")
+    for path in res["outputs"]:
+        print(f"  {path}")
+    return 0
+
+
 def _add_admixture_parser(sub, name):
     a = sub.add_parser(name)
     a.add_argument("-bfile", "--bfile", default=None)
@@ -1862,6 +1903,28 @@ def main(argv=None):
     for flag in ("vcf", "hmp", "file"):
         g.add_argument(f"-{flag}", f"--{flag}", dest=flag, default=None, help=argparse.SUPPRESS)
     g.set_defaults(func=cmd_gstats)
+    t = sub.add_parser("tree")
+    t.add_argument("-bfile", "--bfile", default=None)
+    t.add_argument("-nj", "--nj", nargs="?", const="exact", default=None, metavar="MODE",
+                   help="neighbour joining (the default workflow); MODE: exact (the only one built)")
+    t.add_argument("-ml", "--ml", action="store_true", default=False, help=argparse.SUPPRESS)
+    t.add_argument("-maf", "--maf", type=float, default=0.02)
+    t.add_argument("-geno", "--geno", type=float, default=0.05)
+    t.add_argument("-het", "--het", type=float, default=0.02)
+    t.add_argument("-snps-only", "--snps-only", dest="snps_only", action="store_true", default=False,
+                   help="drop sites whose alleles are not single A/C/G/T")
+    t.add_argument("-o", "--out", default=None)
+    t.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
+    t.add_argument("--write-phylip", dest="write_phylip", action="store_true", default=False,
+                   help="also write the relaxed PHYLIP alignment {out}.phy")
+    t.add_argument("--no-fasta", dest="no_fasta", action="store_true", default=False,
+                   help="do not write {out}.fasta (an extension: the alignment is samples x sites bytes)")
+    t.add_argument("-chunksize", "--chunksize", dest="chunksize", type=int, default=10000, help="accepted for compatibility; unused")
+    t.add_argument("-t", "--thread", "--threads", dest="thread", type=int, default=0, help="accepted for compatibility; unused")
+    for flag in ("fa", "vcf", "hmp", "file"):
+        t.add_argument(f"-{flag}", *(("--fasta",) if flag == "fa" else (f"--{flag}",)), dest="fasta" if flag == "fa" else flag,
+                       default=None, help=argparse.SUPPRESS)
+    t.set_defaults(func=cmd_tree)
     args = ap.parse_args(argv)
     return args.func(args)
 

@@ -6451,3 +6451,11 @@ def write_king_tables(out, ids, n_sites, pairs, kept, removed):
         with open(path, "w", encoding="utf-8") as fh:
             fh.writelines(f"{ids[int(s)]}\n" for s in sel)
     return paths
+
+
+# ------------------------------------------------------------------------------------------------
+# Neighbour-joining tree (src/stats/tree.rs): `jx tree -nj`, in tree.py
+# ------------------------------------------------------------------------------------------------
+from .tree import (geno_chunk_to_alignment_u8, geno_chunk_to_alignment_u8_siteinfo, geno_chunk_to_alignment_u8_sites,  # noqa: E402,F401
+                   nj_merge_log, nj_newick_from_alignment_u8, nj_newick_from_distance_matrix, nj_newick_from_packed,
+                   tree_from_bed, tree_jc69_distance, tree_pair_counts_packed)

@@ -65,6 +65,35 @@ def packed_prep_row_stats(counts: np.ndarray, n: int, maf_thr: float, miss_thr: 
     return keep.astype(bool), miss.astype(np.float32), np.clip(af, F32(0.0), F32(1.0)).astype(np.float32), std
 
 
+def chunk_loader_row_keep(counts: np.ndarray, n: int, maf_thr: float, miss_thr: float, het_thr: float):
+    """Row filter of the chunk loader (`load_genotype_chunks(impute=False, model="add")` over `BedChunkReader`; the rule is
+    `process_snp_row_with_precomputed_counts_impl`, src/io/gfcore.rs:408-480), which `jx tree` reads its sites through:
+    missing rate (1 - nm / n) in f64 cast to f32 and dropped when > the f32 threshold; an all-missing row dropped when the MAF
+    threshold is > 0; the het filter on when the f32 threshold is < 1.0 (`BedChunkReader::new`, src/io/gfreader.rs:3245: not
+    `> 0` as in `packed_prep_row_stats`), het / nm in f64 against the threshold widened to f64; min(af, 1 - af) in f64 cast to f32
+    and dropped when < the f32 threshold.  -> keep (bool), flip (bool: alt frequency > 0.5 in f64, the loader then turns the
+    values round and swaps the two allele strings, :454-462)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    missing, het, hom = counts[:, 0], counts[:, 1], counts[:, 2]
+    maf32, miss32, het32 = F32(maf_thr), F32(miss_thr), F32(het_thr)
+    if n <= 0:
+        return np.zeros(len(missing), dtype=bool), np.zeros(len(missing), dtype=bool)
+    nm = np.maximum(n - missing, 0)
+    has = nm > 0
+    nmf = nm.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        miss_rate = (1.0 - nmf / float(n)).astype(np.float32)
+        keep = ~(miss_rate > miss32)
+        keep &= has | (not bool(maf32 > F32(0.0)))
+        if het32 < F32(1.0):
+            keep &= ~(has & ((het.astype(np.float64) / nmf) > float(het32)))
+        af = (het + 2 * hom).astype(np.float64) / (2.0 * nmf)
+        flip = has & (af > 0.5)
+        maf = np.minimum(af, 1.0 - af).astype(np.float32)
+        keep &= ~(has & (maf < maf32))
+    return keep.astype(bool), flip.astype(bool)
+
+
 def stream_grm_row_prepare(counts: np.ndarray, n_samples: int, method: int, maf_thr: float, miss_thr: float,
                            het_thr: float):
     """-> keep, mean_g (f32), std_scale (f32), flip (bool), var (f64). Thresholds are clamped like
