@@ -290,7 +290,9 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_kernel(const uint8_t *__rest
 // Plane image in LDS: [column][128 bytes], 16-byte chunk index XOR (column >> 1) & 7 (a 16-lane group of a fragment read covers all
 // 64 banks); the DMA writes 1 KB pieces (8 columns) whose lanes pick the source chunk that belongs at their linear position.
 // Same exact i32 sums and the same epilogue as rotate_i8_kernel: the outputs are bit-identical.
-constexpr int RD_BK = 128;                  // samples per step = one payload tile
+// The above is SHAPE 32 (v_mfma_i32_32x32x32_i8); SHAPE 16 (the default: the chip holds a higher clock on it)
+// reads the same images for v_mfma_i32_16x16x64_i8, see in front of the kernel.
+constexpr int RD_BK = 128;                 // samples per step = one payload tile
 constexpr int RD_A = 8 * 1024;              // raw records: piece w = rows 32 w .. + 31, [half][row][16 B]
 constexpr int RD_B = RI_TN * RD_BK;         // one plane
 constexpr int RD_STAGE = RD_A + 3 * RD_B;   // 56 KB
@@ -318,7 +320,36 @@ template <int MODE> __device__ __forceinline__ i32x4 rd_decode(uint32_t w) {
     return r;
 }
 
+// the per-element epilogue of both MFMA shapes: planes combined in f64 in this order, then the row's offset / sign
 template <int MODE>
+__device__ __forceinline__ void rd_store(float *dst, int a0, int a1, int a2, double w1, double w2, double w3, float us, float off,
+                                         float sgn) {
+    const double v = (double)a0 * w1 + (double)a1 * w2 + (double)a2 * w3;
+    if (MODE == 1) *dst = fmaf(off, (float)v, *dst);
+    else *dst = fmaf(off, us, sgn * (float)v);
+}
+
+// SHAPE 16: the same product on v_mfma_i32_16x16x64_i8 (JXGPU_ROT_I8_MFMA, below).  Same workgroup tile, stages, DMA issue,
+// payload and plane images as SHAPE 32.  A 128-sample step is two 64-k products; lane l holds row / column l & 15 and the k
+// quarter kq = l >> 4, and the k slot (product p, quarter kq) is the 16-sample group 4 p + kq of the tile on both operands:
+//   * planes: the chunk (4 p + kq) ^ ((column >> 1) & 7) by ds_read_b128.  The 16 lanes an LDS pass serves together hold the 16
+//     columns of the tile once each, eight of them in quarter kq and eight in kq ^ 1, and those two sets of columns have
+//     disjoint (column >> 1) & 7 ({0, 1, 6, 7} against {2, 3, 4, 5}) whose XOR with kq / kq ^ 1 stays disjoint: all 64 banks,
+//     no conflict (with groups 2 kq + p the two sets would meet in the same chunks);
+//   * payload: the dwords kq and 4 + kq of the row's record (the two halves of the image, 512 B apart): one 64-bit LDS read of
+//     two dwords, 64 consecutive dwords per 16-row fragment and half;
+//   * accumulators i32x4 per 16 x 16 tile: column l & 15, row 4 kq + r (as k_ld.hip / k_pcg_i8.hip read them).
+// Wave tiling RD16_WAVES_M x (8 / RD16_WAVES_M): 4 x 2 = 64 rows x 64 columns per wave (the decode of a row's payload is
+// repeated by two waves instead of four); 2 x 4 = the 128 x 32 of SHAPE 32.
+#ifndef RD16_WAVES_M
+#define RD16_WAVES_M 4
+#endif
+constexpr int RD16_WVM = RD16_WAVES_M, RD16_WVN = 8 / RD16_WVM;
+constexpr int RD16_MT = RI_TM / RD16_WVM / 16, RD16_NT = RI_TN / RD16_WVN / 16;     // 16 x 16 tiles per wave: 4 x 4 or 8 x 2
+static_assert(RD16_WVM == 2 || RD16_WVM == 4, "wave tiling of the 16 x 16 form");
+constexpr int RD_MFMA_DEFAULT = 16;           // shape taken when JXGPU_ROT_I8_MFMA is unset
+
+template <int MODE, int SHAPE>
 __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__restrict__ p32, int64_t m_total,
                                                                const int32_t *__restrict__ rows, int nrows,
                                                                const uint4 *__restrict__ lut16, const float *__restrict__ rowoff,
@@ -331,8 +362,9 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__
     float *sSgn = sOff + RI_TM;
     int *sPos = reinterpret_cast<int *>(sSgn + RI_TM);
 
+    static_assert(SHAPE == 16 || SHAPE == 32, "MFMA shape");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
+    const int wm = SHAPE == 16 ? wave / RD16_WVN : wave >> 2, wn = SHAPE == 16 ? wave % RD16_WVN : wave & 3;
     const int nrt = (nrows + RI_TM - 1) / RI_TM;
     const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
     const int ct = (local / nrt) * 8 + xcd;
@@ -393,65 +425,157 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__
                 rd_glds(qtile + pl * plane + (int64_t)t * RD_BK, boffs[e], st + RD_A + pl * RD_B + (2 * wave + e) * 1024);
     };
 
-    i32x16 acc[3][4];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[pl][mi][r] = 0;
-
-    const int h = lane >> 5, frow = lane & 31;
-    const int afrag = wm * 4 * 1024 + h * 512 + frow * 16;                 // + mi * 1024
-    const int bcol = (wn * 32 + frow) * RD_BK;
-    const int bx0 = (4 * h) ^ ((frow >> 1) & 7);                             // chunk of k slot (ks, h): (bx0 ^ ks)
-
     const int nk = (int)(npad / RD_BK);
-    issue(0, 0);
-    int buf = 0;
-    for (int t = 0; t < nk; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this wave's pieces of step t landed
-        __builtin_amdgcn_s_barrier();                                          // everybody's did, and nobody reads the other stage any more
-        asm volatile("" ::: "memory");
-        issue(t + 1 < nk ? t + 1 : nk - 1, buf ^ 1);                           // past the end: a copy nothing reads
-        const uint8_t *st = rd_smem + buf * RD_STAGE;
-        i32x4 araw[4];
+    if constexpr (SHAPE == 32) {
+        i32x16 acc[3][4];
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) araw[mi] = *reinterpret_cast<const i32x4 *>(st + afrag + mi * 1024);
+        for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            i32x4 b[3];
+            for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-                b[pl] = *reinterpret_cast<const i32x4 *>(st + RD_A + pl * RD_B + bcol + ((bx0 ^ ks) << 4));
+                for (int r = 0; r < 16; ++r) acc[pl][mi][r] = 0;
+
+        const int h = lane >> 5, frow = lane & 31;
+        const int afrag = wm * 4 * 1024 + h * 512 + frow * 16;                 // + mi * 1024
+        const int bcol = (wn * 32 + frow) * RD_BK;
+        const int bx0 = (4 * h) ^ ((frow >> 1) & 7);                             // chunk of k slot (ks, h): (bx0 ^ ks)
+
+        issue(0, 0);
+        int buf = 0;
+        for (int t = 0; t < nk; ++t) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // this wave's pieces of step t landed
+            __builtin_amdgcn_s_barrier();                                          // everybody's did, and nobody reads the other stage any more
+            asm volatile("" ::: "memory");
+            issue(t + 1 < nk ? t + 1 : nk - 1, buf ^ 1);                           // past the end: a copy nothing reads
+            const uint8_t *st = rd_smem + buf * RD_STAGE;
+            i32x4 araw[4];
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                const i32x4 a = rd_decode<MODE>((uint32_t)araw[mi][ks]);
+            for (int mi = 0; mi < 4; ++mi) araw[mi] = *reinterpret_cast<const i32x4 *>(st + afrag + mi * 1024);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                i32x4 b[3];
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    acc[pl][mi] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[pl], acc[pl][mi], 0, 0, 0);
+                    b[pl] = *reinterpret_cast<const i32x4 *>(st + RD_A + pl * RD_B + bcol + ((bx0 ^ ks) << 4));
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) {
+                    const i32x4 a = rd_decode<MODE>((uint32_t)araw[mi][ks]);
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl)
+                        acc[pl][mi] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[pl], acc[pl][mi], 0, 0, 0);
+                }
+            }
+            buf ^= 1;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // no DMA may outlive the workgroup's LDS allocation
+
+        // C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h
+        const int gj = j0 + wn * 32 + frow;
+        const bool colok = gj < n;
+        const double um = colok ? (double)umax[gj] : 0.0;
+        const double w1 = um / 127.0, w2 = um / (127.0 * 254.0), w3 = um / (127.0 * 254.0 * 254.0);
+        const float us = (MODE == 0 && colok) ? usum[gj] : 0.0f;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lr = wm * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int gr = sPos[lr];
+                if (gr >= 0 && colok)
+                    rd_store<MODE>(out + (int64_t)gr * ldo + gj, acc[0][mi][r], acc[1][mi][r], acc[2][mi][r], w1, w2, w3, us, sOff[lr],
+                                   sSgn[lr]);
             }
         }
-        buf ^= 1;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // no DMA may outlive the workgroup's LDS allocation
+    } else {
+        constexpr int MT = RD16_MT, NT = RD16_NT;
+        i32x4 acc[3][MT][NT];
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[pl][mi][ni][r] = 0;
 
-    const int gj = j0 + wn * 32 + frow;
-    const bool colok = gj < n;
-    const double um = colok ? (double)umax[gj] : 0.0;
-    const double w1 = um / 127.0, w2 = um / (127.0 * 254.0), w3 = um / (127.0 * 254.0 * 254.0);
-    const float us = (MODE == 0 && colok) ? usum[gj] : 0.0f;
+        const int kq = lane >> 4, l16 = lane & 15;
+        // fragment mi of the wave = rows 16 mi .. + 15 of its 16 MT rows: piece (mi >> 1), rows 16 (mi & 1) .. of the piece
+        const int afrag = wm * (MT / 2) * 1024 + l16 * 16 + kq * 4;            // + (mi >> 1) * 1024 + (mi & 1) * 256 + p * 512
+        const int bcol = (wn * 16 * NT + l16) * RD_BK;                          // + ni * 16 * RD_BK
+        const int bx0 = kq ^ ((l16 >> 1) & 7);                                   // chunk of k slot (p, kq): bx0 ^ 4 p (16 ni adds nothing)
+
+        issue(0, 0);
+        int buf = 0;
+        for (int t = 0; t < nk; ++t) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            issue(t + 1 < nk ? t + 1 : nk - 1, buf ^ 1);
+            const uint8_t *st = rd_smem + buf * RD_STAGE;
+            uint32_t araw[MT][2];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+            for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int lr = wm * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int gr = sPos[lr];
-            if (gr >= 0 && colok) {
-                const double v = (double)acc[0][mi][r] * w1 + (double)acc[1][mi][r] * w2 + (double)acc[2][mi][r] * w3;
-                float *dst = out + (int64_t)gr * ldo + gj;
-                if (MODE == 1) *dst = fmaf(sOff[lr], (float)v, *dst);
-                else *dst = fmaf(sOff[lr], us, sSgn[lr] * (float)v);
+                for (int p = 0; p < 2; ++p)
+                    araw[mi][p] = *reinterpret_cast<const uint32_t *>(st + afrag + (mi >> 1) * 1024 + (mi & 1) * 256 + p * 512);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                if constexpr (MT <= NT) {
+                    i32x4 a[MT];
+#pragma unroll
+                    for (int mi = 0; mi < MT; ++mi) a[mi] = rd_decode<MODE>(araw[mi][p]);
+#pragma unroll
+                    for (int ni = 0; ni < NT; ++ni) {
+                        i32x4 b[3];
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl)
+                            b[pl] = *reinterpret_cast<const i32x4 *>(st + RD_A + pl * RD_B + bcol + ni * 16 * RD_BK + ((bx0 ^ (4 * p)) << 4));
+#pragma unroll
+                        for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+                            for (int pl = 0; pl < 3; ++pl)
+                                acc[pl][mi][ni] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[mi], b[pl], acc[pl][mi][ni], 0, 0, 0);
+                    }
+                } else {
+                    i32x4 b[NT][3];
+#pragma unroll
+                    for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl)
+                            b[ni][pl] = *reinterpret_cast<const i32x4 *>(st + RD_A + pl * RD_B + bcol + ni * 16 * RD_BK + ((bx0 ^ (4 * p)) << 4));
+#pragma unroll
+                    for (int mi = 0; mi < MT; ++mi) {
+                        const i32x4 a = rd_decode<MODE>(araw[mi][p]);
+#pragma unroll
+                        for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+                            for (int pl = 0; pl < 3; ++pl)
+                                acc[pl][mi][ni] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[ni][pl], acc[pl][mi][ni], 0, 0, 0);
+                    }
+                }
+            }
+            buf ^= 1;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // no DMA may outlive the workgroup's LDS allocation
+
+        // C/D layout of the 16 x 16 shapes: column = lane & 15, row = 4 kq + r
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) {
+            const int gj = j0 + wn * 16 * NT + ni * 16 + l16;
+            const bool colok = gj < n;
+            const double um = colok ? (double)umax[gj] : 0.0;
+            const double w1 = um / 127.0, w2 = um / (127.0 * 254.0), w3 = um / (127.0 * 254.0 * 254.0);
+            const float us = (MODE == 0 && colok) ? usum[gj] : 0.0f;
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int lr = wm * 16 * MT + mi * 16 + 4 * kq + r;
+                    const int gr = sPos[lr];
+                    if (gr >= 0 && colok)
+                        rd_store<MODE>(out + (int64_t)gr * ldo + gj, acc[0][mi][ni][r], acc[1][mi][ni][r], acc[2][mi][ni][r], w1, w2, w3,
+                                       us, sOff[lr], sSgn[lr]);
+                }
             }
         }
     }
@@ -461,6 +585,35 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__
 static bool rot_i8_dma() {
     static const bool on = !(getenv("JXGPU_ROT_I8_DMA") && atoi(getenv("JXGPU_ROT_I8_DMA")) == 0);
     return on;
+}
+
+// MFMA shape of the DMA form: JXGPU_ROT_I8_MFMA=16 | 32 (same bits), read per call: the tests compare both inside one process
+static int rot_i8_mfma() {
+    const char *e = getenv("JXGPU_ROT_I8_MFMA");
+    if (e && atoi(e) == 32) return 32;
+    if (e && atoi(e) == 16) return 16;
+    return RD_MFMA_DEFAULT;
+}
+
+template <int MODE>
+static int launch_rotate_i8_dma(hipStream_t st, dim3 grid, const uint8_t *d_p32, int64_t m_total, const int32_t *d_rows, int nrows,
+                                const uint4 *d_lut16, const float *d_rowoff, const float *d_usum, const int8_t *d_q,
+                                const float *d_umax, int64_t npad, int n, float *d_out, int64_t ld_out, const int32_t *d_sel) {
+    static bool attr = false;
+    const int lds_dma = 2 * RD_STAGE + 3072;
+    if (!attr) {
+        JX_HIP(hipFuncSetAttribute((const void *)rotate_i8_dma_kernel<MODE, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
+        JX_HIP(hipFuncSetAttribute((const void *)rotate_i8_dma_kernel<MODE, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
+        attr = true;
+    }
+    if (rot_i8_mfma() == 16)
+        hipLaunchKernelGGL((rotate_i8_dma_kernel<MODE, 16>), grid, dim3(512), lds_dma, st, d_p32, m_total, d_rows, nrows, d_lut16,
+                           d_rowoff, d_usum, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
+    else
+        hipLaunchKernelGGL((rotate_i8_dma_kernel<MODE, 32>), grid, dim3(512), lds_dma, st, d_p32, m_total, d_rows, nrows, d_lut16,
+                           d_rowoff, d_usum, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
+    JX_LAUNCH_CHECK();
+    return 0;
 }
 
 extern float g_last_ms[24];
@@ -517,18 +670,9 @@ int launch_rotate_i8(hipStream_t st, const uint8_t *d_p32, int64_t m_total, int 
         attr = true;
     }
     dim3 grid((unsigned)(((nct + 7) / 8) * 8 * nrt));
-    if (rot_i8_dma() && m_total < (1LL << 27)) {          // 32-bit byte offsets of the payload records inside a tile
-        static bool attr_dma = false;
-        const int lds_dma = 2 * RD_STAGE + 3072;
-        if (!attr_dma) {
-            JX_HIP(hipFuncSetAttribute((const void *)rotate_i8_dma_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-            attr_dma = true;
-        }
-        hipLaunchKernelGGL(rotate_i8_dma_kernel<0>, grid, dim3(512), lds_dma, st, d_p32, m_total, d_rows, nrows,
-                           (const uint4 *)d_lut16, d_rowoff, d_usum, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
-        JX_LAUNCH_CHECK();
-        return 0;
-    }
+    if (rot_i8_dma() && m_total < (1LL << 27))            // 32-bit byte offsets of the payload records inside a tile
+        return launch_rotate_i8_dma<0>(st, grid, d_p32, m_total, d_rows, nrows, (const uint4 *)d_lut16, d_rowoff, d_usum, d_q, d_umax,
+                                       npad, n, d_out, ld_out, d_sel);
     hipLaunchKernelGGL(rotate_i8_kernel<0>, grid, dim3(512), lds, st, d_p32, m_total, d_rows, nrows, (const uint4 *)d_lut16,
                        d_rowoff, d_usum, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
     JX_LAUNCH_CHECK();
@@ -550,18 +694,9 @@ int launch_rotate_i8_missing(hipStream_t st, const uint8_t *d_p32, int64_t m_tot
         attr = true;
     }
     dim3 grid((unsigned)(((nct + 7) / 8) * 8 * nrt));
-    if (rot_i8_dma() && m_total < (1LL << 27)) {
-        static bool attr_dma = false;
-        const int lds_dma = 2 * RD_STAGE + 3072;
-        if (!attr_dma) {
-            JX_HIP(hipFuncSetAttribute((const void *)rotate_i8_dma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_dma));
-            attr_dma = true;
-        }
-        hipLaunchKernelGGL(rotate_i8_dma_kernel<1>, grid, dim3(512), lds_dma, st, d_p32, m_total, d_rows, nsel,
-                           (const uint4 *)nullptr, d_rowmiss, (const float *)nullptr, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
-        JX_LAUNCH_CHECK();
-        return 0;
-    }
+    if (rot_i8_dma() && m_total < (1LL << 27))
+        return launch_rotate_i8_dma<1>(st, grid, d_p32, m_total, d_rows, nsel, (const uint4 *)nullptr, d_rowmiss, (const float *)nullptr,
+                                       d_q, d_umax, npad, n, d_out, ld_out, d_sel);
     hipLaunchKernelGGL(rotate_i8_kernel<1>, grid, dim3(512), lds, st, d_p32, m_total, d_rows, nsel, (const uint4 *)nullptr,
                        d_rowmiss, (const float *)nullptr, d_q, d_umax, npad, n, d_out, ld_out, d_sel);
     JX_LAUNCH_CHECK();

@@ -94,6 +94,7 @@ SWITCHES = {
         "JXGPU_SYTRD_KT": "untested", "JXGPU_SYTRD_SYR2K": "untested", "JXGPU_SYTRD_TAIL": "untested", "JXGPU_SYTRD_TARGET": "untested",
         "JXGPU_DSYMM_SLOTS": "untested", "JXGPU_DSYMM_SPLIT": "untested", "JXGPU_ORMTR_NB": "test_q1_random_reflectors (unset, 64, 256 through jxg_ormtr_apply_f64, against a per-reflector reference)",
         "JXGPU_ROT_I8_DMA": "test_int8_rotation_forms_give_the_same_bits",
+        "JXGPU_ROT_I8_MFMA": "tests/test_gpu_rotate_i8_mfma.py (16 | 32: MFMA shape of the DMA form of the int8 rotation, bit for bit and against numpy)",
         "JXGPU_SCAN_CHAIN_SPLIT": "test_warm_start_chain_kernels_on_rotated_rows_with_invalid_rows",
         "JXGPU_REPACK_WINDOW": "test_repack_of_a_sample_subset_window_form",
         "JXGPU_SYR2K_PIPE": "test_rank_2k_update_forms_give_the_same_bits",

@@ -1,6 +1,7 @@
 """A/B of the int8 rotation kernels on one block of BASELINE configs[2] rows: prints the time per launch and a digest of the
-rotated block (the two forms of k_rotate_i8.hip must give the same bits).  Run once per value of JXGPU_ROT_I8_DMA (the switch is
-read once per process).  usage: ab_rotate_i8.py [n] [rows] [missing_rate]"""
+rotated block (the forms of k_rotate_i8.hip must give the same bits).  Run once per value of JXGPU_ROT_I8_DMA (the switch is
+read once per process) and of JXGPU_ROT_I8_MFMA (16 | 32: MFMA shape of the DMA form).
+usage: ab_rotate_i8.py [n] [rows] [missing_rate]"""
 import hashlib, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -51,6 +52,7 @@ ts = []
 for _ in range(5):
     e0.record(); run(); e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1))
 ops = 2.0 * len(ex) * n * n * 3 + 2.0 * len(selm) * n * n * 3
-print(f"JXGPU_ROT_I8_DMA={os.environ.get('JXGPU_ROT_I8_DMA', '(default)')} n={n} rows={mk} exact={len(ex)} with_missing_term={len(selm)} "
+print(f"JXGPU_ROT_I8_DMA={os.environ.get('JXGPU_ROT_I8_DMA', '(default)')} "
+      f"JXGPU_ROT_I8_MFMA={os.environ.get('JXGPU_ROT_I8_MFMA', '(default)')} n={n} rows={mk} exact={len(ex)} with_missing_term={len(selm)} "
       f"ms={min(ts):.2f} (median {sorted(ts)[2]:.2f}) int8 POP/s={ops / min(ts) / 1e9:.1f} digest={dig} "
       f"|out|max={float(out.abs().max()):.4f}")
