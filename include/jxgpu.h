@@ -181,6 +181,13 @@ int jxg_eigh_last_dc_windowed(void);
  *                             [s + 1 + 64 k, + min(64, n - that)); only those entries are written) and d_tau2
  *                             (n x jxg_sb2st_steps(n): [s ks + k], zero where no step exists)
  *   jxg_sb2st_steps / jxg_eigh_bandwidth: the stride ks of d_tau2 for n rows / the half bandwidth (64)
+ *   jxg_stedc_f64:            the divide and conquer alone (csrc/k_stedc.hip, for every n >= 4: no rocSOLVER shortcut by size): d_d (n)
+ *                             and d_e (n - 1) hold the tridiagonal matrix, both are overwritten, d_d receives the eigenvalues
+ *                             ascending; d_z is ROW-major, row r = eigenvector of the r-th smallest eigenvalue (the layout the
+ *                             eigensolver hands on): n x n, or with 0 <= sel_lo < sel_hi <= n the (sel_hi - sel_lo) x n rows ranked
+ *                             [sel_lo, sel_hi) -- the top-level merge then forms only those columns, as on the multi-rank path
+ *                             (sel_lo = sel_hi: no window).  leaf <= 0: the product's value (1280, own QL leaves of <= 128 rows),
+ *                             else as jxg_eigh_f64 passes JXGPU_STEDC_LEAF
  *   jxg_sbback_apply_f64:     C (n x ncols, ld = n) <- Q2 C from reflectors in that layout (n >= 131).  form = -1: the product's
  *                             own plan; 0 / 1 / 2 / 3: the three-waves-per-unit / one-wave / two-groups-per-pass / balanced kernel
  *                             with nu 16-column units per slab (1..5 / 4..11 / 4..7 / 4..7; a plan that leaves a slab fewer than
@@ -207,6 +214,7 @@ int jxg_sy2st_reflectors_f64(double *d_a, int n, double *d_d, double *d_e, doubl
                              double *d_v2, double *d_tau2, void *stream);
 int jxg_sb2st_steps(int n);
 int jxg_eigh_bandwidth(void);
+int jxg_stedc_f64(double *d_d, double *d_e, int n, double *d_z, int leaf, int sel_lo, int sel_hi, void *stream);
 int jxg_sbback_apply_f64(const double *d_v2, const double *d_tau2, int n, double *d_c, int ncols, int form, int nu,
                          int groups_per_launch, int *h_info, void *stream);
 int jxg_ormtr_apply_f64(const double *d_a, const double *d_tau, int n, int off, int nref, double *d_c, int ncols, void *stream);

@@ -61,6 +61,7 @@ SIGNATURES = {
     "jxg_sy2st_reflectors_f64": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "jxg_sb2st_steps": [c_i],
     "jxg_eigh_bandwidth": [],
+    "jxg_stedc_f64": [c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_p],
     "jxg_sbback_apply_f64": [c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
     "jxg_ormtr_apply_f64": [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_p],
     "jxg_tri_tiles_doubles": [c_i],

@@ -1,7 +1,8 @@
 // Symmetric eigendecomposition on the device, replacing LAPACK dsyevd/dsyevr behind src/math/eigh.rs:1422-1528
 // (`symmetric_eigh_f64_row_major_with_driver`): own tridiagonalisation (k_sytrd.hip), divide and conquer (k_stedc.hip)
 // and back-transformation (k_ormtr.hip); rocSOLVER dsyevd below n = 256 or with JXGPU_EIGH=rocsolver.
-// Stage entries at the end of the file: jxg_sy2st_f64 / jxg_sy2st_reflectors_f64, jxg_sbback_apply_f64, jxg_ormtr_apply_f64.
+// Stage entries at the end of the file: jxg_sy2st_f64 / jxg_sy2st_reflectors_f64, jxg_stedc_f64, jxg_sbback_apply_f64,
+// jxg_ormtr_apply_f64.
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
@@ -10,6 +11,7 @@
 #include <string.h>
 
 #include <chrono>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -26,6 +28,9 @@ int sytrd_lower(rocblas_handle h, hipStream_t st, double *d_a, int n, double *d_
 int stedc_split(rocblas_handle h, hipStream_t st, int n, double *d_d, double *d_e, double *d_c, int leaf,
                 std::vector<int> &h_perm, int sel_lo = 0, int sel_hi = 0);
 int launch_gather_cols(const double *src, const int *d_perm, int n, double *dst, hipStream_t st);
+int tridiag_normalise(hipStream_t st, int n, double *d_d, double *d_e, int *scale_ex);
+int tridiag_rescale(hipStream_t st, int n, double *d_w, int scale_ex);
+int launch_ldexp(hipStream_t st, double *x, int64_t count, int k);
 void gather_cols_grid(int n, unsigned *gx, unsigned *gy);
 int sytrd_set_dist(int rank, int world, int (*allreduce)(void *), void *user, double *staging, int64_t staging_doubles,
                    int min_n);
@@ -228,10 +233,27 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
     const char *mode = getenv("JXGPU_EIGH");
     const bool use_lib = (n < 256) || (mode && strcmp(mode, "rocsolver") == 0);
     if (use_lib) {
+        // rocSOLVER's dsyevd does not scale its input as LAPACK's does, and its divide and conquer deflates against an absolute
+        // tolerance (measured: 2^-40 tridiag(-1, 2, -1), n = 200: residual 2e-6 ||A||): A goes in with max|a_ij| in [1, 2)
+        int scale_ex = 1;
+        const int64_t nn = (int64_t)n * n;
+        if (nn <= 0x7fffffff) {
+            rocblas_int imax = 0;
+            if (rocblas_idamax(h, (rocblas_int)nn, d_a, 1, &imax) != rocblas_status_success) return fail("rocblas_idamax failed");
+            double amax = 0.0;
+            if (imax >= 1 && imax <= nn) {
+                JX_HIP(hipMemcpyAsync(&amax, d_a + (imax - 1), sizeof(double), hipMemcpyDeviceToHost, st));
+                JX_HIP(hipStreamSynchronize(st));
+            }
+            amax = fabs(amax);
+            if (amax > 0.0 && std::isfinite(amax)) (void)frexp(amax, &scale_ex);
+            if (launch_ldexp(st, d_a, nn, 1 - scale_ex)) return 1;
+        }
         rocblas_status rs = rocsolver_dsyevd(h, rocblas_evect_original, rocblas_fill_lower, n, d_a, n, d_w,
                                              e.as<double>(), info.as<rocblas_int>());
         if (rs != rocblas_status_success)
             return fail("rocsolver_dsyevd failed with status " + std::to_string((int)rs));
+        if (tridiag_rescale(st, n, d_w, scale_ex)) return 1;
     } else {
         // own tridiagonalisation (k_sytrd.hip) + divide & conquer on T (k_stedc.hip) + back-transformation Z = Q C
         DevBuf tau;
@@ -493,10 +515,14 @@ extern "C" int jxg_eigh_f64(double *d_a, int n, double ridge, double *d_w, void 
                 }
             }
         } else {
+            // rocSOLVER's dstedc deflates against an absolute tolerance as the own merges do: T goes in with unit norm
+            int scale_ex = 1;
+            if (tridiag_normalise(st, n, d_w, e.as<double>(), &scale_ex)) return 1;
             rs = rocsolver_dstedc(h, rocblas_evect_tridiagonal, n, d_w, e.as<double>(), c.as<double>(), n,
                                   info.as<rocblas_int>());
             if (rs != rocblas_status_success)
                 return fail("rocsolver_dstedc failed with status " + std::to_string((int)rs));
+            if (tridiag_rescale(st, n, d_w, scale_ex)) return 1;
         }
         JX_HIP(hipEventRecord(ev[3], st));
         if (stage_done("dstedc")) return 1;
@@ -639,6 +665,40 @@ static int sy2st_run(double *d_a, int n, double *d_d, double *d_e, double *d_ab_
 extern "C" int jxg_sy2st_f64(double *d_a, int n, double *d_d, double *d_e, double *d_ab_out, int *h_flags, void *stream) {
     if (n <= 0) return fail("jxg_sy2st_f64: n must be > 0");
     return sy2st_run(d_a, n, d_d, d_e, d_ab_out, h_flags, nullptr, nullptr, nullptr, stream);
+}
+
+// ---- stage entry of the divide and conquer (tests, timing scripts; tests/test_gpu_stedc.py) ---------------------------------
+// T = tridiag(d_d, d_e) in HBM, both overwritten; d_d receives the eigenvalues ascending, d_z (row-major) the eigenvectors: row r
+// = eigenvector of the r-th smallest eigenvalue -- n x n, or with 0 <= sel_lo < sel_hi <= n the (sel_hi - sel_lo) x n rows ranked
+// [sel_lo, sel_hi), the top-level merge forming only those columns as on the multi-rank path.  sel_lo = sel_hi: no window.
+// leaf <= 0: the product's 1280 (own QL leaves of <= 128 rows), else as jxg_eigh_f64 passes JXGPU_STEDC_LEAF.  stedc_split at
+// every n >= 4: no rocSOLVER shortcut by size.
+extern "C" int jxg_stedc_f64(double *d_d, double *d_e, int n, double *d_z, int leaf, int sel_lo, int sel_hi, void *stream) {
+    if (!d_d || !d_e || !d_z) return fail("jxg_stedc_f64: null pointer");
+    if (n < 4) return fail("jxg_stedc_f64: n must be >= 4");
+    const bool windowed = sel_lo != sel_hi;
+    if (windowed && !(0 <= sel_lo && sel_lo < sel_hi && sel_hi <= n))
+        return fail("jxg_stedc_f64: need 0 <= sel_lo < sel_hi <= n (or sel_lo = sel_hi for all eigenvectors)");
+    std::lock_guard<std::mutex> eigh_lock(g_eigh_mu);
+    hipStream_t st = (hipStream_t)stream;
+    rocblas_handle h = get_handle();
+    if (!h) return fail("rocblas_create_handle failed");
+    if (rocblas_set_stream(h, st) != rocblas_status_success) return fail("rocblas_set_stream failed");
+    if (leaf <= 0) leaf = 1280;
+    if (leaf < 2) leaf = 2;
+    if (leaf > kRocsolverStedcMaxN) leaf = kRocsolverStedcMaxN;
+    ScratchLease c;
+    if (c.take(0, sizeof(double) * (size_t)n * (size_t)n)) return 1;
+    std::vector<int> perm;
+    if (stedc_split(h, st, n, d_d, d_e, c.as<double>(), leaf, perm, windowed ? sel_lo : 0, windowed ? sel_hi : 0)) return 1;
+    const int rows = windowed ? sel_hi - sel_lo : n;
+    if ((int)perm.size() != rows) return fail("jxg_stedc_f64: the divide and conquer returned an unexpected column list");
+    DevBuf dperm;
+    if (dperm.alloc(sizeof(int) * (size_t)rows)) return 1;
+    JX_HIP(hipMemcpyAsync(dperm.p, perm.data(), sizeof(int) * (size_t)rows, hipMemcpyHostToDevice, st));
+    if (launch_gather_cols_range(c.as<double>(), dperm.as<int>(), n, rows, d_z, st)) return 1;
+    JX_HIP(hipStreamSynchronize(st));   // the scratch block and the column list are released on return
+    return 0;
 }
 
 // ---- stage entries of the two back-transformations (tests, timing scripts; tests/test_gpu_backtransform.py) ----------------

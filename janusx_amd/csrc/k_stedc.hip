@@ -4,6 +4,12 @@
 // (LAPACK dlaed0/dlaed1 organisation: deflation as in dlaed2, secular equation in the origin-shifted form of dlaed4,
 // eigenvectors from the Gu-Eisenstat / Loewner re-derived z as in dlaed3).  All O(n^2) and O(n^3) work runs on the
 // device; the O(n) deflation scan is host code.
+// Scaling: stedc_split multiplies T on entry by the power of two that brings max(|d|, |e|) into [1, 2) and gives the
+// eigenvalues their scale back on exit (dstedc scales T to unit norm in front of dlaed0 for the same reason: the deflation
+// tolerance 8 eps max(dmax, zmax) compares against the UNIT vector z).  Exact in f64, so T and 2^k T give the same
+// eigenvector bits and eigenvalues that differ by exactly 2^k.  Without it (n = 611) T = 2^-40 tridiag(-1, 2, -1) came back with a
+// residual of 6.7e-6 ||T||, a random T with e < 0 first exceeded the suite's 1e-11 ||T|| at 2^-20 (1.5e-10), and from 2^-52 on
+// every merge found its halves decoupled (tests/test_gpu_stedc.py, docs/EXPERIMENTS.md).  T = 0: eigenvalues 0, eigenvectors I.
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
@@ -22,6 +28,7 @@ namespace jx {
 int dgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, double alpha, const double *a, int64_t lda, const double *b,
           int64_t ldb, double beta, double *c, int64_t ldc, int ksplit, double *ws, size_t ws_doubles);
 int ormtr_oz_min_n();
+int launch_add_diag(double *d_a, int n, int64_t ld, double ridge, hipStream_t st);   // k_misc.hip
 
 constexpr int SD_THREADS = 256;
 constexpr int SD_WAVES = SD_THREADS / 64;
@@ -974,6 +981,38 @@ static int stedc_dc(DcCtx &C, int n, double *d_d, double *d_e, double *d_c, std:
     return 0;
 }
 
+__global__ void sd_ldexp_kernel(double *__restrict__ x, int64_t n, int k) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = ldexp(x[i], k);
+}
+
+// x[0 .. count) *= 2^k, exactly (count < 2^39: one thread per element)
+int launch_ldexp(hipStream_t st, double *x, int64_t count, int k) {
+    if (count <= 0 || k == 0) return 0;
+    hipLaunchKernelGGL(sd_ldexp_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, x, count, k);
+    JX_LAUNCH_CHECK();
+    return 0;
+}
+
+// The normalisation of stedc_split for a caller that hands T to rocSOLVER's dstedc, whose deflation presumes ||T|| ~ 1 in the
+// same way (measured: T = 2^-40 tridiag(-1, 2, -1), n = 611, residual 3.9e-6 ||T||): d_d (n), d_e (n - 1) <- 2^(1 - ex) T with
+// max(|d|, |e|) in [1, 2); tridiag_rescale gives the eigenvalues their scale back.  T = 0 or not finite: ex = 1, nothing changes.
+int tridiag_normalise(hipStream_t st, int n, double *d_d, double *d_e, int *scale_ex) {
+    *scale_ex = 1;
+    std::vector<double> h((size_t)2 * n, 0.0);
+    JX_HIP(hipMemcpyAsync(h.data(), d_d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (n > 1) JX_HIP(hipMemcpyAsync(h.data() + n, d_e, sizeof(double) * (size_t)(n - 1), hipMemcpyDeviceToHost, st));
+    JX_HIP(hipStreamSynchronize(st));
+    double tmax = 0.0;
+    for (double v : h) tmax = std::max(tmax, fabs(v));
+    if (tmax == 0.0 || !std::isfinite(tmax)) return 0;
+    (void)frexp(tmax, scale_ex);
+    if (launch_ldexp(st, d_d, n, 1 - *scale_ex)) return 1;
+    return launch_ldexp(st, d_e, n - 1, 1 - *scale_ex);
+}
+
+int tridiag_rescale(hipStream_t st, int n, double *d_w, int scale_ex) { return launch_ldexp(st, d_w, n, scale_ex - 1); }
+
 // d_d (n), d_e (n-1): tridiagonal T (both overwritten).  d_c: (n,n) column-major, receives the eigenvectors of T as
 // columns in the order given by h_perm (h_perm[r] = column holding the r-th smallest eigenvalue); d_d receives the
 // eigenvalues ascending.  leaf: largest problem handed to rocSOLVER's dstedc.
@@ -985,6 +1024,31 @@ int stedc_split(rocblas_handle h, hipStream_t st, int n, double *d_d, double *d_
     JX_HIP(hipMemcpyAsync(hd.data(), d_d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     JX_HIP(hipMemcpyAsync(he.data(), d_e, sizeof(double) * (size_t)(n - 1), hipMemcpyDeviceToHost, st));
     JX_HIP(hipStreamSynchronize(st));
+    // T is brought to max(|d|, |e|) in [1, 2) by a power of two (exact) and the eigenvalues are scaled back on exit: the
+    // deflation tolerance of a merge, 8 eps max(dmax, zmax) with the unit vector z, presumes ||T|| ~ 1 as LAPACK's dstedc
+    // establishes it before dlaed0.  The eigenvectors do not depend on the factor.  T = 0: eigenvalues 0, eigenvectors I.
+    int scale_ex = 1;   // T = 2^(scale_ex - 1) x the matrix that is decomposed
+    {
+        double tmax = 0.0;
+        for (int i = 0; i < n; ++i) tmax = std::max(tmax, fabs(hd[i]));
+        for (int i = 0; i + 1 < n; ++i) tmax = std::max(tmax, fabs(he[i]));
+        if (tmax == 0.0) {
+            JX_HIP(hipMemsetAsync(d_c, 0, sizeof(double) * (size_t)n * (size_t)n, st));
+            if (launch_add_diag(d_c, n, n, 1.0, st)) return 1;
+            const bool win = sel_hi > sel_lo && sel_lo >= 0 && sel_hi <= n;
+            h_perm.resize((size_t)(win ? sel_hi - sel_lo : n));
+            std::iota(h_perm.begin(), h_perm.end(), win ? sel_lo : 0);
+            JX_HIP(hipStreamSynchronize(st));
+            return 0;
+        }
+        if (std::isfinite(tmax)) (void)frexp(tmax, &scale_ex);
+        if (scale_ex != 1) {
+            for (int i = 0; i < n; ++i) hd[i] = ldexp(hd[i], 1 - scale_ex);
+            for (int i = 0; i + 1 < n; ++i) he[i] = ldexp(he[i], 1 - scale_ex);
+            JX_HIP(hipMemcpyAsync(d_d, hd.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+            JX_HIP(hipMemcpyAsync(d_e, he.data(), sizeof(double) * (size_t)(n - 1), hipMemcpyHostToDevice, st));
+        }
+    }
     // workspace: per level the two half-size eigenvector blocks (n^2/2), their compacted copies when columns were
     // deflated (<= n^2/2) and one U factor at a time (<= n^2/2); the levels below reuse the space above q1/q2, so
     // 2 n^2 doubles cover the recursion; vectors and index lists are O(n) per level
@@ -1092,7 +1156,7 @@ int stedc_split(rocblas_handle h, hipStream_t st, int n, double *d_d, double *d_
     std::iota(h_perm.begin(), h_perm.end(), 0);
     std::sort(h_perm.begin(), h_perm.end(), [&](int a, int b) { return w[a] < w[b] || (w[a] == w[b] && a < b); });
     std::vector<double> ws((size_t)n);
-    for (int r = 0; r < n; ++r) ws[r] = w[h_perm[r]];
+    for (int r = 0; r < n; ++r) ws[r] = ldexp(w[h_perm[r]], scale_ex - 1);   // back to the scale of the input
     if (windowed) {
         // the root problem was a leaf or had nothing to merge (sel_cols empty): the full layout stands, take its window
         if (C.sel_cols.empty()) h_perm.assign(h_perm.begin() + sel_lo, h_perm.begin() + sel_hi);

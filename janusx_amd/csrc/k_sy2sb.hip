@@ -230,27 +230,55 @@ __device__ __forceinline__ void tiny_fetch_colmajor(double (*s)[SB_P], const dou
 // passes 1 and 2: g (pw x pw Gram matrix, column-major ld = SB) -> r_out = R^-1 (SB x SB column-major, identity-padded;
 // G = R'R), rtot <- R rtot (or R in the first pass).  shift_coef > 0:
 // G + shift_coef * trace(G) * I.  *panel_zero is set in the first pass when the panel is exactly zero (trace == 0) and
-// honoured by the later passes.
+// honoured by the later passes.  It is set to 2 when the panel p (nt x pw, ld = ldp) has the reduced form [R; 0] already -- its
+// top pw x pw block upper triangular, every row below exactly zero, as in a matrix whose bandwidth does not exceed SB
+// (tridiagonal, block diagonal with small blocks): such a panel is rank-deficient for CholeskyQR whenever a column of R is zero,
+// and needs no transformation; the later passes treat it like the zero panel (R = I, tau = 0, V = 0) and leave R where it is.
+// A dense panel leaves this test after one load per thread (the entries under the diagonal).
 __global__ __launch_bounds__(256) void sb_chol_kernel(const double *__restrict__ g, int pw, double shift_coef, int first,
                                                       double *__restrict__ r_out, double *__restrict__ rtot,
-                                                      int *__restrict__ flags, int *__restrict__ panel_zero) {
+                                                      int *__restrict__ flags, int *__restrict__ panel_zero,
+                                                      const double *__restrict__ p, int64_t ldp, int nt) {
     __shared__ double s[SB][SB_P];
     __shared__ double s2[SB][SB_P];
     __shared__ TinyVec vec[2];
     __shared__ int zero_sh;
     __shared__ double tr_sh;
     const int t = threadIdx.x;
+    // first filter: the entry under the diagonal of every column (one load per thread, in flight beside the fetch of G; the
+    // barrier below carries its result)
+    bool nz = first && t < nt - 1 && t < pw && p[t + 1 + (int64_t)t * ldp] != 0.0;
     tiny_fetch_colmajor(s, g, pw, true);
     if (!first) {
         for (int e = t; e < SB * SB; e += 256) s2[e / SB][e % SB] = rtot[e];
     }
-    __syncthreads();
+    int any = __syncthreads_or(nz ? 1 : 0);
+    bool reduced = false;
+    if (first && !any) {
+        nz = false;
+        for (int e = t; e < pw * pw; e += 256) {
+            const int c = e / pw, r = e % pw;
+            if (r > c && p[r + (int64_t)c * ldp] != 0.0) nz = true;
+        }
+        any = __syncthreads_or(nz ? 1 : 0);
+        const int nb = nt - pw;                    // rows below the top block, 1024 at a time until one holds a non-zero
+        for (int r0 = 0; r0 < nb && !any; r0 += 1024) {
+            const int rl = (nb - r0 < 1024) ? (nb - r0) : 1024;
+            nz = false;
+            for (int e = t; e < rl * pw; e += 256) {
+                const int c = e / rl, r = e % rl;
+                if (p[pw + r0 + r + (int64_t)c * ldp] != 0.0) nz = true;
+            }
+            any = __syncthreads_or(nz ? 1 : 0);
+        }
+        reduced = !any;
+    }
     if (t == 0) {
         double tr = 0.0;
         for (int i = 0; i < pw; ++i) tr += s[i][i];
         int z = *panel_zero;
         if (first) {
-            z = (tr == 0.0) ? 1 : 0;
+            z = (tr == 0.0) ? 1 : (reduced ? 2 : 0);
             *panel_zero = z;
         }
         zero_sh = z;
@@ -335,14 +363,16 @@ __global__ __launch_bounds__(256) void sb_recon_kernel(const double *__restrict_
     const int t = threadIdx.x;
     const int ti = t >> 4, tk = t & 15;
     if (*panel_zero != 0) {
-        // all-zero panel: identity transformation (tau = 0, V = 0); keep the buffers the next kernels read well-defined
+        // all-zero panel, or one that is [R; 0] already (2: R stays in the top block): identity transformation (tau = 0,
+        // V = 0); keep the buffers the next kernels read well-defined
+        const bool clear_top = (*panel_zero == 1);
         for (int e = t; e < SB * SB; e += 256) {
             const int i = e / SB, k = e % SB;
             u_out[e] = (i == k) ? 1.0 : 0.0;
             t_out[e] = 0.0;
             pan_v1[i + (int64_t)k * ldp] = 0.0;
             pan_v2[i + (int64_t)k * ldp] = 0.0;
-            if (i < pw && k < pw) atop[i + (int64_t)k * lda] = 0.0;
+            if (clear_top && i < pw && k < pw) atop[i + (int64_t)k * lda] = 0.0;
         }
         for (int i = t; i < pw; i += 256) tau[i] = 0.0;
         return;
@@ -648,7 +678,7 @@ int sy2sb_lower(hipStream_t st, double *d_a, int n, double *d_tau, double *d_ab,
                 if (dgemm(s, true, false, pw, pw, nt, 1.0, pp, ld, pp, ld, 0.0, gq, SB, 0, ws, SB_WS)) return 1;
                 const double shift = (pass == 0) ? 11.0 * ((double)nt * pw + (double)pw * (pw + 1)) * eps : 0.0;
                 hipLaunchKernelGGL(sb_chol_kernel, dim3(1), dim3(256), 0, s, gq, pw, shift, pass == 0 ? 1 : 0, rmat, rtot,
-                                   d_flags, pz);
+                                   d_flags, pz, pp, ld, nt);
                 JX_LAUNCH_CHECK();
                 if (dgemm(s, false, false, nt, pw, pw, 1.0, pp, ld, rmat, SB, 0.0, pp, ld, 1, nullptr, 0)) return 1;
             }

@@ -68,7 +68,7 @@ SWITCHES = {
     "JXGPU_DIST_BAND": ("knob", "1", "0: band reduction replicated", "untested"),
     "JXGPU_DIST_BAND_MIN_N": ("knob", "16384", "size from which the band reduction is sharded", "test_sharded_band_reduction_rccl_single_rank"),
     "JXGPU_DIST_BAND_BLOCK": ("test", "auto", "block rows of the sharded band reduction", "test_sharded_band_reduction_rccl_single_rank"),
-    "JXGPU_DIST_DC_WINDOW": ("knob", "1", "0: top-level merge replicated", "untested"),
+    "JXGPU_DIST_DC_WINDOW": ("knob", "1", "0: top-level merge replicated", "form covered through jxg_stedc_f64 (both values: test_column_windows with sel_lo / sel_hi per rank of world 2, 3, 8 and one-column windows, test_full_solve without a window); the switch itself unread"),
     "JXGPU_Q1_TAIL_NT": ("knob", "8192", "trailing size of the band reduction from which complete Q1 reflector blocks are prepared beside "
                          "its last panels (same bits); 0: all of them in line in front of the Q1 products",
                          "test_q1_blocks_prepared_beside_the_band_reduction_give_the_same_bits"),

@@ -3505,8 +3505,9 @@ def test_grm_accumulator_lower_tile_packing():
 def test_eigh_two_stage_path_and_its_fallback(case, monkeypatch):
     """The two-stage reduction (band reduction by CholeskyQR panels, bulge chasing, two back-transformations), forced at a
     small size, on matrices that exercise its special cases: all-zero panels (diagonal input: every reflector is the
-    identity), exactly rank-deficient panels (block-diagonal / low-rank input: the panel factorisation raises its flag
-    and the driver falls back to the one-stage reduction on the saved copy) and a well-conditioned GRM-like matrix."""
+    identity), panels that are in the reduced form [R; 0] already (block-diagonal input with blocks inside the band: identity
+    again), exactly rank-deficient panels (low-rank input: the panel factorisation raises its flag and the driver falls back
+    to the one-stage reduction on the saved copy) and a well-conditioned GRM-like matrix."""
     import torch
     from janusx_amd import pipeline
     monkeypatch.setenv("JXGPU_EIGH", "twostage")

@@ -18,7 +18,10 @@ def _grm_like(n, seed):
 
 
 def _block_diagonal(n, seed):
-    """families of 7, as a thresholded sparse GRM looks: the band reduction flags a rank-deficient panel"""
+    """families of 7, as a thresholded sparse GRM looks, and one pair of relatives 100 samples apart at the end.  The families
+    alone lie inside the band (half bandwidth 64): every panel is in the reduced form [R; 0] already and passes without a flag.
+    The pair puts one entry under the band of column n - 101, so its panel has a single non-zero column beside the corner of R:
+    exactly rank-deficient and not reduced, which the band reduction flags."""
     import torch
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev)
@@ -28,6 +31,7 @@ def _block_diagonal(n, seed):
         b1 = min(n, b0 + 7)
         z = torch.randn((b1 - b0, 20), generator=g, device=dev, dtype=torch.float64)
         k[b0:b1, b0:b1] = z @ z.T / 20
+    k[n - 1, n - 101] = k[n - 101, n - 1] = 0.25      # inside the last 192 rows, which the one-stage reduction finishes in one workgroup
     return 0.5 * (k + k.T)
 
 
