@@ -938,6 +938,27 @@ int64_t jxg_nj_work_bytes(int n);
 int jxg_nj_run(double *d_dist, int n, int keep_negzero, int32_t *d_log_ij, double *d_log_vals, double *d_last, void *d_work,
                void *stream);
 
+/* ---- Joint SNP-pair interaction test under the fixed-lambda LMM (`jx fvlmm2`; csrc/k_fvlmm2.hip; src/stats/fvlmm2.rs:37-290).
+ *   jxg_fvlmm2_combo_p32 : for pair r over the n selected samples of a P32 image, with c1 / c2 the 2-bit codes of the records
+ *                          d_rows1[r] / d_rows2[r]:  d_g1[r][i] = d_lut1[r][c1],  d_g2[r][i] = d_lut2[r][c2],
+ *                          d_gc[r][i] = d_tab[r][4 c1 + c2]  (three (nrows, ld >= n) f32 blocks; d_lut1, d_lut2
+ *                          (nrows, 4) and d_tab (nrows, 16) f32 built by the host: decoded rows, literals and the combo of
+ *                          python/janusx/script/fvlmm2.py:306-385 are functions of the two codes alone).  d_counts[r] = number of
+ *                          samples whose literal 1, literal 2, combo value is > 0, by the masks d_pos[r]: bit c1 (literal 1), bit
+ *                          4 + c2 (literal 2), bit 8 + 4 c1 + c2 (combo).  A record index outside [0, m_total) gives a NaN row.
+ *   jxg_fvlmm2_joint     : `fvlmm2_assoc_chunk_f32` on device rows used as given: d_out (nrows, 9) f64 = (beta, se, p) of g1, g2
+ *                          and the combo in  y ~ xcov + g1 + g2 + gc  with weights 1 / (d_s + lbd), ridge 1e-6 on the normal
+ *                          equations, Cholesky pivot floor 1e-18, sigma^2 from an explicit residual pass, p = clamp(2 sf(|z|)).  A
+ *                          row is nine NaN when one of its 3 n values is not finite, the factorisation fails or r'Wr / sigma^2 is
+ *                          not finite and positive; a later coefficient whose variance is not finite and positive leaves the
+ *                          earlier ones written.  d_xcov (n, p_cov) f64 row-major, p_cov <= 13 (more is refused), n > p_cov + 3.
+ *                          Fails with the reference's messages on a non-positive d_s + lbd and non-finite d_y / d_xcov. */
+int jxg_fvlmm2_combo_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows1, const int32_t *d_rows2, int nrows,
+                         const float *d_lut1, const float *d_lut2, const float *d_tab, const uint32_t *d_pos, float *d_g1,
+                         float *d_g2, float *d_gc, int64_t ld, int32_t *d_counts, void *stream);
+int jxg_fvlmm2_joint(const float *d_g1, const float *d_g2, const float *d_gc, int nrows, int n, int64_t ld, const double *d_s,
+                     const double *d_xcov, int p_cov, const double *d_y, double lbd, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

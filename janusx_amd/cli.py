@@ -21,6 +21,10 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
                                  (site / sample QC tables and LD scores; WINDOW: 100, 100kb, 0.1mb, 100000b, 10cm; bare -ldsc: 100kb)
   python -m janusx_amd tree -bfile PREFIX -nj [exact] [-maf 0.02] [-geno 0.05] [-het 0.02] [-snps-only] [-o OUT | -o DIR/ -prefix NAME]
                                  [--write-phylip] [--no-fasta]   (neighbour-joining tree: {out}.nwk, {out}.fasta, {out}.phy)
+  python -m janusx_amd fvlmm2 -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-i PAIRS.txt | -among SNPS.txt [--op '*']) [-c COV.tsv] [-k GRM.npy]
+                                 [-maf 0.02] [-geno 0.05] [-het 1.0] [-snps-only] [--batch-size 4096] [--n-tests 0] [-pmax P]
+                                 [-o OUT | -o DIR/ -prefix NAME]   (joint SNP-pair interaction test at the null lambda:
+                                 {out}.{trait}.fvlmm2.tsv, {out}.fvlmm2.skip)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
@@ -44,6 +48,7 @@ import math
 import os
 import sys
 import time
+import types
 
 import numpy as np
 
@@ -557,6 +562,48 @@ def _run_lmm_trait_level(packed_t, n_fam, k, traits, names, samples_of, design_o
     return done
 
 
+def _load_cov_items(cov_items, fam, bim, packed_t, n_fam):
+    """The -c items of a run joined on the samples they share -> (cv (samples, columns) f64, {sample id: row}), or (None, {})
+    when no item gave columns.  An item is a covariate table or a SNP site `chr:pos` (`chr:start:end` with start = end) whose
+    additive genotype -- missing calls at the site's mean over all genotyped samples -- becomes a covariate (conditional analysis;
+    `_load_covariates_for_models` / `_load_site_covariates`, python/janusx/assoc/workflow.py:1742-1789, 1979-2145)."""
+    cv, cpos = None, {}
+    if cov_items:
+        parts = []
+        for item in cov_items:
+            site = _parse_cov_site_token(item)
+            if site is None:
+                if not os.path.isfile(item):
+                    print(f"Covariate file not found: {item}; skipped.")
+                    continue
+                cids_i, _, cv_i = _read_table(item)
+                parts.append((list(cids_i), np.asarray(cv_i, dtype=np.float64).reshape(len(cids_i), -1)))
+            else:
+                key = _canon_site_key(*site)
+                hit = next((j for j in range(len(bim.chrom)) if _canon_site_key(bim.chrom[j], bim.pos[j]) == key), None)
+                if hit is None:
+                    raise SystemExit(f"Some --cov SNP site(s) were not found in genotype: {site[0]}:{site[1]}")
+                row = packed_t[hit].cpu().numpy()
+                codes = ((row[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:n_fam]
+                gv = np.array([0.0, np.nan, 1.0, 2.0])[codes]
+                gv[np.isnan(gv)] = float(np.nanmean(gv)) if np.isfinite(gv).any() else 0.0
+                parts.append((list(fam), gv.reshape(-1, 1)))
+        if parts:
+            common = set(parts[0][0])
+            for ids_i, _m in parts[1:]:
+                common &= set(ids_i)
+            cids = [sid for sid in fam if sid in common]
+            if not cids:
+                raise SystemExit("No overlapping samples between genotype and covariates.")
+            cols = []
+            for ids_i, m_i in parts:
+                ix = {sid: i for i, sid in enumerate(ids_i)}
+                cols.append(m_i[[ix[sid] for sid in cids]])
+            cv = np.concatenate(cols, axis=1)
+            cpos = {s: i for i, s in enumerate(cids)}
+    return cv, cpos
+
+
 def cmd_gwas(args):
     import torch
     from . import janusx as jxrs
@@ -627,43 +674,8 @@ def cmd_gwas(args):
     # `_load_covariates_for_models` / `_load_site_covariates`, python/janusx/assoc/workflow.py:1742-1789, 1979-2145).  The
     # columns of all items are joined on the samples they share.
     cov_items = args.cov if isinstance(args.cov, list) else ([args.cov] if args.cov else [])
-    args.cov = bool(cov_items)
-    cv, cpos = None, {}
-    if cov_items:
-        parts = []
-        for item in cov_items:
-            site = _parse_cov_site_token(item)
-            if site is None:
-                if not os.path.isfile(item):
-                    print(f"Covariate file not found: {item}; skipped.")
-                    continue
-                cids_i, _, cv_i = _read_table(item)
-                parts.append((list(cids_i), np.asarray(cv_i, dtype=np.float64).reshape(len(cids_i), -1)))
-            else:
-                key = _canon_site_key(*site)
-                hit = next((j for j in range(len(bim.chrom)) if _canon_site_key(bim.chrom[j], bim.pos[j]) == key), None)
-                if hit is None:
-                    raise SystemExit(f"Some --cov SNP site(s) were not found in genotype: {site[0]}:{site[1]}")
-                row = packed_t[hit].cpu().numpy()
-                codes = ((row[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:n_fam]
-                gv = np.array([0.0, np.nan, 1.0, 2.0])[codes]
-                gv[np.isnan(gv)] = float(np.nanmean(gv)) if np.isfinite(gv).any() else 0.0
-                parts.append((list(fam), gv.reshape(-1, 1)))
-        if parts:
-            common = set(parts[0][0])
-            for ids_i, _m in parts[1:]:
-                common &= set(ids_i)
-            cids = [sid for sid in fam if sid in common]
-            if not cids:
-                raise SystemExit("No overlapping samples between genotype and covariates.")
-            cols = []
-            for ids_i, m_i in parts:
-                ix = {sid: i for i, sid in enumerate(ids_i)}
-                cols.append(m_i[[ix[sid] for sid in cids]])
-            cv = np.concatenate(cols, axis=1)
-            cpos = {s: i for i, s in enumerate(cids)}
-        else:
-            args.cov = False
+    cv, cpos = _load_cov_items(cov_items, fam, bim, packed_t, n_fam)
+    args.cov = cv is not None
     # -lm2 without -c, or without COVCOL, runs -lm instead (python/janusx/assoc/workflow.py:7969-8001); once, if -lm was given too
     run_lm, lm2_idx = bool(getattr(args, "lm", False)), None
     if lm2_flag is not None:
@@ -1704,6 +1716,121 @@ def cmd_tree(args):
     return 0
 
 
+def cmd_fvlmm2(args):
+    """`jx fvlmm2 -bfile PREFIX -p PHENO -i PAIRS.txt` (python/janusx/script/fvlmm2.py:887-1117): for every SNP pair of the
+    interaction file the joint test of  y = covariates + SNP1 + SNP2 + combo + Zu + e  at the null model's lambda
+    -> `{out}.{trait}.fvlmm2.tsv`, and `{out}.fvlmm2.skip` for the lines that did not resolve.  The pair rows are rotated with the
+    trait's eigenvectors before the test (the reference's script leaves them unrotated; README, known differences).  Extensions:
+    -among SNPS.txt [--op OP] tests all pairs among the named SNPs, -pmax P writes only the rows with p_combo_joint <= P.  The
+    reference's `.fvlmm2.log` and configuration banner are not written; non-BED input is refused."""
+    from . import fvlmm2 as f2
+    for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"fvlmm2: {what} input is not supported on this build; give a PLINK prefix with -bfile")
+    if not args.bfile:
+        raise SystemExit("fvlmm2 needs -bfile PREFIX")
+    if not args.interaction and not args.among:
+        raise SystemExit("fvlmm2 needs an interaction file (-i PAIRS.txt) and/or -among SNPS.txt")
+    if int(args.n_tests) < 0:
+        raise SystemExit("--n-tests must be >= 0")
+    if args.pmax is not None and not (0.0 <= float(args.pmax) <= 1.0):
+        raise SystemExit("-pmax must be within [0, 1]")
+    if args.op not in f2.OPS:
+        raise SystemExit(f"--op must be one of {' '.join(f2.OPS)}")
+    for path, what in ((args.interaction, "Interaction file"), (args.among, "-among file"), (args.pheno, "Phenotype file")):
+        if path and not os.path.isfile(path):
+            raise SystemExit(f"fvlmm2: {what} not found: {path}")
+    among_names = None
+    if args.among:
+        try:
+            among_names = f2.read_among_names(args.among)
+        except ValueError as e:
+            raise SystemExit(f"fvlmm2: {e}") from None
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    import torch
+    from . import janusx as jxrs
+    from . import pipeline as pl
+    from .bed import read_fam_ids
+    src = jxrs._bed_prefix(args.bfile)
+    t0 = time.perf_counter()
+    # the active rows: `prepare_packed_ctx_from_plink` (filter over all samples, no flips, maf = ALT frequency), fvlmm2.py:1037-1046
+    try:
+        pk, _miss, maf, _std, flip, site_keep, n_fam, _total = jxrs.prepare_bed_2bit_packed(
+            src, float(args.maf), float(args.geno), float(args.het), bool(args.snps_only))
+    except (RuntimeError, ValueError, OSError) as e:
+        raise SystemExit(f"fvlmm2: {e}") from None
+    chrom, pos_bp, snp, _a0, _a1 = jxrs.load_bim_columns(src, np.nonzero(site_keep)[0])
+    row_names, name_map = f2.build_name_map(chrom, pos_bp, snp)
+    specs, skipped = f2.parse_interaction_file(args.interaction, name_map) if args.interaction else ([], [])
+    if among_names is not None:
+        sp2, sk2 = f2.among_specs(among_names, name_map, row_names, args.op)
+        specs, skipped = specs + sp2, skipped + sk2
+    if not specs:
+        raise SystemExit(f"fvlmm2: {f2.NO_EXPRESSIONS}")
+    out = _resolve_out(args, src)
+    print(f"Resolved {len(specs)} interaction rows against {len(row_names)} active filtered variants; skipped={len(skipped)}.")
+    if skipped:
+        f2.write_skip(f"{out}.fvlmm2.skip", skipped)
+        print(f"Skipped interaction rows were written to {out}.fvlmm2.skip")
+    fam = read_fam_ids(src)
+    ids, names, ph = _read_table(args.pheno)
+    pos = {s: i for i, s in enumerate(ids)}
+    dev = torch.device("cuda", torch.cuda.current_device())
+    packed_t = torch.from_numpy(pk).to(dev)
+    cov_items = args.cov if isinstance(args.cov, list) else ([args.cov] if args.cov else [])
+    # a `chr:pos` item of -c is looked up among the active rows of this run
+    cv, cpos = _load_cov_items(cov_items, fam, types.SimpleNamespace(chrom=chrom, pos=pos_bp), packed_t, n_fam)
+    if 1 + (0 if cv is None else int(cv.shape[1])) > jxrs.FVLMM2_MAX_PCOV:      # before the GRM and the eigendecomposition
+        raise SystemExit(f"fvlmm2: at most {jxrs.FVLMM2_MAX_PCOV - 1} covariate columns beside the intercept on this build, got "
+                         f"{int(cv.shape[1])}")
+    # the GRM of `jx gwas -fvlmm` (-k FILE, else method 1 over the kept sites of this run)
+    if args.grm:
+        k = torch.from_numpy(_load_grm(args.grm, fam)).to(dev)
+    else:
+        k, eff, _ = pl.build_grm(packed_t, n_fam, 1, args.maf, args.geno)
+        print(f"GRM method 1: eff_m={eff} ({time.perf_counter() - t0:.2f}s)")
+    row1 = np.array([sp.row1 for sp in specs], dtype=np.int64)
+    row2 = np.array([sp.row2 for sp in specs], dtype=np.int64)
+    ops = [sp.op for sp in specs]
+    neg1 = np.array([sp.neg1 for sp in specs], dtype=bool)
+    neg2 = np.array([sp.neg2 for sp in specs], dtype=bool)
+    cov_dim = 0 if cv is None else int(cv.shape[1])
+    for ti in _select_traits(names, args.ncol):
+        name = names[ti]
+        t1 = time.perf_counter()
+        keep_idx = np.array([j for j, sid in enumerate(fam)
+                             if pos.get(sid) is not None and math.isfinite(ph[pos[sid], ti])
+                             and (cv is None or (sid in cpos and np.all(np.isfinite(cv[cpos[sid]]))))], dtype=np.int64)
+        n = len(keep_idx)
+        if n <= cov_dim + 4:
+            raise SystemExit(f"Trait {name} has too few usable samples after alignment/filtering: n={n}, cov={cov_dim}.")
+        y = np.array([ph[pos[fam[j]], ti] for j in keep_idx])
+        x = np.ones((n, 1))
+        if cv is not None:
+            x = np.concatenate([x, np.array([cv[cpos[fam[j]]] for j in keep_idx])], axis=1)
+        model = pl.trait_null_model(k, keep_idx, x, y)
+        lbd = float(model.null.lbd)
+        if not (math.isfinite(lbd) and lbd > 0.0):
+            raise SystemExit(f"Trait {name} produced invalid null lambda: {lbd}")
+        try:
+            res = jxrs.fvlmm2_pairs_packed(packed_t, n_fam, flip, maf, row1, row2, ops, neg1, neg2, model.S, model.xcov, model.y,
+                                           model.ut, math.log10(lbd), sample_indices=keep_idx, batch_size=int(args.batch_size))
+        except RuntimeError as e:
+            raise SystemExit(f"fvlmm2: {e}") from None
+        joint = np.stack([res[c] for c in ("beta1", "se1", "p1", "beta2", "se2", "p2", "beta_combo", "se_combo", "p_combo")], axis=1)
+        fdr = f2.bh_adjust(joint[:, 8], n_tests=int(args.n_tests) if int(args.n_tests) > 0 else None)
+        keep = None if args.pmax is None else joint[:, 8] <= float(args.pmax)
+        path = f"{out}.{f2.trait_label(name)}.fvlmm2.tsv"
+        wrote = f2.write_table(path, [chrom[r] for r in row1], [pos_bp[r] for r in row1], [sp.expr for sp in specs],
+                               res["combo_af"], joint, fdr, keep)
+        print(f"[{name}] fvlmm2: n={n} pairs={len(specs)} written={wrote} lambda0={lbd:.5g} -> {path} "
+              f"({time.perf_counter() - t1:.2f}s)")
+        del model
+    return 0
+
+
 def _add_admixture_parser(sub, name):
     a = sub.add_parser(name)
     a.add_argument("-bfile", "--bfile", default=None)
@@ -1925,6 +2052,36 @@ def main(argv=None):
         t.add_argument(f"-{flag}", *(("--fasta",) if flag == "fa" else (f"--{flag}",)), dest="fasta" if flag == "fa" else flag,
                        default=None, help=argparse.SUPPRESS)
     t.set_defaults(func=cmd_tree)
+    v = sub.add_parser("fvlmm2")
+    v.add_argument("-bfile", "--bfile", default=None)
+    v.add_argument("-p", "--pheno", required=True)
+    v.add_argument("-n", "--n", dest="ncol", action="append", default=None)
+    v.add_argument("-i", "--interaction", dest="interaction", default=None,
+                   help="interaction file, one expression per line: snp1*snp2, snp1&snp2, snp1|snp2, snp1^snp2; '!' negates a "
+                        "literal of the logic operators")
+    v.add_argument("-among", "--among", dest="among", default=None, metavar="SNPS.txt",
+                   help="test all unordered pairs among the SNPs named in this file, one name per line, at most 4096 (an "
+                        "extension); may be combined with -i, whose rows come first")
+    v.add_argument("--op", dest="op", default="*", help="operator of the -among pairs: *, &, | or ^ (default *)")
+    v.add_argument("-pmax", "--pmax", dest="pmax", type=float, default=None, metavar="P",
+                   help="write only the rows with p_combo_joint <= P (an extension); the FDR column is computed over every "
+                        "tested row first")
+    v.add_argument("-c", "--cov", dest="cov", action="append", default=None, help="covariate table (sample id + columns); may be repeated")
+    v.add_argument("-k", "--grm", dest="grm", default=None, help="dense GRM (.npy with a sibling .id); default: built from the genotypes")
+    v.add_argument("-maf", "--maf", type=float, default=0.02)
+    v.add_argument("-geno", "--geno", type=float, default=0.05)
+    v.add_argument("-het", "--het", type=float, default=1.0)
+    v.add_argument("-snps-only", "--snps-only", dest="snps_only", action="store_true", default=False,
+                   help="drop sites whose alleles are not single A/C/G/T")
+    v.add_argument("--batch-size", dest="batch_size", type=int, default=4096, help="pairs per device batch")
+    v.add_argument("--n-tests", dest="n_tests", type=int, default=0,
+                   help="total hypothesis count of the BH adjustment of p_combo_joint (default: the tested rows)")
+    v.add_argument("-o", "--out", default=None)
+    v.add_argument("-prefix", "--prefix", default=None, help="file name prefix inside the -o directory")
+    v.add_argument("-t", "--thread", "--threads", dest="thread", type=int, default=0, help="accepted for compatibility; unused")
+    for flag in ("vcf", "hmp", "file"):
+        v.add_argument(f"-{flag}", f"--{flag}", dest=flag, default=None, help=argparse.SUPPRESS)
+    v.set_defaults(func=cmd_fvlmm2)
     args = ap.parse_args(argv)
     return args.func(args)
 

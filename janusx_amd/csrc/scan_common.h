@@ -133,6 +133,8 @@ __device__ __attribute__((noinline)) double jx_pow10(double x) { return pow(10.0
 __device__ __attribute__((noinline)) double jx_log(double x) { return log(x); }
 __device__ __attribute__((noinline)) double jx_erfc(double x) { return erfc(x); }
 
+__device__ __forceinline__ double normal_sf_dev(double z) { return 0.5 * jx_erfc(z / 1.4142135623730951); }  // src/math/linalg.rs:2-4
+
 __device__ __forceinline__ double chi2_sf_df1_dev(double stat) {  // src/math/linalg.rs:7-17
     if (!isfinite(stat) || stat <= 0.0) return 1.0;
     double p = jx_erfc(sqrt(0.5 * stat));

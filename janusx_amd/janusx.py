@@ -2682,6 +2682,194 @@ def fvlmm_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_rot,
 
 
 # ------------------------------------------------------------------------------------------------
+# joint SNP-pair interaction test at the null lambda  (src/stats/fvlmm2.rs; csrc/k_fvlmm2.hip)
+# ------------------------------------------------------------------------------------------------
+
+FVLMM2_MAX_PCOV = 13          # p_cov + 3 <= 16, the largest dense system the scan kernels instantiate
+
+
+def _fvlmm2_null(s, xcov, y_rot, log10_lbd):
+    """The null-model arguments of the joint test with the reference's checks in its order (src/stats/fvlmm2.rs:57-71, 89-100),
+    shapes only: host arrays or torch CUDA tensors -> (s, xcov, y, n, p_cov, on_device)."""
+    on_dev = any(_is_device_tensor(a) for a in (s, xcov, y_rot))
+    if on_dev:
+        import torch
+        dev = next(a.device for a in (s, xcov, y_rot) if _is_device_tensor(a))
+
+        def f64(a):
+            t = a if _is_device_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            return t.to(device=dev, dtype=torch.float64).contiguous()
+        s, xcov, y = f64(s).reshape(-1), f64(xcov), f64(y_rot).reshape(-1)
+        ndim = xcov.dim()
+    else:
+        s, xcov, y = _c(s, np.float64).ravel(), _c(xcov, np.float64), _c(y_rot, np.float64).ravel()
+        ndim = xcov.ndim
+    n = int(y.shape[0])
+    if n == 0:
+        raise RuntimeError("y_rot must not be empty")
+    if ndim != 2 or int(xcov.shape[0]) != n:
+        raise RuntimeError("xcov.n_rows must equal len(y_rot)")
+    if int(s.shape[0]) != n:
+        raise RuntimeError("len(S) must equal len(y_rot)")
+    if not np.isfinite(log10_lbd):
+        raise RuntimeError("log10_lbd must be finite")
+    return s, xcov, y, n, int(xcov.shape[1]), on_dev
+
+
+def _fvlmm2_lambda(n, p_cov, log10_lbd):
+    with np.errstate(over="ignore", under="ignore"):
+        lbd = float(np.float64(10.0) ** np.float64(log10_lbd))
+    if not (np.isfinite(lbd) and lbd > 0.0):
+        raise RuntimeError("log10_lbd must map to a finite positive lambda")
+    if n <= p_cov + 3:
+        raise RuntimeError(f"n must be > p_cov + 3 for the joint test, got n={n}, p_cov={p_cov}")
+    if p_cov > FVLMM2_MAX_PCOV:
+        raise RuntimeError(f"fvlmm2 joint test supports at most {FVLMM2_MAX_PCOV} covariate columns (p_cov + 3 <= 16), got "
+                           f"p_cov={p_cov}")
+    return lbd
+
+
+def _fvlmm2_host_values(s, xcov, y, lbd):
+    """Value checks of host arrays in the reference's order (src/stats/fvlmm2.rs:119-149); device tensors are checked by
+    `jxg_fvlmm2_joint` with the same messages."""
+    vv = s + lbd
+    if not np.all(np.isfinite(vv) & (vv > 0.0)):
+        raise RuntimeError("S + lambda must stay finite and positive for all samples")
+    bad_y = ~np.isfinite(y)
+    bad_x = ~np.all(np.isfinite(xcov), axis=1) if xcov.shape[1] else np.zeros(len(y), dtype=bool)
+    if bad_y.any() or bad_x.any():
+        i = int(np.argmax(bad_y | bad_x))                   # the first sample with either: y is looked at before its covariates
+        raise RuntimeError("y_rot contains non-finite values" if bad_y[i] else "xcov contains non-finite values")
+
+
+def _fvlmm2_chunk(a, n, rows, msg):
+    """A (rows, n) f32 chunk, host array or torch CUDA tensor, checked against n and (where given) the row count of the first
+    chunk -> (chunk, rows)."""
+    if not _is_device_tensor(a):
+        a = _c(a, np.float32)
+    shape = tuple(int(v) for v in a.shape)
+    if len(shape) != 2 or shape[1] != n or (rows is not None and shape[0] != rows):
+        raise RuntimeError(msg)
+    return a, shape[0]
+
+
+def _fvlmm2_to_device(a, dtype, dev):
+    import torch
+    if not _is_device_tensor(a):
+        a = torch.from_numpy(a if a.flags.writeable else a.copy())
+    return a.to(device=dev, dtype=dtype).contiguous()
+
+
+def fvlmm2_assoc_chunk_f32(s, xcov, y_rot, log10_lbd, snp1_chunk, snp2_chunk, combo_chunk, threads=4):
+    """src/stats/fvlmm2.rs:37-290 -> f64 (rows, 9) = (beta, se, p) of snp1, snp2 and the combo term in
+    y ~ xcov + snp1 + snp2 + combo at lambda = 10^log10_lbd, the rows used AS GIVEN (the reference's script hands unrotated
+    rows to this function; `fvlmm2_pairs_packed` rotates them).  Host arrays or torch CUDA tensors; the result is a host array.
+    p_cov <= 13 on this build."""
+    s, xcov, y, n, p_cov, on_dev = _fvlmm2_null(s, xcov, y_rot, log10_lbd)
+    g1, rows = _fvlmm2_chunk(snp1_chunk, n, None, "snp1_chunk.n_cols must equal len(y_rot)")
+    g2, _ = _fvlmm2_chunk(snp2_chunk, n, rows, "snp2_chunk must have the same shape as snp1_chunk")
+    gc, _ = _fvlmm2_chunk(combo_chunk, n, rows, "combo_chunk must have the same shape as snp1_chunk")
+    lbd = _fvlmm2_lambda(n, p_cov, log10_lbd)
+    if not on_dev:
+        _fvlmm2_host_values(s, xcov, y, lbd)
+    import torch
+    from .pipeline import _ptr, _stream
+    dev = s.device if on_dev else torch.device("cuda", torch.cuda.current_device())
+    s, xcov, y = (_fvlmm2_to_device(a, torch.float64, dev) for a in (s, xcov, y))
+    g1, g2, gc = (_fvlmm2_to_device(a, torch.float32, dev) for a in (g1, g2, gc))
+    out = torch.empty((rows, 9), dtype=torch.float64, device=dev)
+    check(lib().jxg_fvlmm2_joint(_ptr(g1), _ptr(g2), _ptr(gc), rows, n, n, _ptr(s), _ptr(xcov), p_cov, _ptr(y), lbd, _ptr(out),
+                                 _stream()))
+    return out.cpu().numpy()
+
+
+def fvlmm2_pairs_packed(packed, n_samples, row_flip, row_maf, row1, row2, op, neg1, neg2, s, xcov_rot, y_rot, u_t, log10_lbd,
+                        sample_indices=None, batch_size=4096):
+    """Joint interaction test of SNP pairs of a packed payload (extension; the device form of `_run_trait_scan`,
+    python/janusx/script/fvlmm2.py:696-739, with the rows ROTATED as the model y = X b + g1 + g2 + combo + Zu + e needs).
+    row1, row2 (R): payload rows of the pairs; op: R operators of '*', '&', '|', '^' (or one for all); neg1, neg2 (R) bool: negated
+    literals; s, xcov_rot, y_rot, u_t: the rotated null model (host arrays or torch CUDA tensors, u_t (n, n) f32 row-major U^T);
+    row_flip, row_maf: one entry per payload row.  Per batch of `batch_size` pairs: g1, g2 and the combo row from the P32 image
+    (`jxg_fvlmm2_combo_p32`), three rotations (`jxg_rotate_dense_f32`), the joint test (`jxg_fvlmm2_joint`); the buffers are
+    allocated once.  -> dict: beta1, se1, p1, beta2, se2, p2, beta_combo, se_combo, p_combo (R) f64 and af1, af2, combo_af
+    (R) f64 = share of the samples whose literal 1, literal 2, combo value is > 0."""
+    import torch
+    from . import fvlmm2 as f2
+    from .pipeline import _ptr, _stream
+    from .tree import _check_hbm
+    s, xcov, y, n, p_cov, on_dev = _fvlmm2_null(s, xcov_rot, y_rot, log10_lbd)
+    lbd = _fvlmm2_lambda(n, p_cov, log10_lbd)
+    if not on_dev:
+        _fvlmm2_host_values(s, xcov, y, lbd)
+    r1, r2 = _c(row1, np.int64).ravel(), _c(row2, np.int64).ravel()
+    npairs = int(r1.shape[0])
+    ops = [str(op)] * npairs if isinstance(op, str) else [str(o) for o in op]
+    ng1, ng2 = np.asarray(neg1, dtype=bool).ravel(), np.asarray(neg2, dtype=bool).ravel()
+    if not (r2.shape[0] == len(ops) == ng1.shape[0] == ng2.shape[0] == npairs):
+        raise RuntimeError("row1, row2, op, neg1 and neg2 must have one entry per pair")
+    pk, _pk_ptr, m = _payload(packed, n_samples)
+    flip, maf = np.asarray(row_flip).astype(bool).ravel(), _c(row_maf, np.float32).ravel()
+    if flip.shape[0] != m or maf.shape[0] != m:
+        raise RuntimeError(f"row_flip/row_maf length mismatch: got row_flip={flip.shape[0]}, row_maf={maf.shape[0]}, expected "
+                           f"packed_rows={m}")
+    if npairs and (min(r1.min(), r2.min()) < 0 or max(r1.max(), r2.max()) >= m):
+        raise RuntimeError(f"row1/row2 out of range for {m} rows")
+    idx, n_sel = _opt_idx(sample_indices)
+    if (n_sel if idx is not None else int(n_samples)) != n:
+        raise RuntimeError(f"selected sample count {n_sel if idx is not None else int(n_samples)} != len(y_rot) {n}")
+    batch = max(1, int(batch_size))
+    if int(batch) * n >= 2 ** 31:
+        raise RuntimeError(f"batch_size {batch} x n {n} exceeds 2^31 elements per block; use a smaller batch")
+    keys = ("beta1", "se1", "p1", "beta2", "se2", "p2", "beta_combo", "se_combo", "p_combo")
+    if npairs == 0:
+        return {k: np.zeros(0, dtype=np.float64) for k in keys + ("af1", "af2", "combo_af")}
+    lut_all = _raw_additive_lut(maf, flip, True)
+    tab, pos = f2.pair_tables(lut_all[r1], lut_all[r2], ops, ng1, ng2)      # refuses '*' with a negation before any device work
+    nb = min(batch, npairs)
+    _check_hbm(6.0 * nb * n * 4.0 + (0.0 if _is_device_tensor(u_t) else 4.0 * n * n) + 200.0 * nb + 16.0 * n * (p_cov + 2),
+               f"fvlmm2 pair scan of {n} samples in batches of {nb}")
+    panel = _panel(pk, n_samples, idx)
+    dev = panel.device
+    s, xcov, y = (_fvlmm2_to_device(a, torch.float64, dev) for a in (s, xcov, y))
+    if _is_device_tensor(u_t):
+        if tuple(u_t.shape) != (n, n):
+            raise RuntimeError("u_t must be (n, n) and row-major U^T")
+        ut = u_t.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        ut = torch.from_numpy(_assoc_u_t(u_t, n)).to(dev)
+    g = torch.empty((3, nb, n), dtype=torch.float32, device=dev)
+    grot = torch.empty((3, nb, n), dtype=torch.float32, device=dev)
+    d_rows = torch.empty((2, nb), dtype=torch.int32, device=dev)
+    d_lut = torch.empty((2, nb, 4), dtype=torch.float32, device=dev)
+    d_tab = torch.empty((nb, 16), dtype=torch.float32, device=dev)
+    d_pos = torch.empty(nb, dtype=torch.int32, device=dev)
+    d_cnt = torch.empty((nb, 3), dtype=torch.int32, device=dev)
+    d_out = torch.empty((nb, 9), dtype=torch.float64, device=dev)
+    joint = np.empty((npairs, 9), dtype=np.float64)
+    cnt = np.empty((npairs, 3), dtype=np.int32)
+    for b0 in range(0, npairs, nb):
+        nr = min(nb, npairs - b0)
+        sl = slice(b0, b0 + nr)
+        d_rows[:, :nr].copy_(torch.from_numpy(np.stack([r1[sl], r2[sl]]).astype(np.int32)))
+        d_lut[:, :nr].copy_(torch.from_numpy(np.stack([lut_all[r1[sl]], lut_all[r2[sl]]])))
+        d_tab[:nr].copy_(torch.from_numpy(tab[sl]))
+        d_pos[:nr].copy_(torch.from_numpy(pos[sl].view(np.int32)))
+        check(lib().jxg_fvlmm2_combo_p32(_ptr(panel.p32), panel.m, n, _ptr(d_rows[0]), _ptr(d_rows[1]), nr, _ptr(d_lut[0]),
+                                         _ptr(d_lut[1]), _ptr(d_tab), _ptr(d_pos), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), n,
+                                         _ptr(d_cnt), _stream()))
+        for k in range(3):
+            check(lib().jxg_rotate_dense_f32(_ptr(g[k]), nr, n, _ptr(ut), _ptr(grot[k]), _stream()))
+        check(lib().jxg_fvlmm2_joint(_ptr(grot[0]), _ptr(grot[1]), _ptr(grot[2]), nr, n, n, _ptr(s), _ptr(xcov), p_cov, _ptr(y),
+                                     lbd, _ptr(d_out), _stream()))
+        joint[sl] = d_out[:nr].cpu().numpy()
+        cnt[sl] = d_cnt[:nr].cpu().numpy()
+    res = {k: np.ascontiguousarray(joint[:, j]) for j, k in enumerate(keys)}
+    for j, k in enumerate(("af1", "af2", "combo_af")):
+        res[k] = cnt[:, j].astype(np.float64) / float(n)
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
 # BED -> QC -> scan -> TSV entry points (src/stats/lmm.rs:2488-2751, src/stats/fvlmm.rs:2482-2526,
 # orchestration of src/stats/lmm.rs:975-1477 `run_unified_bed_scan_to_tsv_common`)
 # ------------------------------------------------------------------------------------------------

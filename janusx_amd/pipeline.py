@@ -394,8 +394,10 @@ class SpectralModel:
     @classmethod
     def rotated(cls, s, u_t, xcov, y, device):
         """A model from what a caller has rotated already (the mirror's packed entry points): s (n) f64, u_t (n, n) f32 row-major
-        U^T kept as given, X~ (n, p) and y~ (n) f64.  No rotation and no null fit (null = None)."""
+        U^T kept as given, X~ (n, p) and y~ (n) f64, host arrays or torch tensors.  No rotation and no null fit (null = None)."""
         def dev(a, dtype):
+            if torch.is_tensor(a):           # parts that are on a device already
+                return a.to(device=device, dtype=torch.float64 if dtype == np.float64 else torch.float32).contiguous()
             a = np.ascontiguousarray(a, dtype=dtype)
             return torch.from_numpy(a if a.flags.writeable else a.copy()).to(device)
         self = cls.__new__(cls)
@@ -1455,6 +1457,13 @@ def build_grm(packed: torch.Tensor, n_samples: int, method=1, maf=0.02, geno=0.0
     return k32, int(round(eff)), panel
 
 
+def trait_null_model(k: torch.Tensor, keep_idx, x: np.ndarray, y: np.ndarray) -> SpectralModel:
+    """The spectral null model of one trait: eigh of K[keep, keep] + 1e-6 I, rotation of [X | y], REML null fit (`model.null`).
+    What `run_trait` scans with and `jx fvlmm2` tests pairs with."""
+    s, ut64 = eigh_from_grm(k, 1e-6, keep_idx, f32_consumer=True)     # only the f32 U^T of SpectralModel is kept
+    return SpectralModel(s, ut64, x, y)
+
+
 def run_trait(packed: torch.Tensor, n_samples: int, k: torch.Tensor, keep_idx, y: np.ndarray, x: np.ndarray,
               mode="lmm", maf=0.02, geno=0.05, het=1.0, max_iter=30, tol=1e-2, warm_start=False, on_rows=None,
               force_model=True, payload_sharded: bool = False, warm_chain=None):
@@ -1477,9 +1486,7 @@ def run_trait(packed: torch.Tensor, n_samples: int, k: torch.Tensor, keep_idx, y
     at chain boundaries (same table as one rank); with a payload shard per rank the chunks count from the shard's first row."""
     rank, world = dist_info()
     keep_idx = None if keep_idx is None else np.asarray(keep_idx, dtype=np.int64)
-    s, ut64 = eigh_from_grm(k, 1e-6, keep_idx, f32_consumer=True)     # only the f32 U^T of SpectralModel is kept
-    model = SpectralModel(s, ut64, x, y)
-    del ut64
+    model = trait_null_model(k, keep_idx, x, y)
     panel = Panel(packed, n_samples, keep_idx)
     panel.sharded = bool(payload_sharded)
     counts = panel.counts()
