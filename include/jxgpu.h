@@ -959,6 +959,27 @@ int jxg_fvlmm2_combo_p32(const uint8_t *d_p32, int64_t m_total, int n, const int
 int jxg_fvlmm2_joint(const float *d_g1, const float *d_g2, const float *d_gc, int nrows, int n, int64_t ld, const double *d_s,
                      const double *d_xcov, int p_cov, const double *d_y, double lbd, double *d_out, void *stream);
 
+/* ---- FarmCPU raw route (`jx gwas -farmcpu`; csrc/k_farmcpu.hip; src/stats/farmcpu.rs:2629-2941, 3310-3760): the per-marker
+ * statistics over the sums of jxg_lmt_sums_p32 against [Q | r_y], Q the orthonormal basis of the design X (n x q0, rank columns).
+ *   d_qg, d_qg_lo (nrows, ldq >= rank): the sums of Q's digits and of what they leave (d_qg_lo optional); d_gy[r ldg]: g'r_y;
+ *   d_ss (nrows): g'g; bg_rss = |r_y|^2; df = n - q0 - 1 (q0, not the rank: a rank-deficient design keeps the reference's df).
+ *   jxg_farmcpu_fem_stats  : b22 = ss - |Q'g|^2; a row with df <= 0, b22 <= 1e-8 or not finite, or ve < 0 / not finite is void:
+ *                            d_out (nrows, 3) f64 = (NaN, NaN, 1).  Otherwise beta = gy / b22, ve = (bg_rss - gy beta) / df,
+ *                            se = sqrt(ve / b22), p = two-sided Student t through `sanitize_assoc_pvalue`.  k_qtn > 0: d_w
+ *                            (k_qtn, ldw >= rank) maps Q'g to b21 of the QTN slots, d_bg_beta / d_diag_ixx (k_qtn) are the
+ *                            background coefficients and diag(pinv(X'X)) of the slots; d_max_t2_bits[j] (uint64, zeroed by the
+ *                            caller, kept across calls) takes the maximum over the non-void rows of the bit pattern of
+ *                            t_j^2 = beta_j^2 / se_j^2, beta_j = bg_beta[j] - b21_j beta, se_j^2 = (ixx_jj + b21_j^2 / b22) ve
+ *                            (integer atomicMax: deterministic).  Refuses k_qtn > jxg_farmcpu_max_qtn() = 512 and rank > 512.
+ *   jxg_farmcpu_final_stats: the final scan's rule: rss = max(bg_rss - gy^2 / b22, 0), ve = rss / df; a void row, or one without a
+ *                            finite beta and a positive finite se, is three NaN. */
+int jxg_farmcpu_max_qtn(void);
+int jxg_farmcpu_fem_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq, int rank, const double *d_gy, int64_t ldg,
+                          const double *d_ss, int nrows, double bg_rss, int df, const double *d_w, int64_t ldw, int k_qtn, const double *d_bg_beta,
+                          const double *d_diag_ixx, double *d_out, uint64_t *d_max_t2_bits, void *stream);
+int jxg_farmcpu_final_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq, int rank, const double *d_gy, int64_t ldg,
+                            const double *d_ss, int nrows, double bg_rss, int df, double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,9 @@ SIGNATURES = {
     "jxg_nj_run": [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
     "jxg_fvlmm2_combo_p32": [c_p, c_l, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p],
     "jxg_fvlmm2_joint": [c_p, c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_i, c_p, c_d, c_p, c_p],
+    "jxg_farmcpu_max_qtn": [],
+    "jxg_farmcpu_fem_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_d, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
+    "jxg_farmcpu_final_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_d, c_i, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

@@ -11,6 +11,10 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
                             [-warm-chain-pieces P] [-force-model] [-trait-pmax P]
                             (traits that share a sample mask share one eigendecomposition and one rotation of every SNP block,
                             one table {out}.lmm.tsv)
+  python -m janusx_amd gwas -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -farmcpu [-q N] [-c COV.tsv] [--farmcpu-iter 30]
+                            [--farmcpu-threshold P] [--farmcpu-qtn-bound auto|N] [--farmcpu-nbin 5]
+                            [--farmcpu-bin-size 500000,5000000,50000000]
+                            (FarmCPU, the classic route: {out}.{trait}.farmcpu.tsv and {out}.{trait}.farmcpu.qtn)
   python -m janusx_amd grm  -bfile PREFIX [-m 1|2] [-maf 0.02] [-geno 0.05] [-o OUT]
   python -m janusx_amd pca  (-bfile PREFIX | -k GRM) [-dim 3] [-maf 0.02] [-geno 0.05] [-rsvd [power] [tol]] [-snps-only] [-o OUT]
   python -m janusx_amd adamixture -bfile PREFIX -k 2..4 [-o OUTDIR] [-prefix NAME] [-maf 0.02] [-geno 0.05] [-seed 42]
@@ -455,6 +459,63 @@ def _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, a
               f"({time.perf_counter() - t1:.2f}s)")
 
 
+def _parse_farmcpu_args(args):
+    """The FarmCPU options of `jx gwas` (python/janusx/assoc/workflow.py:6727-6790) -> dict for `farmcpu.run_raw`."""
+    if int(args.farmcpu_iter) < 1:
+        raise SystemExit("--farmcpu-iter must be >= 1")
+    thr = args.farmcpu_threshold
+    if thr is not None and not (math.isfinite(thr) and thr > 0.0):
+        raise SystemExit("--farmcpu-threshold must be finite and > 0")
+    qb = str(args.farmcpu_qtn_bound).strip().lower()
+    if qb in ("auto", ""):
+        bound = None
+    else:
+        try:
+            bound = int(qb)
+        except ValueError:
+            raise SystemExit(f"--farmcpu-qtn-bound {args.farmcpu_qtn_bound}: expected auto or an integer >= 1")
+        if bound < 1:
+            raise SystemExit("--farmcpu-qtn-bound must be >= 1")
+    if int(args.farmcpu_nbin) < 1:
+        raise SystemExit("--farmcpu-nbin must be >= 1")
+    try:
+        szbin = [float(t) for t in str(args.farmcpu_bin_size).split(",") if t.strip()]
+    except ValueError:
+        raise SystemExit(f"--farmcpu-bin-size {args.farmcpu_bin_size}: expected comma-separated numbers")
+    if not szbin or any(not (math.isfinite(v) and v > 0.0) for v in szbin):
+        raise SystemExit("--farmcpu-bin-size: every bin size must be finite and > 0")
+    return {"threshold": thr, "max_iter": int(args.farmcpu_iter), "qtn_bound": bound, "nbin": int(args.farmcpu_nbin),
+            "szbin": szbin}
+
+
+def _run_farmcpu(packed_t, n_fam, keep_idx, y, x, farm, args, bim, out, name):
+    """`-farmcpu` of one trait on a panel of its samples: the QC of the other models, then `farmcpu.run_raw` with the design
+    [1 | Q | C] as the base; `af` = ALT frequency, `miss` = the count of missing samples."""
+    from . import farmcpu as fc
+    from . import pipeline as pl
+    from . import stats as st
+    t1 = time.perf_counter()
+    n = len(keep_idx)
+    panel = pl.Panel(packed_t, n_fam, keep_idx)
+    keep, af, _miss = st.gwas_scan_row_stats(panel.counts(), n, args.maf, args.geno, args.het)
+    rows = np.nonzero(keep)[0]
+    if len(rows) == 0:
+        print(f"[{name}] -farmcpu: no SNP passes the filters, skipped")
+        return
+    chrom, pos, snp, a0, a1 = bim.columns(rows)
+    thr = farm["threshold"] if farm["threshold"] is not None else 1.0 / len(rows)
+    res = fc.run_raw(panel, rows, af[rows], np.zeros(len(rows), dtype=bool), y, x, chrom, pos, thr, farm["max_iter"],
+                     farm["qtn_bound"], farm["nbin"], farm["szbin"])
+    path = f"{out}.{name}.farmcpu.tsv"
+    fc.write_main_tsv(path, chrom, pos, snp, a0, a1, af[rows], res.miss, res.stats)
+    note = ""
+    if res.qtn:
+        fc.write_qtn_tsv(f"{out}.{name}.farmcpu.qtn", res.qtn, chrom, pos, snp, a0, a1, af[rows], res.miss, res.stats, rows)
+        note = f", {out}.{name}.farmcpu.qtn"
+    print(f"[{name}] -farmcpu: n={n} snps={len(rows)} iterations={len(res.trace)} qtn={len(res.qtn)} -> {path}{note} "
+          f"({time.perf_counter() - t1:.2f}s)")
+
+
 def group_traits_by_samples(traits, samples_of):
     """Traits (column indices, in selection order) grouped by their sample set: -> [(keep_idx, [trait, ...])], the groups in the
     order of their first trait, the traits of a group in selection order.  `samples_of(trait)` -> int64 FAM positions."""
@@ -624,8 +685,13 @@ def cmd_gwas(args):
     if args.splmm is None and sp_stems:
         args.splmm = float(args.splmm_exact)
     lm2_flag = getattr(args, "lm2", None)
-    if not (getattr(args, "lm", False) or lm2_flag is not None or args.lmm or args.fvlmm or args.lmm2 or args.splmm is not None):
+    run_farmcpu = bool(getattr(args, "farmcpu", False))
+    if getattr(args, "frgwas", False) or getattr(args, "algwas", False):
+        raise SystemExit("-frgwas / -algwas (the unified FarmCPU routes) are not built; -farmcpu runs the classic route")
+    if not (getattr(args, "lm", False) or lm2_flag is not None or args.lmm or args.fvlmm or args.lmm2 or args.splmm is not None
+            or run_farmcpu):
         raise SystemExit("select at least one model: -lm, -lm2, -lmm, -lmm2, -fvlmm, -splmm and/or -splmm-exact")
+    farm = _parse_farmcpu_args(args) if run_farmcpu else None
     try:
         lm2_sel = _parse_lm2_covariate_selector(lm2_flag)
     except ValueError as e:
@@ -635,6 +701,8 @@ def cmd_gwas(args):
     trait_lmm = bool(getattr(args, "trait_level_lmm", False))
     if trait_pmax is not None and not (trait_level or trait_lmm):
         raise SystemExit("-trait-pmax belongs to -trait-level")
+    if run_farmcpu and (trait_level or trait_lmm):
+        raise SystemExit("-farmcpu goes trait by trait: it does not combine with -trait-level / -trait-level-lmm")
     if trait_level:
         # the reference's conditions (python/janusx/assoc/workflow_model_packed.py:5046-5064), before anything is loaded
         if not getattr(args, "lm", False):
@@ -695,6 +763,8 @@ def cmd_gwas(args):
                 raise SystemExit(f"-lm2/--lm2: at most {LM2_MAX_INTERACTIONS} interaction columns in this build, got {len(lm2_idx)}")
     if (run_lm or lm2_idx is not None) and world > 1:
         print("-lm / -lm2: computed on rank 0 alone")
+    if run_farmcpu and world > 1:
+        print("-farmcpu: computed on rank 0 alone")
     traits = _select_traits(names, args.ncol)
     out = _resolve_out(args, args.bfile)
     dev = packed_t.device
@@ -807,6 +877,8 @@ def cmd_gwas(args):
         if (run_lm or lm2_idx is not None) and rank == 0:
             cov_rows = np.array([cv[cpos[fam[j]]] for j in keep_idx]) if lm2_idx is not None else None
             _run_lm_models(packed_t, n_fam, keep_idx, y, x, cov_rows, lm2_idx, run_lm, args, bim, out, name)
+        if run_farmcpu and rank == 0:
+            _run_farmcpu(packed_t, n_fam, keep_idx, y, x, farm, args, bim, out, name)
         for mode in ((["lmm"] if args.lmm and ti not in lmm_done else []) + (["lmm2"] if args.lmm2 else []) +
                      (["fvlmm"] if args.fvlmm else [])):
             t1 = time.perf_counter()
@@ -1882,6 +1954,19 @@ def main(argv=None):
     g.add_argument("-lm2", "--lm2", nargs="?", const="__SELF__", default=None, metavar="COVCOL",
                    help="linear model with SNP-by-covariate interaction terms over the selected columns of the merged -c table "
                         "-> {out}.{trait}.lm2.tsv; 0-based selectors like 0, 0:3, :2, 0,3; without columns it runs -lm")
+    g.add_argument("-farmcpu", "--farmcpu", dest="farmcpu", action="store_true", default=False,
+                   help="FarmCPU, the classic (raw) route -> {out}.{trait}.farmcpu.tsv and, when pseudo-QTNs exist, "
+                        "{out}.{trait}.farmcpu.qtn")
+    g.add_argument("-frgwas", "--frgwas", dest="frgwas", action="store_true", default=False, help=argparse.SUPPRESS)
+    g.add_argument("-algwas", "--algwas", dest="algwas", action="store_true", default=False, help=argparse.SUPPRESS)
+    g.add_argument("--farmcpu-iter", dest="farmcpu_iter", type=int, default=30, help="FarmCPU iteration cap (default 30)")
+    g.add_argument("--farmcpu-threshold", dest="farmcpu_threshold", type=float, default=None,
+                   help="FarmCPU p threshold (default 1 / tested SNP count)")
+    g.add_argument("--farmcpu-qtn-bound", dest="farmcpu_qtn_bound", type=str, default="auto",
+                   help="largest lead count of the FarmCPU lead search (default auto = floor(sqrt(n / log10 n)))")
+    g.add_argument("--farmcpu-nbin", dest="farmcpu_nbin", type=int, default=5, help="lead-count grid size (default 5)")
+    g.add_argument("--farmcpu-bin-size", dest="farmcpu_bin_size", type=str, default="500000,5000000,50000000",
+                   help="comma-separated bin sizes in bp (default 500000,5000000,50000000)")
     g.add_argument("-lmm", "--lmm", action="store_true", default=False)
     g.add_argument("-lmm2", "--lmm2", action="store_true", default=False)
     g.add_argument("-fvlmm", "--fvlmm", action="store_true", default=False)

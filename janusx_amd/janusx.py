@@ -6647,3 +6647,98 @@ def write_king_tables(out, ids, n_sites, pairs, kept, removed):
 from .tree import (geno_chunk_to_alignment_u8, geno_chunk_to_alignment_u8_siteinfo, geno_chunk_to_alignment_u8_sites,  # noqa: E402,F401
                    nj_merge_log, nj_newick_from_alignment_u8, nj_newick_from_distance_matrix, nj_newick_from_packed,
                    tree_from_bed, tree_jc69_distance, tree_pair_counts_packed)
+
+
+# ------------------------------------------------------------------------------------------------
+# FarmCPU, raw route (src/stats/farmcpu.rs:4153-5510): `jx gwas -farmcpu`, host half in farmcpu.py
+# ------------------------------------------------------------------------------------------------
+
+def _farmcpu_inputs(y, x_cov, packed, n_samples, row_flip, row_maf, sample_indices, row_indices, threshold):
+    if int(n_samples) <= 0:
+        raise RuntimeError("n_samples must be > 0")
+    y = _c(y, np.float64).ravel()
+    n = int(y.shape[0])
+    if n == 0:
+        raise RuntimeError("empty phenotype vector")
+    x_cov = np.zeros((n, 0)) if x_cov is None else _c(x_cov, np.float64)
+    if x_cov.ndim != 2:
+        raise RuntimeError("x_cov must be 2D (n, p_cov)")
+    if x_cov.shape[0] != n:
+        raise RuntimeError(f"x_cov rows mismatch: got {x_cov.shape[0]}, expected n={n}")
+    pk, _ptr_unused, m_packed = _payload(packed, n_samples)
+    idx, n_sel = _opt_idx(sample_indices)
+    if (n_sel if idx is not None else int(n_samples)) != n:
+        raise RuntimeError(f"sample_indices length mismatch: got {n_sel if idx is not None else int(n_samples)}, "
+                           f"expected len(y)={n}")
+    if row_indices is None:
+        rows = np.arange(m_packed, dtype=np.int64)
+    else:
+        rows = _c(row_indices, np.int64).ravel()
+        if rows.size and (rows.min() < 0 or rows.max() >= m_packed):
+            raise RuntimeError("row_indices out of range")
+    m = int(rows.shape[0])
+    if m == 0:
+        raise RuntimeError("empty packed marker matrix")
+    flip = np.asarray(row_flip).astype(bool).ravel()
+    maf = _c(row_maf, np.float32).ravel()
+    if flip.shape[0] != m or maf.shape[0] != m:
+        raise RuntimeError(f"row metadata length mismatch: row_flip={flip.shape[0]}, row_maf={maf.shape[0]}, m={m}")
+    thr = 1.0 / m if threshold is None else float(threshold)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise RuntimeError("threshold must be finite and > 0")
+    x_base = np.ascontiguousarray(np.hstack([np.ones((n, 1)), x_cov]))
+    return y, x_base, pk, idx, rows, flip, maf, thr
+
+
+def farmcpu_packed(y, x_cov, packed, n_samples, row_flip, row_maf, chrom, pos, sample_indices=None, row_indices=None,
+                   threshold=None, max_iter=30, qtn_bound=None, nbin=5, szbin=(5e5, 5e6, 5e7), stage1_progress_callback=None):
+    """In-memory form of the raw FarmCPU route (an extension: the reference only writes files): `chrom` / `pos` per marker
+    (after `row_indices`), threshold None = 1 / markers.  -> `farmcpu.FarmcpuResult`: stats (m, 3) [beta, se, p] of the final
+    scan, the final QTN list (marker positions), the per-iteration trace (QTN set, winning (sz, nn), scores) and the missing
+    counts."""
+    from . import farmcpu as fc
+    y, x_base, pk, idx, rows, flip, maf, thr = _farmcpu_inputs(y, x_cov, packed, n_samples, row_flip, row_maf, sample_indices,
+                                                               row_indices, threshold)
+    if len(chrom) != len(rows) or len(pos) != len(rows):
+        raise RuntimeError(f"chrom / pos length mismatch: chrom={len(chrom)}, pos={len(pos)}, m={len(rows)}")
+    return fc.run_raw(_panel(pk, n_samples, idx), rows, maf, flip, y, x_base, chrom, pos, thr, max_iter, qtn_bound, nbin, szbin,
+                      stage1_progress_callback)
+
+
+def farmcpu_packed_to_tsv(y, x_cov, packed, n_samples, row_flip, row_maf, row_missing, out_tsv, sample_indices=None,
+                          row_indices=None, source_row_indices=None, threshold=1e-6, max_iter=30, qtn_bound=None, nbin=5,
+                          szbin=(5e5, 5e6, 5e7), threads=0, stage1_progress_callback=None, progress_callback=None,
+                          pseudo_tsv=None, bed_prefix=None, raw=False, skip_main_scan=False):
+    """src/stats/farmcpu.rs:4127-5510 with the reference's signature; only `raw=True` is built (`-farmcpu`), the unified route
+    and `skip_main_scan` are refused.  The marker metadata comes from `<bed_prefix>.bim` (rows `source_row_indices`, else
+    `row_indices`); `pseudo_tsv` takes the QTN table when QTNs exist.  `threads` is accepted for signature parity.
+    -> (rows written, QTN count, QTN rows written, stage 1 seconds, stage 2 seconds)."""
+    from . import farmcpu as fc
+    if not raw:
+        raise RuntimeError("farmcpu_packed_to_tsv: the unified route (raw=False, -frgwas) is not built; pass raw=True (-farmcpu)")
+    if skip_main_scan:
+        raise RuntimeError("farmcpu_packed_to_tsv: skip_main_scan=True is not built")
+    y, x_base, pk, idx, rows, flip, maf, thr = _farmcpu_inputs(y, x_cov, packed, n_samples, row_flip, row_maf, sample_indices,
+                                                               row_indices, threshold)
+    m = len(rows)
+    if _c(row_missing, np.float32).ravel().shape[0] != m:
+        raise RuntimeError(f"row metadata length mismatch: row_missing={_c(row_missing, np.float32).ravel().shape[0]}, m={m}")
+    if source_row_indices is not None:
+        meta_rows = _c(source_row_indices, np.int64).ravel()
+        if meta_rows.shape[0] != m:
+            raise RuntimeError(f"source_row_indices length mismatch: got {meta_rows.shape[0]}, expected {m}")
+        if meta_rows.size and meta_rows.min() < 0:
+            raise RuntimeError("source_row_indices must be non-negative")
+    else:
+        meta_rows = rows
+    chrom, pos, snp, a0, a1 = _resolve_assoc_tsv_metadata(bed_prefix, [], [], [], [], [], meta_rows, m,
+                                                          "FarmCPU streaming scan requires non-empty bed_prefix")
+    res = fc.run_raw(_panel(pk, n_samples, idx), rows, maf, flip, y, x_base, chrom, pos, thr, max_iter, qtn_bound, nbin, szbin,
+                     stage1_progress_callback)
+    t0 = time.perf_counter()
+    written = fc.write_main_tsv(out_tsv, chrom, pos, snp, a0, a1, maf, res.miss, res.stats)
+    qtn_rows = 0
+    if pseudo_tsv and res.qtn:
+        qtn_rows = fc.write_qtn_tsv(pseudo_tsv, res.qtn, chrom, pos, snp, a0, a1, maf, res.miss, res.stats, rows)
+    _done(progress_callback, m)
+    return written, len(res.qtn), qtn_rows, res.stage1_secs, res.stage2_secs + (time.perf_counter() - t0)

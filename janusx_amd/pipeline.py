@@ -1348,6 +1348,90 @@ def scan_rows_lm_traits(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.nd
     return LmTraitHits(np.ascontiguousarray(ht[order]), np.ascontiguousarray(hr[order]), np.ascontiguousarray(hv[order]))
 
 
+FarmcpuFem = namedtuple("FarmcpuFem", "p qtn_min_p stats")
+
+
+def farmcpu_missing_value(af: np.ndarray) -> np.ndarray:
+    """Major-allele imputation of the FarmCPU routes (`farmcpu_missing_impute_value`, src/stats/farmcpu.rs:206-217): a missing call
+    decodes to 2 where 2 af > 1 and to 0 otherwise (f32, the `mean` operand of `jxg_lmt_sums_p32`); a flip leaves it alone."""
+    a = np.asarray(af, dtype=np.float32).astype(np.float64)
+    return np.where(2.0 * a > 1.0, np.float32(2.0), np.float32(0.0)).astype(np.float32)
+
+
+def _farmcpu_scan(panel: Panel, rows, af, flip, x, q_base, y, final, block_rows):
+    from . import farmcpu as fc
+    dev, n = panel.device, panel.n
+    des = fc.design_operands(x, q_base, y)
+    q, rank, kq = des.q, int(des.q.shape[1]), int(des.w.shape[0])
+    if kq > lib().jxg_farmcpu_max_qtn():
+        raise RuntimeError(f"FarmCPU scan: {kq} pseudo-QTN columns are above the cap of {lib().jxg_farmcpu_max_qtn()} "
+                           "(lower the QTN bound)")
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    mk = len(rows)
+    if mk and (rows.min() < 0 or rows.max() >= panel.m):
+        raise RuntimeError("row index out of range")
+    out = torch.empty((mk, 3), dtype=torch.float64, device=dev)
+    maxbits = torch.zeros(max(kq, 1), dtype=torch.int64, device=dev)
+    if mk:
+        miss_g = farmcpu_missing_value(af)
+        fl = np.zeros(mk, dtype=bool) if flip is None else np.asarray(flip, dtype=bool)
+        if len(miss_g) != mk or len(fl) != mk:
+            raise RuntimeError("af / flip length != number of rows")
+        ss_t = torch.from_numpy(lm_traits_row_d(panel.counts()[rows], n, miss_g, fl)).to(dev)
+        rows_t = torch.from_numpy(rows).to(dev)
+        mean_t = torch.from_numpy(miss_g).to(dev)
+        flip_t = torch.from_numpy(fl.astype(np.uint8)).to(dev)
+        # one operand [Q | r_y]: its digits; a second one for what the digits of Q leave (b22 meets an absolute threshold)
+        op_hi = _LmtOperand(np.vstack([q.T, des.r_y[None, :]]), n, panel.npad, dev, keep_rem=True)
+        op_lo = _LmtOperand(op_hi.rem[:rank], n, panel.npad, dev)
+        w_t = torch.from_numpy(np.ascontiguousarray(des.w)).to(dev) if kq else None
+        bgb_t = torch.from_numpy(np.ascontiguousarray(des.bg_beta[q_base:])).to(dev) if kq else None
+        dixx_t = torch.from_numpy(np.diag(des.ixx)[q_base:].copy()).to(dev) if kq else None
+        br = int(block_rows) if block_rows else max(128, min(LMT_SCRATCH_BYTES // (8 * (2 * rank + 1)), 1 << 22) // 128 * 128)
+        br = max(1, min(br, mk))
+        hi = torch.empty((br, rank + 1), dtype=torch.float64, device=dev)
+        lo = torch.empty((br, rank + 1), dtype=torch.float64, device=dev)    # the kernel reads both with one leading dimension
+        for r0 in range(0, mk, br):
+            nr = min(br, mk - r0)
+            for op, dst in ((op_hi, hi), (op_lo, lo)):
+                check(lib().jxg_lmt_sums_p32(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr, mean_t[r0:].data_ptr(),
+                                             flip_t[r0:].data_ptr(), _ptr(op.planes), _ptr(op.scale), _ptr(op.colsum), op.ncols,
+                                             _ptr(dst), dst.shape[1], _stream()))
+            gy = hi[:, rank:]
+            if final:
+                check(lib().jxg_farmcpu_final_stats(_ptr(hi), _ptr(lo), rank + 1, rank, gy.data_ptr(), rank + 1, ss_t[r0:].data_ptr(),
+                                                    nr, des.bg_rss, des.df, out[r0:].data_ptr(), _stream()))
+            else:
+                check(lib().jxg_farmcpu_fem_stats(_ptr(hi), _ptr(lo), rank + 1, rank, gy.data_ptr(), rank + 1, ss_t[r0:].data_ptr(),
+                                                  nr, des.bg_rss, des.df, _ptr(w_t), rank, kq, _ptr(bgb_t), _ptr(dixx_t),
+                                                  out[r0:].data_ptr(), _ptr(maxbits), _stream()))
+    return des, out, maxbits[:kq]
+
+
+def scan_rows_farmcpu_fem(panel: Panel, rows: np.ndarray, af: np.ndarray, flip, x: np.ndarray, q_base: int, y: np.ndarray,
+                          block_rows=None) -> FarmcpuFem:
+    """Fixed-effect scan of FarmCPU's raw route (`scan_packed_full_matrix_reduced`, src/stats/farmcpu.rs:2629-2941) over the given
+    rows of a resident panel: `x` (n, q0) = [1 | covariates | pseudo-QTN columns] with the QTN columns from `q_base` on.  Rows
+    decode additively with major-allele imputation (`farmcpu_missing_value`).  Host: `farmcpu.design_operands`; device: the
+    products G [Q | r_y] (`jxg_lmt_sums_p32`, Q as two operands) and `jxg_farmcpu_fem_stats` per block of rows; the bits of a row
+    do not depend on `block_rows`.  -> FarmcpuFem(p: (len(rows),) f64 device tensor, void rows 1; qtn_min_p: host (q0 - q_base,)
+    = per QTN slot the p of the largest t^2 of its restated coefficient over the non-void rows (1 where there is none);
+    stats: (len(rows), 3) device tensor [beta, se, p], void rows (NaN, NaN, 1))."""
+    from . import lm2
+    des, out, maxbits = _farmcpu_scan(panel, rows, af, flip, x, q_base, y, False, block_rows)
+    t2 = maxbits.cpu().numpy().view(np.float64)
+    qmin = np.array([lm2.student_t_two_sided(math.sqrt(v), des.df) if v > 0.0 else 1.0 for v in t2], dtype=np.float64)
+    return FarmcpuFem(out[:, 2], qmin, out)
+
+
+def scan_rows_farmcpu_final(panel: Panel, rows: np.ndarray, af: np.ndarray, flip, x: np.ndarray, q_base: int, y: np.ndarray,
+                            block_rows=None) -> torch.Tensor:
+    """Final scan of FarmCPU's raw route against the final design (`write_farmcpu_packed_main_scan`, src/stats/farmcpu.rs:
+    3613-3650; `jxg_farmcpu_final_stats`): a (len(rows), 3) f64 device tensor [beta, se, p], three NaN for a void row.  The rows
+    of the QTNs themselves are the caller's (they take the background fit's coefficients)."""
+    return _farmcpu_scan(panel, rows, af, flip, x, q_base, y, True, block_rows)[1]
+
+
 def scan_rows_lm2(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, cov_sel: np.ndarray, y: np.ndarray, flip=None,
                   block_rows=LM_BLOCK_ROWS, progress=None, progress_every=0):
     """SNP-by-covariate interaction scan of the given SNP rows of a resident panel (`lm2_fit_single_snp`, src/stats/glm2.rs:
