@@ -17,6 +17,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
@@ -180,10 +181,7 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), (DBUF ? (EXACT ? 4 : 2)
     const int t = blockIdx.x + tile_base;     // tile_base > 0: a panel of tile rows (sparse GRM of large n, row panels)
     int ti, tj;
     if (RATIO == 1) {
-        ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while ((int64_t)ti * (ti + 1) / 2 > t) --ti;
-        while ((int64_t)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
-        tj = t - (int)((int64_t)ti * (ti + 1) / 2);
+        JX_TRI_TILE(t, ti, tj);
     } else {  // RATIO == 2: row block ti owns 2 * ti + 2 column blocks, ti * (ti + 1) precede it
         ti = (int)((sqrtf(4.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
         while ((int64_t)ti * (ti + 1) > t) --ti;
@@ -325,7 +323,7 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), (DBUF ? (EXACT ? 4 : 2)
         }
     }
 
-    // f64 merge: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    // f64 merge; the accumulators hold (cd_row, cd_col) of the 32 x 32 shapes (i8_tile.h)
     const bool add_corr = EXACT && corr != nullptr && k0 == k_begin;
     const double corr_b = add_corr ? corr[ld] : 0.0;
 #pragma unroll
@@ -336,7 +334,7 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), (DBUF ? (EXACT ? 4 : 2)
             const double corr_j = (add_corr && gj < ld) ? corr[gj] + corr_b : 0.0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t gi = (int64_t)ti * TM + wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t gi = cd_row(r, h, (int64_t)ti * TM + wm * WM + mi * 32);
                 if (gi < ld && gj < ld) {
                     double *dst = acc + gi * ld + gj;
                     double v = (double)c[mi][ni][r];

@@ -18,18 +18,16 @@
 
 #include <algorithm>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
 
-typedef int f4_i32x2 __attribute__((ext_vector_type(2)));
-typedef int f4_i32x8 __attribute__((ext_vector_type(8)));
 typedef float f4_f32x16 __attribute__((ext_vector_type(16)));
 
 // 16 two-bit codes -> 16 e2m1 nibbles of the counts (code 00 -> 0, 10 -> 1, 11 -> 2, 01 = missing / pad -> 0), nibble s = sample s
 __device__ __forceinline__ uint2 nib16_counts(uint32_t w) {
-    const uint32_t hi = (w >> 1) & 0x55555555u;
-    const uint32_t v = hi + (hi & w);                       // per 2-bit field: the count
+    const uint32_t v = count_field(w);
     auto spread = [](uint32_t y) {                          // 8 two-bit fields (16 bits) -> 8 nibbles holding field << 1
         y = (y | (y << 8)) & 0x00ff00ffu;
         y = (y | (y << 4)) & 0x0f0f0f0fu;
@@ -55,11 +53,11 @@ __global__ __launch_bounds__(256) void grm_nib_kernel(const uint8_t *__restrict_
 // MFMA operand of this lane (32 consecutive k of one position, e2m1) from a [k][position] nibble image: two transposed reads.
 // `lane_base` = image + (k0 + 32 (lane >> 5) + (lane & 15)) * PITCH + (pos0 + 16 ((lane >> 4) & 1)) / 2
 template <int PITCH>
-__device__ __forceinline__ f4_i32x8 tr4_frag(const uint8_t *lane_base) {
-    typedef __attribute__((address_space(3))) f4_i32x2 lds_i32x2;
-    const f4_i32x2 a = __builtin_amdgcn_ds_read_tr4_b64_v2i32((lds_i32x2 *)(lane_base));
-    const f4_i32x2 b = __builtin_amdgcn_ds_read_tr4_b64_v2i32((lds_i32x2 *)(lane_base + 16 * PITCH));
-    f4_i32x8 r = {a.x, a.y, b.x, b.y, 0, 0, 0, 0};
+__device__ __forceinline__ i32x8 tr4_frag(const uint8_t *lane_base) {
+    typedef __attribute__((address_space(3))) i32x2 lds_i32x2;
+    const i32x2 a = __builtin_amdgcn_ds_read_tr4_b64_v2i32((lds_i32x2 *)(lane_base));
+    const i32x2 b = __builtin_amdgcn_ds_read_tr4_b64_v2i32((lds_i32x2 *)(lane_base + 16 * PITCH));
+    i32x8 r = {a.x, a.y, b.x, b.y, 0, 0, 0, 0};
     return r;
 }
 
@@ -69,23 +67,18 @@ __global__ __launch_bounds__(512, 2) void grm_fp4_kernel(const uint8_t *__restri
     constexpr int TM = 256, WM = 128, WN = 64, BK = 128;
     constexpr int NWN = 4, NTHREADS = 512;
     constexpr int MI = WM / 32, NI = WN / 32;
-    constexpr int PITCH = TM / 2 + 8;              // bytes per SNP row of an image: 16 rows x 8 bytes of a transposed read on disjoint banks
-    constexpr int IMG = BK * PITCH;
-    constexpr int DW = TM / 16;                    // 8-byte groups (16 samples) per SNP row of a panel
-    constexpr int NL = BK * DW / NTHREADS;         // groups per thread, step and panel (4)
-    constexpr int SET = 2 * IMG;
+    // the nibble-width panel geometry of i8_tile.h (8-byte groups of 16 samples); the bytes are copied, not decoded, so the loads
+    // and the masked stores (0 = count 0) are written here
+    using Geom = PanelGeom<TM, BK, NTHREADS, 4>;
+    constexpr int PITCH = Geom::PITCH, IMG = Geom::IMG, SET = Geom::SET, NL = Geom::NL, DW = Geom::DW, KSTRIDE = Geom::KSTRIDE;
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * SET];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / NWN, wn = wave % NWN;
-    const int t = blockIdx.x + tile_base;
-    int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while ((int64_t)ti * (ti + 1) / 2 > t) --ti;
-    while ((int64_t)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int tj = t - (int)((int64_t)ti * (ti + 1) / 2);
+    int ti, tj;
+    JX_TRI_TILE(blockIdx.x + tile_base, ti, tj);
 
     const int d_of = tid % DW, kk_of = tid / DW;   // group of the panel row, SNP of the step (+ u * KSTRIDE)
-    constexpr int KSTRIDE = NTHREADS / DW;
     const int recA128 = ti * 2 + (d_of >> 3), recB128 = tj * 2 + (d_of >> 3);
     const uint32_t maskA = recA128 < nt128 ? 0xffffffffu : 0u, maskB = recB128 < nt128 ? 0xffffffffu : 0u;
     const uint8_t *const baseA = nib + (int64_t)(recA128 < nt128 ? recA128 : nt128 - 1) * cnt * 64 + 8 * (d_of & 7);
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(512, 2) void grm_fp4_kernel(const uint8_t *__restri
     const int lane_off = (32 * h + (lane & 15)) * PITCH + 8 * ((lane >> 4) & 1);
     auto mfma_ks = [&](const uint8_t *base, int ks) {
         const uint8_t *sA = base + lane_off + (wm * WM) / 2 + ks * 64 * PITCH, *sB = base + IMG + lane_off + (wn * WN) / 2 + ks * 64 * PITCH;
-        f4_i32x8 a[MI], b[NI];
+        i32x8 a[MI], b[NI];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) a[mi] = tr4_frag<PITCH>(sA + mi * 16);
 #pragma unroll
@@ -156,18 +149,18 @@ __global__ __launch_bounds__(512, 2) void grm_fp4_kernel(const uint8_t *__restri
         cur ^= 1;
     }
 
-    // f64 merge (C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)); position = sample
+    // f64 merge; the accumulators hold (cd_row, cd_col) of the 32 x 32 shapes, position = sample
     const bool add_corr = corr != nullptr;
     const double corr_b = add_corr ? corr[ld] : 0.0;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-            const int64_t gj = (int64_t)tj * TM + wn * WN + ni * 32 + (lane & 31);
+            const int64_t gj = (int64_t)tj * TM + wn * WN + ni * 32 + cd_col(lane);
             const double corr_j = (add_corr && gj < ld) ? corr[gj] + corr_b : 0.0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t gi = (int64_t)ti * TM + wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t gi = cd_row(r, h, (int64_t)ti * TM + wm * WM + mi * 32);
                 if (gi < ld && gj < ld) {
                     double *dst = acc + gi * ld + gj;
                     double v = (double)c[mi][ni][r];

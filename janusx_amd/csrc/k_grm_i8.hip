@@ -11,15 +11,11 @@
 // terms are one f64 matrix-vector product over the payload (jxg_packed_dot), added in the first chunk's merge.
 //
 // Design (gfx950):
-//  * decode is pure VALU, 11 instructions per payload dword (16 samples): value fields V = hi + (hi & w), hi = (w >> 1) &
-//    0x5555..., (code 00 -> 0, 10 -> 1, 11 -> 2, 01 = missing / pad -> 0), then the four dwords (V >> 2q) & 0x03030303:
-//    byte 4q + b of the 16-byte group holds sample 4b + q.  No table lookups, no per-SNP value LUT, no flips.  The sample
-//    order inside a 16-group is therefore a fixed 4 x 4 transposition `pos_to_sample`, applied once in the merge;
-//  * LDS images are [k = SNP][position] with one BYTE per element (half the LDS traffic of the fp16 images), written with
-//    one ds_write_b128 per payload dword; MFMA operands (16 consecutive k of one position per lane) come from two
-//    ds_read_b64_tr_b8 transposed reads (lane map measured with scripts/probes/i8_probe.hip: inside a 16-lane group
-//    supplier lane 2 e + c provides row e, columns 8 c .. 8 c + 7, and lane i receives column i); the pitch (row + 32 B)
-//    puts the eight rows of a transposed read on disjoint banks;
+//  * decode is pure VALU, 11 instructions per payload dword (16 samples): `counts16` of i8_tile.h (code 00 -> 0, 10 -> 1,
+//    11 -> 2, 01 = missing / pad -> 0).  No table lookups, no per-SNP value LUT, no flips.  i8_tile.h defines the byte order inside
+//    a 16-group, `pos_to_sample` that undoes it once in the merge, the LDS images ([k = SNP][position], one BYTE per element: half
+//    the LDS traffic of the fp16 images, one ds_write_b128 per payload dword), their pitch, the masking of rows beyond the chunk
+//    and tiles beyond the panel, and the transposed fragment reads (two ds_read_b64_tr_b8 per MFMA operand);
 //  * large n: 256 x 256 output tile per 512-thread workgroup (8 waves of 128 x 64), one workgroup per CU, two image sets:
 //    the decode of step k + 1 shares a barrier interval with the MFMAs of step k (decode bytes and fragment reads per
 //    MFMA are half those of a 128 x 128 tile); few tiles / row panels: 128 x 128 per 256-thread workgroup, 4 per CU.
@@ -31,29 +27,6 @@
 #include "jx_common.h"
 
 namespace jx {
-
-// 16 two-bit codes -> 16 count bytes (see the header for the order)
-__device__ __forceinline__ u32x4v decode16_counts(uint32_t w) {
-    const uint32_t hi = (w >> 1) & 0x55555555u;
-    const uint32_t v = hi + (hi & w);                      // per 2-bit field: b1 + (b1 & b0)
-    u32x4v o;
-    o.x = v & 0x03030303u;
-    o.y = (v >> 2) & 0x03030303u;
-    o.z = (v >> 4) & 0x03030303u;
-    o.w = (v >> 6) & 0x03030303u;
-    return o;
-}
-
-// 16 two-bit codes -> 16 bytes through a per-SNP byte LUT (byte c of `lut` = value of code c): v_perm_b32 with the code bytes
-// as selectors.  Same byte order as decode16_counts.
-__device__ __forceinline__ u32x4v decode16_lut(uint32_t w, uint32_t lut) {
-    u32x4v o;
-    o.x = __builtin_amdgcn_perm(lut, lut, w & 0x03030303u);
-    o.y = __builtin_amdgcn_perm(lut, lut, (w >> 2) & 0x03030303u);
-    o.z = __builtin_amdgcn_perm(lut, lut, (w >> 4) & 0x03030303u);
-    o.w = __builtin_amdgcn_perm(lut, lut, (w >> 6) & 0x03030303u);
-    return o;
-}
 
 // LUT = true: the operand bytes come from a per-SNP byte LUT `luts[k]` (byte c = value of the 2-bit code c; k = position in the
 // row list) instead of the counts {0, 0, 1, 2}, and the i32 Gram is scaled by `gscale` in the merge: the two-Gram form of rows
@@ -67,12 +40,8 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), MINW) void grm_i8_kerne
     constexpr int NWN = TN / WN;
     constexpr int NTHREADS = 64 * (TM / WM) * NWN;
     constexpr int MI = WM / 32, NI = WN / 32;
-    constexpr int PITCH = TM + 32;                 // bytes per SNP row of an image
-    constexpr int IMG = BK * PITCH;
-    constexpr int DW = TM / 16;                    // payload dwords per SNP row of a panel
-    constexpr int NL = BK * DW / NTHREADS;         // payload dwords per thread, step and panel
-    static_assert(NL * NTHREADS == BK * DW && BK % 32 == 0, "panel dwords must divide evenly");
-    constexpr int SET = 2 * IMG;                   // A image, B image
+    using Reader = PanelReader<TM, BK, NTHREADS, 0u>;   // fill 0: code 00 = count 0 = byte 0 of a LUT, masked rows / tiles vanish
+    constexpr int PITCH = Reader::PITCH, IMG = Reader::IMG, SET = Reader::SET, NL = Reader::NL;
     __shared__ __attribute__((aligned(16))) uint8_t smem[(DBUF ? 2 : 1) * SET];
 
     const int tid = threadIdx.x;
@@ -80,52 +49,30 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), MINW) void grm_i8_kerne
     const int wave = tid >> 6;
     const int wm = wave / NWN, wn = wave % NWN;
 
-    // lower-triangle tile (ti >= tj) of TM x TM blocks
-    const int t = blockIdx.x + tile_base;
-    int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while ((int64_t)ti * (ti + 1) / 2 > t) --ti;
-    while ((int64_t)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int tj = t - (int)((int64_t)ti * (ti + 1) / 2);
+    int ti, tj;                                    // lower-triangle tile (ti >= tj) of TM x TM blocks
+    JX_TRI_TILE(blockIdx.x + tile_base, ti, tj);
 
     const int64_t k0 = k_begin + (int64_t)blockIdx.y * kchunk;
     const int64_t k1 = (k0 + kchunk < k_end) ? (k0 + kchunk) : k_end;
 
-    // decode mapping: dword idx = tid + u NTHREADS -> (SNP kk = idx / DW of the step, dword d = idx % DW of the panel row);
-    // both panels use the same (kk, d), so one record index per u serves both
-    const int d_of = tid % DW;
-    const int kk_of = tid / DW;                    // + u * (NTHREADS / DW)
-    constexpr int KSTRIDE = NTHREADS / DW;
-    const int recA128 = ti * (TM / 128) + (d_of >> 3), recB128 = tj * (TM / 128) + (d_of >> 3);
-    // Nothing in the step loop is conditional: loads go to clamped (always valid) addresses and are consumed one step
-    // later, where rows beyond the chunk / tiles beyond the panel are zeroed with a mask (codes 00 = count 0).  A guarded
-    // load is a branch around the load plus a wait right behind it, and branches keep the decode out of the MFMA gaps.
-    const uint32_t maskA = recA128 < nt128 ? 0xffffffffu : 0u, maskB = recB128 < nt128 ? 0xffffffffu : 0u;
-    const uint8_t *const baseA = p32 + (int64_t)(recA128 < nt128 ? recA128 : nt128 - 1) * m_total * 32 + 4 * (d_of & 7);
-    const uint8_t *const baseB = p32 + (int64_t)(recB128 < nt128 ? recB128 : nt128 - 1) * m_total * 32 + 4 * (d_of & 7);
-
+    const Reader rd(p32, m_total, nt128, ti, tj);
     int32_t rec[NL];                               // payload record (SNP row), loaded two steps ahead of its payload's use
     uint32_t lutn[NL], lutw[NL];                   // LUT: the SNP's byte LUT, travelling with rec (lutn) and with the payload (lutw)
     uint32_t wA[NL], wB[NL];                       // payload dwords, loaded one step ahead of their decode
     auto load_rec = [&](int u, int64_t kbase) {
-        const int64_t k = kbase + kk_of + u * KSTRIDE;
-        rec[u] = rows[k < k1 ? k : k1 - 1];
-        if constexpr (LUT) lutn[u] = luts[k < k1 ? k : k1 - 1];
+        const int64_t k = rd.row(u, kbase, k1);
+        rec[u] = rows[k];
+        if constexpr (LUT) lutn[u] = luts[k];
     };
     auto load_payload = [&](int u) {               // consumes rec[u]
-        wA[u] = *reinterpret_cast<const uint32_t *>(baseA + (int64_t)rec[u] * 32);
-        wB[u] = *reinterpret_cast<const uint32_t *>(baseB + (int64_t)rec[u] * 32);
+        rd.load(rec[u], wA[u], wB[u]);
         if constexpr (LUT) lutw[u] = lutn[u];
     };
     auto decode_to = [&](uint8_t *base, int u, int64_t kbase) {     // payload of the step that starts at kbase
-        const bool valid = kbase + kk_of + u * KSTRIDE < k1;
-        const int o = (kk_of + u * KSTRIDE) * PITCH + d_of * 16;
         if constexpr (LUT) {
-            // code 00 -> byte 0 of the LUT = 0: masked rows / tiles vanish as in the count decode
-            *reinterpret_cast<u32x4v *>(base + o) = decode16_lut(wA[u] & (valid ? maskA : 0u), lutw[u]);
-            *reinterpret_cast<u32x4v *>(base + IMG + o) = decode16_lut(wB[u] & (valid ? maskB : 0u), lutw[u]);
+            rd.store(base, u, kbase, k1, wA[u], wB[u], [&](uint32_t w) { return lut16(w, lutw[u]); });
         } else {
-            *reinterpret_cast<u32x4v *>(base + o) = decode16_counts(wA[u] & (valid ? maskA : 0u));
-            *reinterpret_cast<u32x4v *>(base + IMG + o) = decode16_counts(wB[u] & (valid ? maskB : 0u));
+            rd.store(base, u, kbase, k1, wA[u], wB[u], [](uint32_t w) { return counts16(w); });
         }
     };
 
@@ -138,7 +85,7 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), MINW) void grm_i8_kerne
             for (int r = 0; r < 16; ++r) c[mi][ni][r] = 0;
 
     const int h = lane >> 5;
-    const int lane_off = (16 * h + ((lane & 15) >> 1)) * PITCH + 16 * ((lane >> 4) & 1) + 8 * (lane & 1);
+    const int lane_off = frag_lane_off<PITCH>(lane, h);
     auto mfma_ks = [&](const uint8_t *base, int ks) {
         const uint8_t *sA = base + lane_off + wm * WM + ks * 32 * PITCH, *sB = base + IMG + lane_off + wn * WN + ks * 32 * PITCH;
         i32x4 a[MI], b[NI];
@@ -210,19 +157,18 @@ __global__ __launch_bounds__(64 * (TM / WM) * (TN / WN), MINW) void grm_i8_kerne
         }
     }
 
-    // f64 merge.  C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): tile
-    // POSITIONS, mapped to samples by pos_to_sample.
+    // f64 merge.  The accumulators hold tile POSITIONS (cd_row, cd_col), mapped to samples by pos_to_sample.
     const bool add_corr = corr != nullptr && k0 == k_begin;
     const double corr_b = add_corr ? corr[ld] : 0.0;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-            const int64_t gj = (int64_t)tj * TN + pos_to_sample(wn * WN + ni * 32 + (lane & 31));
+            const int64_t gj = (int64_t)tj * TN + pos_to_sample(wn * WN + ni * 32 + cd_col(lane));
             const double corr_j = (add_corr && gj < ld) ? corr[gj] + corr_b : 0.0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t gi = (int64_t)ti * TM + pos_to_sample(wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
+                const int64_t gi = (int64_t)ti * TM + pos_to_sample(cd_row(r, h, wm * WM + mi * 32));
                 if (gi < ld && gj < ld) {
                     double *dst = acc + gi * ld + gj;
                     double v = (double)c[mi][ni][r];

@@ -8,8 +8,8 @@
 // and kinship = (both_het - 2 ibs0) / (het_i + het_j) in f64, NaN when the denominator is 0.
 //
 // Design (gfx950):
-//  * the LDS images are [k = SNP][position] with one byte per element as in k_grm_i8.hip (same pitch, same 4 x 4 position order inside
-//    a 16-sample group, same transposed fragment reads), but the byte is the raw 2-bit CODE (0..3), not a value: one image per
+//  * the LDS images are the [k = SNP][position] byte images of i8_tile.h (its pitch, its 4 x 4 position order inside a 16-sample
+//    group, its transposed fragment reads), but the byte is the raw 2-bit CODE (0..3), not a value: one image per
 //    side serves every indicator.  A lane turns its fragment (16 code bytes of one position) into an indicator operand with four
 //    v_perm_b32 against a compile-time byte LUT, in registers, right in front of the MFMAs that consume it.  Decoding into four
 //    indicator images per side instead would cost four times the LDS writes and four times the fragment reads, and the fragment
@@ -37,28 +37,6 @@ constexpr int KING_BK = 64;                        // SNP rows per step of every
 
 // byte c of a LUT = value of the 2-bit code c (0 = 00 hom-ref, 1 = 01 missing, 2 = 10 het, 3 = 11 hom-alt)
 constexpr uint32_t KG_Z = 0x00000001u, KG_H = 0x00010000u, KG_A = 0x01000000u, KG_N = 0x01010001u;
-constexpr uint32_t KG_MISSING = 0x55555555u;       // 16 codes 01
-
-// 16 two-bit codes -> 16 code bytes: byte 4 q + b = sample 4 b + q of the dword (the order `pos_to_sample` undoes)
-__device__ __forceinline__ u32x4v kg_codes(uint32_t w) {
-    u32x4v o;
-    o.x = w & 0x03030303u;
-    o.y = (w >> 2) & 0x03030303u;
-    o.z = (w >> 4) & 0x03030303u;
-    o.w = (w >> 6) & 0x03030303u;
-    return o;
-}
-
-// 16 code bytes -> 16 indicator bytes through a byte LUT
-template <uint32_t LUT>
-__device__ __forceinline__ i32x4 kg_ind(const i32x4 c) {
-    i32x4 o;
-    o.x = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.x);
-    o.y = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.y);
-    o.z = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.z);
-    o.w = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.w);
-    return o;
-}
 
 #define KG_MFMA(a, b, c) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0)
 
@@ -74,16 +52,11 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
     constexpr int NTHREADS = 64 * NW * NW;
     constexpr int FI = WT / 32;                    // 32 x 32 MFMA tiles per side of a wave
     constexpr int NACC = COUNTS ? 6 : 3;
-    constexpr int PITCH = TM + 32;                 // bytes per SNP row of an image
-    constexpr int IMG = BK * PITCH;
-    constexpr int DW = TM / 16;                    // payload dwords per SNP row of a panel
-    constexpr int NL = BK * DW / NTHREADS;         // payload dwords per thread, step and panel
-    static_assert(NL * NTHREADS == BK * DW && NL >= 1 && BK % 32 == 0 && 128 % TM == 0, "panel dwords must divide evenly");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[2 * IMG];
+    using Reader = PanelReader<TM, BK, NTHREADS, P32_ALL_MISSING>;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[Reader::SET];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int wave = threadIdx.x >> 6;
     const int wm = wave / NW, wn = wave % NW;
 
     int ti, tj;
@@ -91,38 +64,14 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
         ti = ti0 + (int)blockIdx.y;
         tj = tj0 + (int)blockIdx.x;
     } else {
-        const int t = blockIdx.x;                  // lower-triangle tile (ti >= tj)
-        ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while ((int64_t)ti * (ti + 1) / 2 > t) --ti;
-        while ((int64_t)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
-        tj = t - (int)((int64_t)ti * (ti + 1) / 2);
+        JX_TRI_TILE(blockIdx.x, ti, tj);              // lower-triangle tile (ti >= tj)
     }
 
-    // decode mapping: dword idx = tid + u NTHREADS -> (SNP kk = idx / DW of the step, dword d = idx % DW of the panel row); dword
-    // ti DW + d of the sample axis lies in the 128-sample record (ti DW + d) / 8 at dword (ti DW + d) % 8
-    const int d_of = tid % DW;
-    const int kk_of = tid / DW;                    // + u * KSTRIDE
-    constexpr int KSTRIDE = NTHREADS / DW;
-    const int gdA = ti * DW + d_of, gdB = tj * DW + d_of;
-    const int recA = gdA >> 3, recB = gdB >> 3;
-    // loads go to clamped (always valid) addresses; rows beyond m and records beyond the panel become all-missing words
-    const bool inA = recA < nt128, inB = recB < nt128;
-    const uint8_t *const baseA = p32 + (int64_t)(inA ? recA : nt128 - 1) * m * 32 + 4 * (gdA & 7);
-    const uint8_t *const baseB = p32 + (int64_t)(inB ? recB : nt128 - 1) * m * 32 + 4 * (gdB & 7);
-
+    const Reader rd(p32, m, nt128, ti, tj);
+    constexpr int NL = Reader::NL, PITCH = Reader::PITCH, IMG = Reader::IMG;
     uint32_t wA[NL], wB[NL];                       // payload dwords, loaded one step ahead of their use
-    auto load_payload = [&](int u, int64_t kbase) {
-        const int64_t k = kbase + kk_of + u * KSTRIDE;
-        const int64_t kc = k < m ? k : m - 1;
-        wA[u] = *reinterpret_cast<const uint32_t *>(baseA + kc * 32);
-        wB[u] = *reinterpret_cast<const uint32_t *>(baseB + kc * 32);
-    };
-    auto store_codes = [&](int u, int64_t kbase) {
-        const bool valid = kbase + kk_of + u * KSTRIDE < m;
-        const int o = (kk_of + u * KSTRIDE) * PITCH + d_of * 16;
-        *reinterpret_cast<u32x4v *>(smem + o) = kg_codes(valid && inA ? wA[u] : KG_MISSING);
-        *reinterpret_cast<u32x4v *>(smem + IMG + o) = kg_codes(valid && inB ? wB[u] : KG_MISSING);
-    };
+    auto load_payload = [&](int u, int64_t kbase) { rd.load(rd.row(u, kbase, m), wA[u], wB[u]); };
+    auto store_codes = [&](int u, int64_t kbase) { rd.store(smem, u, kbase, m, wA[u], wB[u], [](uint32_t w) { return codes16(w); }); };
 
     i32x16 c[NACC][FI][FI];
 #pragma unroll
@@ -134,8 +83,7 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
 #pragma unroll
                 for (int r = 0; r < 16; ++r) c[p][a][b][r] = 0;
 
-    const int h = lane >> 5;
-    const int lane_off = (16 * h + ((lane & 15) >> 1)) * PITCH + 16 * ((lane >> 4) & 1) + 8 * (lane & 1);
+    const int lane_off = frag_lane_off<PITCH>(lane, h);
     auto mfma_ks = [&](int ks) {
         const uint8_t *sA = smem + lane_off + wm * WT + ks * 32 * PITCH, *sB = smem + IMG + lane_off + wn * WT + ks * 32 * PITCH;
         i32x4 ca[FI], cb[FI];
@@ -146,14 +94,14 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
         i32x4 zb[FI], hb[FI], ab[FI], nb[FI];
 #pragma unroll
         for (int b = 0; b < FI; ++b) {
-            zb[b] = kg_ind<KG_Z>(cb[b]);
-            hb[b] = kg_ind<KG_H>(cb[b]);
-            ab[b] = kg_ind<KG_A>(cb[b]);
-            nb[b] = kg_ind<KG_N>(cb[b]);
+            zb[b] = lut_frag<KG_Z>(cb[b]);
+            hb[b] = lut_frag<KG_H>(cb[b]);
+            ab[b] = lut_frag<KG_A>(cb[b]);
+            nb[b] = lut_frag<KG_N>(cb[b]);
         }
 #pragma unroll
         for (int a = 0; a < FI; ++a) {
-            const i32x4 za = kg_ind<KG_Z>(ca[a]), ha = kg_ind<KG_H>(ca[a]), aa = kg_ind<KG_A>(ca[a]), na = kg_ind<KG_N>(ca[a]);
+            const i32x4 za = lut_frag<KG_Z>(ca[a]), ha = lut_frag<KG_H>(ca[a]), aa = lut_frag<KG_A>(ca[a]), na = lut_frag<KG_N>(ca[a]);
 #pragma unroll
             for (int b = 0; b < FI; ++b) {
                 if constexpr (COUNTS) {            // plane order: the fields of KingBitCounts
@@ -190,15 +138,15 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
         __syncthreads();
     }
 
-    // C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): tile POSITIONS
+    // the accumulators hold tile POSITIONS (cd_row, cd_col)
 #pragma unroll
     for (int a = 0; a < FI; ++a)
 #pragma unroll
         for (int b = 0; b < FI; ++b) {
-            const int64_t gj = (int64_t)tj * TM + pos_to_sample(wn * WT + b * 32 + (lane & 31));
+            const int64_t gj = (int64_t)tj * TM + pos_to_sample(wn * WT + b * 32 + cd_col(lane));
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t gi = (int64_t)ti * TM + pos_to_sample(wm * WT + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
+                const int64_t gi = (int64_t)ti * TM + pos_to_sample(cd_row(r, h, wm * WT + a * 32));
                 if constexpr (COUNTS) {
                     if (gi >= i0 && gi < i1 && gj >= j0 && gj < j1) {
                         const int64_t ni = i1 - i0, nj = j1 - j0, o = (gi - i0) * nj + (gj - j0);
@@ -214,21 +162,12 @@ __global__ __launch_bounds__(64 * (TM / WT) * (TM / WT), 2) void king_kernel(
                         kin = ((double)hh - 2.0 * (double)ibs0) / (double)den;
                         hit = kin >= threshold;
                     }
-                    const unsigned long long bal = __ballot(hit);
-                    if (bal) {                                              // wave-uniform
-                        const int leader = __ffsll((long long)bal) - 1;
-                        unsigned long long base = 0ull;
-                        if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(bal));
-                        base = ((unsigned long long)(uint32_t)__shfl((int)(base >> 32), leader, 64) << 32) |
-                               (unsigned long long)(uint32_t)__shfl((int)(base & 0xffffffffull), leader, 64);
-                        const unsigned long long slot = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
-                        if (hit && slot < cap) {
-                            out_i[slot] = (uint32_t)gj;
-                            out_j[slot] = (uint32_t)gi;
-                            out_ibs0[slot] = (uint32_t)ibs0;
-                            out_kin[slot] = kin;
-                        }
-                    }
+                    wave_append(hit, counter, cap, [&](unsigned long long slot) {
+                        out_i[slot] = (uint32_t)gj;
+                        out_j[slot] = (uint32_t)gi;
+                        out_ibs0[slot] = (uint32_t)ibs0;
+                        out_kin[slot] = kin;
+                    });
                 }
             }
         }

@@ -5,7 +5,7 @@
 // dosage (0 at a missing call) and v the called indicator of a row:
 //     D = sum g_i g_j,  N = sum v_i v_j,  S_i = sum g_i v_j,  S_j = sum v_i g_j,  Q_i = sum g_i^2 v_j,  Q_j = sum v_i g_j^2
 // The planes g (0/1/2), g^2 (0/1/4) and v (0/1) of 16 two-bit codes are decoded in registers from the lane's own payload dword,
-// as `rs_planes` of k_rsvd.hip does, and are both operands of v_mfma_i32_16x16x64_i8: A holds 16 SNPs i (row = lane & 15), B 16
+// with the decoders of i8_tile.h, and are both operands of v_mfma_i32_16x16x64_i8: A holds 16 SNPs i (row = lane & 15), B 16
 // SNPs j (column = lane & 15), the lane's quarter (lane >> 4) its 16 samples of a 64-sample step.  Lane (s, kq) then holds the
 // sums of the pairs (i0 + 4 kq + r, j0 + s), r = 0..3.  Pad samples of the image are code 01 (missing) and add nothing.
 //
@@ -29,11 +29,10 @@
 //                the i-block to the one that holds its largest end; a wave adds its 32 x 32 values along j (in lane over its two
 //                j tiles, then over the 16 lanes of a quarter) and writes one f64 per (row, j-block); a second kernel adds the
 //                self term and the partials of a row in ascending j-block.
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
-
-typedef int ld_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LD_WAVES = 4;          // waves per workgroup: four j-blocks of one i-block
 constexpr int LD_U = 2;              // MFMA tiles of 16 SNPs per side of a wave's block
@@ -42,34 +41,14 @@ constexpr int LD_B = 16 * LD_U;      // SNPs per side of a wave's block
 // multiplies two sums in f64 (D N, Q N, S S <= 4 n^2), exact below 2^53: n <= 2^24 keeps every product an exact integer.
 constexpr int LD_MAX_N = 1 << 24;
 
-__device__ __forceinline__ ld_i32x4 ld_bytes(uint32_t f, uint32_t keep) {
-    ld_i32x4 o;                                   // byte 4 q + b = element 4 b + q, the same for both operands
-    o.x = (int)(f & keep);
-    o.y = (int)((f >> 2) & keep);
-    o.z = (int)((f >> 4) & keep);
-    o.w = (int)((f >> 6) & keep);
-    return o;
-}
-
-// dose plane of 16 two-bit codes (00 -> 0, 10 -> 1, 11 -> 2, 01 -> 0)
-__device__ __forceinline__ ld_i32x4 ld_dose(uint32_t w) {
-    const uint32_t l = w & 0x55555555u, h = (w >> 1) & 0x55555555u;
-    return ld_bytes(h + (l & h), 0x03030303u);    // 0, 1, 2 per field: no carry into the next field
-}
-
-// g^2 (0 / 1 / 4) from the dose bytes, and the called plane
-__device__ __forceinline__ ld_i32x4 ld_square(const ld_i32x4 g) {
-    ld_i32x4 q;
+// g^2 (0 / 1 / 4) from the dose bytes (`counts16` of i8_tile.h)
+__device__ __forceinline__ i32x4 ld_square(const i32x4 g) {
+    i32x4 q;
     q.x = (g.x & 0x01010101) | ((g.x & 0x02020202) << 1);
     q.y = (g.y & 0x01010101) | ((g.y & 0x02020202) << 1);
     q.z = (g.z & 0x01010101) | ((g.z & 0x02020202) << 1);
     q.w = (g.w & 0x01010101) | ((g.w & 0x02020202) << 1);
     return q;
-}
-
-__device__ __forceinline__ ld_i32x4 ld_called(uint32_t w) {
-    const uint32_t l = w & 0x55555555u, h = (w >> 1) & 0x55555555u;
-    return ld_bytes((l ^ 0x55555555u) | h, 0x01010101u);
 }
 
 // record (row of the P32 image) of position o of the row list, positions past the end read the last row (their sums are unused)
@@ -81,7 +60,7 @@ __device__ __forceinline__ int64_t ld_record(const int32_t *__restrict__ rows, i
 // acc[p][ui][uj]: p = 0 D, and with SIX 1 N, 2 S_i, 3 S_j, 4 Q_i, 5 Q_j
 template <bool SIX>
 __device__ __forceinline__ void ld_main(const uint8_t *__restrict__ p32, int64_t tstride, int ntiles, const int32_t *__restrict__ rows,
-                                        int nrows, int i0, int j0, ld_i32x4 (&acc)[SIX ? 6 : 1][LD_U][LD_U]) {
+                                        int nrows, int i0, int j0, i32x4 (&acc)[SIX ? 6 : 1][LD_U][LD_U]) {
     const int lane = threadIdx.x & 63, s = lane & 15, kq = lane >> 4;
     const uint8_t *pi[LD_U], *pj[LD_U];
 #pragma unroll
@@ -94,7 +73,7 @@ __device__ __forceinline__ void ld_main(const uint8_t *__restrict__ p32, int64_t
 #pragma unroll
         for (int a = 0; a < LD_U; ++a)
 #pragma unroll
-            for (int b = 0; b < LD_U; ++b) acc[p][a][b] = ld_i32x4{0, 0, 0, 0};
+            for (int b = 0; b < LD_U; ++b) acc[p][a][b] = i32x4{0, 0, 0, 0};
     uint2 ni[LD_U], nj[LD_U];                                 // the next tile's words are in flight under this tile's products
 #pragma unroll
     for (int u = 0; u < LD_U; ++u) {
@@ -113,22 +92,22 @@ __device__ __forceinline__ void ld_main(const uint8_t *__restrict__ p32, int64_t
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            ld_i32x4 gi[LD_U], gj[LD_U];
+            i32x4 gi[LD_U], gj[LD_U];
 #pragma unroll
             for (int u = 0; u < LD_U; ++u) {
-                gi[u] = ld_dose(h ? wi[u].y : wi[u].x);
-                gj[u] = ld_dose(h ? wj[u].y : wj[u].x);
+                gi[u] = (i32x4)counts16(h ? wi[u].y : wi[u].x);
+                gj[u] = (i32x4)counts16(h ? wj[u].y : wj[u].x);
             }
 #pragma unroll
             for (int a = 0; a < LD_U; ++a)
 #pragma unroll
                 for (int b = 0; b < LD_U; ++b) acc[0][a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(gi[a], gj[b], acc[0][a][b], 0, 0, 0);
             if constexpr (SIX) {
-                ld_i32x4 vi[LD_U], vj[LD_U], qi[LD_U], qj[LD_U];
+                i32x4 vi[LD_U], vj[LD_U], qi[LD_U], qj[LD_U];
 #pragma unroll
                 for (int u = 0; u < LD_U; ++u) {
-                    vi[u] = ld_called(h ? wi[u].y : wi[u].x);
-                    vj[u] = ld_called(h ? wj[u].y : wj[u].x);
+                    vi[u] = (i32x4)called16(h ? wi[u].y : wi[u].x);
+                    vj[u] = (i32x4)called16(h ? wj[u].y : wj[u].x);
                     qi[u] = ld_square(gi[u]);
                     qj[u] = ld_square(gj[u]);
                 }
@@ -147,7 +126,7 @@ __device__ __forceinline__ void ld_main(const uint8_t *__restrict__ p32, int64_t
     }
 }
 
-__device__ __forceinline__ int ld_elem(const ld_i32x4 a, int r) { return r == 0 ? a.x : (r == 1 ? a.y : (r == 2 ? a.z : a.w)); }
+__device__ __forceinline__ int ld_elem(const i32x4 a, int r) { return r == 0 ? a.x : (r == 1 ? a.y : (r == 2 ? a.z : a.w)); }
 
 // r^2 of a pair with both rows complete: src/stats/ld.rs:339-355
 __device__ __forceinline__ double ld_r2_clean(int d, double nf, double denom, double mean_i, double mean_j, double sd_i, double sd_j) {
@@ -177,7 +156,7 @@ __device__ __forceinline__ void ld_band_block(const uint8_t *__restrict__ p32, i
                                               const int32_t *__restrict__ band_end, const double *__restrict__ mean,
                                               const double *__restrict__ sd, const uint8_t *__restrict__ hasmiss, double thresh,
                                               int wpr, uint32_t *__restrict__ mask) {
-    ld_i32x4 acc[SIX ? 6 : 1][LD_U][LD_U];
+    i32x4 acc[SIX ? 6 : 1][LD_U][LD_U];
     ld_main<SIX>(p32, tstride, ntiles, rows, nrows, i0, j0, acc);
     const int lane = threadIdx.x & 63, s = lane & 15, kq = lane >> 4;
     const double nf = (double)n, denom = (double)(n - 1 > 1 ? n - 1 : 1);
@@ -269,7 +248,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) void ld_sums_kernel(const uint8_t *_
     const int64_t ibl = (int64_t)i0 + (int64_t)blockIdx.y * LD_B, jbl = (int64_t)j0 + ((int64_t)blockIdx.x * LD_WAVES + wave) * LD_B;
     if (ibl >= i1 || jbl >= j1) return;
     const int ib = (int)ibl, jb = (int)jbl;
-    ld_i32x4 acc[6][LD_U][LD_U];
+    i32x4 acc[6][LD_U][LD_U];
     ld_main<true>(p32, m_total * 32, ntiles, rows, nrows, ib, jb, acc);
     const int64_t ni = i1 - i0, nj = j1 - j0;
 #pragma unroll
@@ -289,7 +268,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) void ld_sums_kernel(const uint8_t *_
 // has no positive denominator or a non-finite covariance (a finite covariance cannot give a non-finite square here: the square
 // stays below 1e40) and where the pairwise-complete formula has no value
 template <bool SIX>
-__device__ __forceinline__ double ld_score_pair(const ld_i32x4 (&acc)[SIX ? 6 : 1][LD_U][LD_U], int a, int b, int r, bool clean, double nf,
+__device__ __forceinline__ double ld_score_pair(const i32x4 (&acc)[SIX ? 6 : 1][LD_U][LD_U], int a, int b, int r, bool clean, double nf,
                                                 double denom, double mean_i, double mean_j, double sd_i, double sd_j) {
     double r2;
     if (!SIX || clean)
@@ -336,7 +315,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2
     const int j0 = (jb0 + x) * LD_B;                          // <= hi - 1 < nrows
     if (lane < LD_B && j0 + lane < nrows) miss |= hasmiss[j0 + lane];
     if ((__ballot(miss != 0) != 0ull) != SIX) return;         // wave-uniform
-    ld_i32x4 acc[SIX ? 6 : 1][LD_U][LD_U];
+    i32x4 acc[SIX ? 6 : 1][LD_U][LD_U];
     ld_main<SIX>(p32, m_total * 32, ntiles, rows, nrows, i0, j0, acc);
     const double nf = (double)n, denom = (double)(n - 1 > 1 ? n - 1 : 1);
 #pragma unroll

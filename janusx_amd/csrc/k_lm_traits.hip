@@ -10,8 +10,8 @@
 // whose entries are multiples of S 2^-27 splits exactly.  Three planes (the rotation's count) leave 2^-21: 1e-5 on beta at
 // n = 300 .. 20 000, over the bar; four leave 1e-7 (DESIGN 3.16 derives the bound).
 //
-// Product: the called genotypes are the exact int8 operand c in {0, 1, 2} (ri_decode16 of k_rotate_i8.hip), the missing calls a
-// second exact operand e in {0, 1} (ri_decode16_missing); both meet the same four planes in v_mfma_i32_32x32x32_i8 products whose
+// Product: the called genotypes are the exact int8 operand c in {0, 1, 2} (`counts16` of i8_tile.h), the missing calls a
+// second exact operand e in {0, 1} (`missing16`); both meet the same four planes in v_mfma_i32_32x32x32_i8 products whose
 // i32 sums are exact (|c q| <= 128 per sample: n < 2^31 / 254 is required).  Per (row, column) the epilogue combines the planes as
 // 64-bit INTEGERS,  N_c = ((a1 128 + a2) 128 + a3) 128 + a4  and N_e likewise, takes a flipped row as 2 (colsum - N_e) - N_c
 // (colsum = the integer column sum of the planes over the samples) and writes
@@ -27,40 +27,17 @@
 // [column][128 B] with the 16-byte chunk index XOR (column >> 1) & 7.  No atomics: one workgroup owns a (row tile, column tile).
 #include <cmath>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 #include "lm_pvalue.h"
 
 namespace jx {
-
-typedef int lt_i32x4 __attribute__((ext_vector_type(4)));
-typedef int lt_i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int LT_PLANES = 4;
 constexpr int LT_TM = 128;                       // rows per workgroup (32 per wave)
 constexpr int LT_TN = 32;                        // columns per workgroup
 constexpr int LT_PLANE_LDS = LT_TN * 128;        // one plane of a 128-sample step
 constexpr int LT_STAGE = LT_PLANES * LT_PLANE_LDS;
-
-// 16 two-bit codes -> 16 count bytes / 16 missing-call indicator bytes, byte 4 q + b = sample 4 b + q (k_rotate_i8.hip)
-__device__ __forceinline__ lt_i32x4 lt_decode_count(uint32_t w) {
-    const uint32_t hi = (w >> 1) & 0x55555555u;
-    const uint32_t v = hi + (hi & w);
-    lt_i32x4 o;
-    o.x = (int)(v & 0x03030303u);
-    o.y = (int)((v >> 2) & 0x03030303u);
-    o.z = (int)((v >> 4) & 0x03030303u);
-    o.w = (int)((v >> 6) & 0x03030303u);
-    return o;
-}
-__device__ __forceinline__ lt_i32x4 lt_decode_missing(uint32_t w) {
-    const uint32_t v = w & ~(w >> 1) & 0x55555555u;
-    lt_i32x4 o;
-    o.x = (int)(v & 0x03030303u);
-    o.y = (int)((v >> 2) & 0x03030303u);
-    o.z = (int)((v >> 4) & 0x03030303u);
-    o.w = (int)((v >> 6) & 0x03030303u);
-    return o;
-}
 
 // ---- operand preparation ----------------------------------------------------------------------------------------------------
 // b: column c at b + c ldb (n contiguous f64).  sexp[c] = e with S = 2^e the smallest power of two >= max |b_c| (0 for a zero or
@@ -167,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void lt_sums_kernel(const uint8_t *__restri
     const int64_t bplane = (int64_t)cpad * npad;
     const int bdst = bcol * 128 + ((bchunk ^ ((bcol >> 1) & 7)) << 4);
 
-    lt_i32x16 accc[LT_PLANES], acce[LT_PLANES];
+    i32x16 accc[LT_PLANES], acce[LT_PLANES];
 #pragma unroll
     for (int pl = 0; pl < LT_PLANES; ++pl)
 #pragma unroll
@@ -202,11 +179,11 @@ __global__ __launch_bounds__(256, 2) void lt_sums_kernel(const uint8_t *__restri
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const uint32_t w = ks == 0 ? acur.x : ks == 1 ? acur.y : ks == 2 ? acur.z : acur.w;
-            const lt_i32x4 ac = lt_decode_count(w), ae = lt_decode_missing(w);
+            const i32x4 ac = (i32x4)counts16(w), ae = (i32x4)missing16(w);
             const int boff = frow * 128 + (((4 * h + ks) ^ fx) << 4);
 #pragma unroll
             for (int pl = 0; pl < LT_PLANES; ++pl) {
-                const lt_i32x4 b = *reinterpret_cast<const lt_i32x4 *>(st + pl * LT_PLANE_LDS + boff);
+                const i32x4 b = *reinterpret_cast<const i32x4 *>(st + pl * LT_PLANE_LDS + boff);
                 accc[pl] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ac, b, accc[pl], 0, 0, 0);
                 acce[pl] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ae, b, acce[pl], 0, 0, 0);
             }
@@ -224,14 +201,14 @@ __global__ __launch_bounds__(256, 2) void lt_sums_kernel(const uint8_t *__restri
 #undef LT_LOAD_B
     static_assert(LT_PLANES == 4, "the plane registers of the product kernel are written out for four planes");
 
-    // C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h
+    // the accumulators hold (cd_row, cd_col) of the 32 x 32 shapes
     const int gj = j0 + frow;
     if (gj >= ncols) return;
     const double s = scale[gj];
     const long long cs = colsum[gj];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int gr = r0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int gr = cd_row(r, h, r0);
         if (gr >= nrows) continue;
         long long nc = 0, ne = 0;
 #pragma unroll
@@ -293,22 +270,12 @@ __global__ __launch_bounds__(256) void lt_stats_kernel(const double *__restrict_
     }
     if (counter) {
         const bool hit = live && p <= pmax;
-        const int lane = threadIdx.x & 63;
-        const unsigned long long bal = __ballot(hit);
-        if (bal) {                                              // wave-uniform
-            const int leader = __ffsll((long long)bal) - 1;
-            unsigned long long base = 0ull;
-            if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(bal));
-            base = ((unsigned long long)(uint32_t)__shfl((int)(base >> 32), leader, 64) << 32) |
-                   (unsigned long long)(uint32_t)__shfl((int)(base & 0xffffffffull), leader, 64);
-            const unsigned long long slot = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
-            if (hit && slot < cap) {
-                hit_trait[slot] = trait0 + t;
-                hit_row[slot] = row0 + r;
-                double *o = hit_vals + slot * 4;
-                o[0] = beta, o[1] = se, o[2] = chisq, o[3] = p;
-            }
-        }
+        wave_append(hit, counter, cap, [=](unsigned long long slot) {
+            hit_trait[slot] = trait0 + t;
+            hit_row[slot] = row0 + r;
+            double *o = hit_vals + slot * 4;
+            o[0] = beta, o[1] = se, o[2] = chisq, o[3] = p;
+        });
     }
 }
 

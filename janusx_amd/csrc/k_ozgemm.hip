@@ -27,12 +27,10 @@
 // The MFMA A operand is the N-side image, so an accumulator's lane index is the memory-contiguous row index of C.
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "k_ozgemm.h"
 
 namespace jx {
-
-typedef int oz_i32x4 __attribute__((ext_vector_type(4)));
-typedef int oz_i32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int OZ_TM = 128;                    // rows per image block = tile edge
 constexpr int OZ_BK = 32;                     // k per step
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(512, 2) void oz_mm_kernel(OzArgs g) {
         oz_glds(src, lds0 + buf * STAGE + piece * 1024);
     };
 
-    oz_i32x16 acc[P][2];
+    i32x16 acc[P][2];
 #pragma unroll
     for (int l = 0; l < P; ++l)
 #pragma unroll
@@ -258,14 +256,14 @@ __global__ __launch_bounds__(512, 2) void oz_mm_kernel(OzArgs g) {
         const int nbuf = buf >= 1 ? buf - 1 : OZ_NST - 1;          // (t + 2) % 3
         const uint8_t *sa = oz_smem + buf * STAGE;
         const uint8_t *sb = sa + P * OZ_PLANE;
-        oz_i32x4 bn[P];
+        i32x4 bn[P];
 #pragma unroll
-        for (int j = 0; j < P; ++j) bn[j] = *reinterpret_cast<const oz_i32x4 *>(sb + j * OZ_PLANE + (wn * 32) * 32 + frag);
+        for (int j = 0; j < P; ++j) bn[j] = *reinterpret_cast<const i32x4 *>(sb + j * OZ_PLANE + (wn * 32) * 32 + frag);
         // M-side fragments of plane i + 1 are read while plane i is multiplied
-        oz_i32x4 am[2][2];
+        i32x4 am[2][2];
 #pragma unroll
         for (int bj = 0; bj < 2; ++bj)
-            am[0][bj] = *reinterpret_cast<const oz_i32x4 *>(sa + (wm * 64 + bj * 32) * 32 + frag);
+            am[0][bj] = *reinterpret_cast<const i32x4 *>(sa + (wm * 64 + bj * 32) * 32 + frag);
         int q = 0;
 #pragma unroll
         for (int i = 0; i < P; ++i) {
@@ -273,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void oz_mm_kernel(OzArgs g) {
 #pragma unroll
                 for (int bj = 0; bj < 2; ++bj)
                     am[(i + 1) & 1][bj] =
-                        *reinterpret_cast<const oz_i32x4 *>(sa + (i + 1) * OZ_PLANE + (wm * 64 + bj * 32) * 32 + frag);
+                        *reinterpret_cast<const i32x4 *>(sa + (i + 1) * OZ_PLANE + (wm * 64 + bj * 32) * 32 + frag);
             }
 #pragma unroll
             for (int j = 0; j < P - i; ++j) {
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(512, 2) void oz_mm_kernel(OzArgs g) {
         sam *= W0 * g.alpha;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int gn = n0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int gn = cd_row(r, h, n0);
             if (mok && gn < g.n) {
                 double sbn = g.sb[gn];
                 if (sbn == 0.0) sbn = 1.0;

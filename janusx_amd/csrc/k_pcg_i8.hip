@@ -23,11 +23,10 @@
 // 8-byte load); byte 4 q + b of a decoded dword is element 4 b + q, and the digit images are stored in that order.
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
-
-typedef int pi_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PI_STAGE = 8;          // records (128 elements of K) per LDS stage of the digit image
 constexpr int PI_WAVES = 8;          // waves per workgroup, 16 units each
@@ -49,21 +48,7 @@ __device__ __forceinline__ void pi_digits(double x, double inv, int q[4]) {
     }
 }
 
-// three bit planes of 16 two-bit codes as MFMA operand bytes (byte 4 q + b = element 4 b + q; 0 / 1)
-__device__ __forceinline__ void pi_planes(uint32_t w, pi_i32x4 &lo, pi_i32x4 &hi, pi_i32x4 &both) {
-    const uint32_t l = w & 0x55555555u, h = (w >> 1) & 0x55555555u;
-    lo.x = (int)(l & 0x01010101u);
-    lo.y = (int)((l >> 2) & 0x01010101u);
-    lo.z = (int)((l >> 4) & 0x01010101u);
-    lo.w = (int)((l >> 6) & 0x01010101u);
-    hi.x = (int)(h & 0x01010101u);
-    hi.y = (int)((h >> 2) & 0x01010101u);
-    hi.z = (int)((h >> 4) & 0x01010101u);
-    hi.w = (int)((h >> 6) & 0x01010101u);
-    both = lo & hi;
-}
-
-__device__ __forceinline__ double pi_combine(const pi_i32x4 a) {
+__device__ __forceinline__ double pi_combine(const i32x4 a) {
     constexpr double W1 = 1.0 / 127.0, R = 1.0 / 254.0;
     return (((double)a.w * R + (double)a.z) * R + (double)a.y) * R * W1 + (double)a.x * W1;
 }
@@ -131,7 +116,7 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pi_tdot_kernel(const uint8_t *_
     const int64_t rec = (r < nrows) ? (rows ? (int64_t)rows[r] : (int64_t)r) : 0;
     const uint8_t *gsrc = p32 + rec * 32 + 8 * kq;
     const int64_t tstride = m_total * 32;
-    pi_i32x4 acc_lo = {0, 0, 0, 0}, acc_hi = {0, 0, 0, 0}, acc_b = {0, 0, 0, 0};
+    i32x4 acc_lo = {0, 0, 0, 0}, acc_hi = {0, 0, 0, 0}, acc_b = {0, 0, 0, 0};
     const int nstage = (ntiles + PI_STAGE - 1) / PI_STAGE;
     auto stage_load = [&](int sg, int buf) {
         // 512 threads x 8 B = one stage of the digit image (tiles past the end: zeros)
@@ -154,17 +139,17 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pi_tdot_kernel(const uint8_t *_
         }
 #pragma unroll
         for (int j = 0; j < PI_STAGE; ++j) {
-            pi_i32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+            i32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
             if (s < 4) {
-                a0 = *reinterpret_cast<const pi_i32x4 *>(&a_sh[buf][((j * 8 + kq) * 4 + s) * 16]);
-                a1 = *reinterpret_cast<const pi_i32x4 *>(&a_sh[buf][((j * 8 + 4 + kq) * 4 + s) * 16]);
+                a0 = *reinterpret_cast<const i32x4 *>(&a_sh[buf][((j * 8 + kq) * 4 + s) * 16]);
+                a1 = *reinterpret_cast<const i32x4 *>(&a_sh[buf][((j * 8 + 4 + kq) * 4 + s) * 16]);
             }
-            pi_i32x4 lo, hi, bo;
-            pi_planes(g[j].x, lo, hi, bo);
+            i32x4 lo, hi, bo;
+            planes16(g[j].x, lo, hi, bo);
             acc_lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, lo, acc_lo, 0, 0, 0);
             acc_hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, hi, acc_hi, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, bo, acc_b, 0, 0, 0);
-            pi_planes(g[j].y, lo, hi, bo);
+            planes16(g[j].y, lo, hi, bo);
             acc_lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, lo, acc_lo, 0, 0, 0);
             acc_hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, hi, acc_hi, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, bo, acc_b, 0, 0, 0);
@@ -256,7 +241,7 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pi_dot_kernel(const uint8_t *__
     const int st1 = (st0 + tiles_per_slice < nst) ? st0 + tiles_per_slice : nst;
     const uint8_t *gsrc = t32 + (int64_t)(i < n ? i : 0) * 32 + 8 * kq;
     const int64_t tstride = (int64_t)n * 32;
-    pi_i32x4 acc_lo = {0, 0, 0, 0}, acc_hi = {0, 0, 0, 0}, acc_b = {0, 0, 0, 0};
+    i32x4 acc_lo = {0, 0, 0, 0}, acc_hi = {0, 0, 0, 0}, acc_b = {0, 0, 0, 0};
     const int ntl = st1 - st0;
     const int nstage = (ntl + PI_STAGE - 1) / PI_STAGE;
     auto stage_load = [&](int sg, int buf) {
@@ -285,17 +270,17 @@ __global__ __launch_bounds__(PI_WAVES * 64) void pi_dot_kernel(const uint8_t *__
         }
 #pragma unroll
         for (int j = 0; j < PI_STAGE; ++j) {
-            pi_i32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+            i32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
             if (s < 12) {
-                a0 = *reinterpret_cast<const pi_i32x4 *>(&a_sh[buf][((j * 8 + kq) * 12 + s) * 16]);
-                a1 = *reinterpret_cast<const pi_i32x4 *>(&a_sh[buf][((j * 8 + 4 + kq) * 12 + s) * 16]);
+                a0 = *reinterpret_cast<const i32x4 *>(&a_sh[buf][((j * 8 + kq) * 12 + s) * 16]);
+                a1 = *reinterpret_cast<const i32x4 *>(&a_sh[buf][((j * 8 + 4 + kq) * 12 + s) * 16]);
             }
-            pi_i32x4 lo, hi, bo;
-            pi_planes(g[j].x, lo, hi, bo);
+            i32x4 lo, hi, bo;
+            planes16(g[j].x, lo, hi, bo);
             acc_lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, lo, acc_lo, 0, 0, 0);
             acc_hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, hi, acc_hi, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, bo, acc_b, 0, 0, 0);
-            pi_planes(g[j].y, lo, hi, bo);
+            planes16(g[j].y, lo, hi, bo);
             acc_lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, lo, acc_lo, 0, 0, 0);
             acc_hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, hi, acc_hi, 0, 0, 0);
             acc_b = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, bo, acc_b, 0, 0, 0);

@@ -13,23 +13,20 @@
 // epilogue.  Measured on a family-structured panel (n = 3000) the quantisation error of the rotated values is 1.6e-8 of their
 // range at most (fp16 hi/lo split: 1.0e-7; the f32 SGEMM of the reference: 1.8e-6).  Three int8 products cost 0.75 of the two
 // fp16 products of the exact-row form of rotate256_kernel, the operand images are bytes (A: 1 B instead of 2 B per element,
-// B: 3 B instead of 4 B), and the design decode is pure VALU (no LUT, no selector table: k_grm_i8.hip).
+// B: 3 B instead of 4 B), and the design decode is pure VALU (no LUT, no selector table: `counts16` of i8_tile.h).
 //
 // Shape: 512 threads = 8 waves (2 x 4) on 256 SNP rows x 128 eigenvector columns, 128 x 32 per wave (3 planes x 4 tiles of
 // 32 x 32 i32 accumulators = 192 registers); images [row][64 k] bytes with the 16-byte chunk index XOR-swizzled by
 // (row >> 2) & 3, double buffered, one barrier per 64-sample step; the k order inside a 16-sample group is the decode's
-// (byte 4 q + b = sample 4 b + q) and the planes are stored in that order.  The exact rows of a block are passed as a compacted
+// (i8_tile.h: byte 4 q + b = sample 4 b + q) and the planes are stored in that order.  The exact rows of a block are passed as a compacted
 // list of positions (`sel`), the other rows go to the fp16 kernel the same way: a row takes the same path, and gets the same
 // bits, whatever rows surround it (chunked scans equal unchunked ones, the reference's smoke invariant).
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4q __attribute__((ext_vector_type(4)));
 
 constexpr int RI_TM = 256;                // SNP rows per workgroup
 constexpr int RI_TN = 128;                // eigenvector columns per workgroup
@@ -39,29 +36,6 @@ constexpr int RI_IMG_B = RI_TN * RI_BK;   // one plane
 constexpr int RI_SET = RI_IMG_A + 3 * RI_IMG_B;
 
 __device__ __forceinline__ int ri_chunk_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-// 16 two-bit codes -> 16 count bytes, byte 4 q + b = sample 4 b + q (same as k_grm_i8.hip)
-__device__ __forceinline__ u32x4q ri_decode16(uint32_t w) {
-    const uint32_t hi = (w >> 1) & 0x55555555u;
-    const uint32_t v = hi + (hi & w);
-    u32x4q o;
-    o.x = v & 0x03030303u;
-    o.y = (v >> 2) & 0x03030303u;
-    o.z = (v >> 4) & 0x03030303u;
-    o.w = (v >> 6) & 0x03030303u;
-    return o;
-}
-
-// 16 two-bit codes -> 16 bytes that are 1 at a missing call (code 01) and 0 elsewhere, same byte order
-__device__ __forceinline__ u32x4q ri_decode16_missing(uint32_t w) {
-    const uint32_t v = w & ~(w >> 1) & 0x55555555u;
-    u32x4q o;
-    o.x = v & 0x03030303u;
-    o.y = (v >> 2) & 0x03030303u;
-    o.z = (v >> 4) & 0x03030303u;
-    o.w = (v >> 6) & 0x03030303u;
-    return o;
-}
 
 // ---- quantisation of U^T (n x n f32, row j = eigenvector j) into three int8 planes (npad x npad each) ---------------------
 __global__ __launch_bounds__(256) void ut_rowmax_kernel(const float *__restrict__ ut, int n, int npad, float *__restrict__ umax) {
@@ -181,23 +155,23 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_kernel(const uint8_t *__rest
     const int boff_lds = ri_chunk_off(brow, bpart);
 
     uint2 wa = make_uint2(0, 0);
-    u32x4q b0, b1, b2;
+    u32x4v b0, b1, b2;
     auto load_a = [&](int kstep) {        // samples 64 kstep .. + 63: 16 payload bytes of the row, 8 per thread
         const int tile = kstep >> 1, sub = kstep & 1;
         wa = *reinterpret_cast<const uint2 *>(arec + (int64_t)tile * m_total * 32 + sub * 16);
     };
     auto load_b = [&](int64_t kcol) {
-        b0 = *reinterpret_cast<const u32x4q *>(bsrc + kcol);
-        b1 = *reinterpret_cast<const u32x4q *>(bsrc + plane + kcol);
-        b2 = *reinterpret_cast<const u32x4q *>(bsrc + 2 * plane + kcol);
+        b0 = *reinterpret_cast<const u32x4v *>(bsrc + kcol);
+        b1 = *reinterpret_cast<const u32x4v *>(bsrc + plane + kcol);
+        b2 = *reinterpret_cast<const u32x4v *>(bsrc + 2 * plane + kcol);
     };
     auto stage = [&](uint8_t *set) {
-        *reinterpret_cast<u32x4q *>(set + ri_chunk_off(arow, 2 * ahalf)) = MODE == 1 ? ri_decode16_missing(wa.x) : ri_decode16(wa.x);
-        *reinterpret_cast<u32x4q *>(set + ri_chunk_off(arow, 2 * ahalf + 1)) = MODE == 1 ? ri_decode16_missing(wa.y) : ri_decode16(wa.y);
-        const u32x4q mk = {bmask, bmask, bmask, bmask};
-        *reinterpret_cast<u32x4q *>(set + RI_IMG_A + boff_lds) = b0 & mk;
-        *reinterpret_cast<u32x4q *>(set + RI_IMG_A + RI_IMG_B + boff_lds) = b1 & mk;
-        *reinterpret_cast<u32x4q *>(set + RI_IMG_A + 2 * RI_IMG_B + boff_lds) = b2 & mk;
+        *reinterpret_cast<u32x4v *>(set + ri_chunk_off(arow, 2 * ahalf)) = MODE == 1 ? missing16(wa.x) : counts16(wa.x);
+        *reinterpret_cast<u32x4v *>(set + ri_chunk_off(arow, 2 * ahalf + 1)) = MODE == 1 ? missing16(wa.y) : counts16(wa.y);
+        const u32x4v mk = {bmask, bmask, bmask, bmask};
+        *reinterpret_cast<u32x4v *>(set + RI_IMG_A + boff_lds) = b0 & mk;
+        *reinterpret_cast<u32x4v *>(set + RI_IMG_A + RI_IMG_B + boff_lds) = b1 & mk;
+        *reinterpret_cast<u32x4v *>(set + RI_IMG_A + 2 * RI_IMG_B + boff_lds) = b2 & mk;
     };
 
     i32x16 acc[3][4];
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_kernel(const uint8_t *__rest
         cur ^= 1;
     }
 
-    // epilogue: planes combined in f64; C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h
+    // epilogue: planes combined in f64; the accumulators hold (cd_row, cd_col) of the 32 x 32 shapes
     const int gj = j0 + wn * 32 + frow;
     const bool colok = gj < n;
     const double um = colok ? (double)umax[gj] : 0.0;
@@ -265,7 +239,7 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_kernel(const uint8_t *__rest
     for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int lr = wm * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int lr = cd_row(r, h, wm * 128 + mi * 32);
             const int gr = sPos[lr];
             if (gr >= 0 && colok) {
                 const double v = (double)acc[0][mi][r] * w1 + (double)acc[1][mi][r] * w2 + (double)acc[2][mi][r] * w3;
@@ -309,16 +283,8 @@ __device__ __forceinline__ void rd_glds(const void *base, uint32_t off, unsigned
                  : "memory");
 }
 
-// 16 two-bit codes -> the MFMA operand of one k slot (same byte order as ri_decode16)
-template <int MODE> __device__ __forceinline__ i32x4 rd_decode(uint32_t w) {
-    const u32x4q o = MODE == 1 ? ri_decode16_missing(w) : ri_decode16(w);
-    i32x4 r;
-    r.x = (int)o.x;
-    r.y = (int)o.y;
-    r.z = (int)o.z;
-    r.w = (int)o.w;
-    return r;
-}
+// 16 two-bit codes -> the MFMA operand of one k slot: the counts, or (MODE 1) the missing-call indicator
+template <int MODE> __device__ __forceinline__ i32x4 rd_decode(uint32_t w) { return (i32x4)(MODE == 1 ? missing16(w) : counts16(w)); }
 
 // the per-element epilogue of both MFMA shapes: planes combined in f64 in this order, then the row's offset / sign
 template <int MODE>
@@ -469,7 +435,7 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // no DMA may outlive the workgroup's LDS allocation
 
-        // C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 h
+        // the accumulators hold (cd_row, cd_col) of the 32 x 32 shapes
         const int gj = j0 + wn * 32 + frow;
         const bool colok = gj < n;
         const double um = colok ? (double)umax[gj] : 0.0;
@@ -479,7 +445,7 @@ __global__ __launch_bounds__(512, 2) void rotate_i8_dma_kernel(const uint8_t *__
         for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int lr = wm * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int lr = cd_row(r, h, wm * 128 + mi * 32);
                 const int gr = sPos[lr];
                 if (gr >= 0 && colok)
                     rd_store<MODE>(out + (int64_t)gr * ldo + gj, acc[0][mi][r], acc[1][mi][r], acc[2][mi][r], w1, w2, w3, us, sOff[lr],

@@ -19,11 +19,10 @@
 // the same bits.  Up to 32 columns are one pass over the payload (8 A tiles); more columns loop over passes of 32.
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
-
-typedef int rs_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RS_WAVES = 8;          // waves per workgroup
 constexpr int RS_U = 2;              // units of 16 SNPs (samples) per wave
@@ -42,22 +41,7 @@ __device__ __forceinline__ void rs_digits(double x, double inv, int q[4]) {
     }
 }
 
-// dose and missing planes of 16 two-bit codes as MFMA operand bytes (byte 4 q + b = element 4 b + q), as pi_planes
-__device__ __forceinline__ void rs_planes(uint32_t w, rs_i32x4 &dose, rs_i32x4 &miss) {
-    const uint32_t l = w & 0x55555555u, h = (w >> 1) & 0x55555555u;
-    const uint32_t d = h + (l & h);              // 0, 1, 2 per 2-bit field: no carry into the next field
-    const uint32_t mi = l & ~h;
-    dose.x = (int)(d & 0x03030303u);
-    dose.y = (int)((d >> 2) & 0x03030303u);
-    dose.z = (int)((d >> 4) & 0x03030303u);
-    dose.w = (int)((d >> 6) & 0x03030303u);
-    miss.x = (int)(mi & 0x01010101u);
-    miss.y = (int)((mi >> 2) & 0x01010101u);
-    miss.z = (int)((mi >> 4) & 0x01010101u);
-    miss.w = (int)((mi >> 6) & 0x01010101u);
-}
-
-__device__ __forceinline__ double rs_combine(const rs_i32x4 a) {
+__device__ __forceinline__ double rs_combine(const i32x4 a) {
     constexpr double W1 = 1.0 / 127.0, R = 1.0 / 254.0;
     return (((double)a.w * R + (double)a.z) * R + (double)a.y) * R * W1 + (double)a.x * W1;
 }
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256) void rs_quant_kernel(const double *__restrict_
 template <int NT, int NV>
 __device__ __forceinline__ void rs_main(const uint8_t *__restrict__ src, int64_t tstride, const int32_t *__restrict__ rows, int nout,
                                         int t_lo, int t_hi, const int8_t *__restrict__ img, int8_t *a_sh, int o0,
-                                        rs_i32x4 (&acc_g)[RS_U][NT], rs_i32x4 (&acc_m)[RS_U][NT]) {
+                                        i32x4 (&acc_g)[RS_U][NT], i32x4 (&acc_m)[RS_U][NT]) {
     constexpr int R = 16 * NT * NV;                          // A rows of one slot
     constexpr int TB = 8 * R * 16;                           // image bytes per record tile
     constexpr int ST = (256 / R) > 8 ? 8 : ((256 / R) < 1 ? 1 : 256 / R);   // tiles per LDS stage (32 KB at most)
@@ -162,7 +146,7 @@ __device__ __forceinline__ void rs_main(const uint8_t *__restrict__ src, int64_t
 #pragma unroll
     for (int u = 0; u < RS_U; ++u)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acc_g[u][t] = acc_m[u][t] = rs_i32x4{0, 0, 0, 0};
+        for (int t = 0; t < NT; ++t) acc_g[u][t] = acc_m[u][t] = i32x4{0, 0, 0, 0};
     const int ntl = t_hi - t_lo;
     if (ntl <= 0) return;
     const int nstage = (ntl + ST - 1) / ST;
@@ -195,14 +179,14 @@ __device__ __forceinline__ void rs_main(const uint8_t *__restrict__ src, int64_t
         for (int j = 0; j < ST; ++j) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                rs_i32x4 dose[RS_U], miss[RS_U];
+                i32x4 dose[RS_U], miss[RS_U];
 #pragma unroll
-                for (int u = 0; u < RS_U; ++u) rs_planes(h ? g[j][u].y : g[j][u].x, dose[u], miss[u]);
+                for (int u = 0; u < RS_U; ++u) counts_missing16(h ? g[j][u].y : g[j][u].x, dose[u], miss[u]);
                 const int8_t *arow = ab + (int64_t)j * TB + ((h * 4 + kq) * R + s) * 16;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
-                    const rs_i32x4 a_g = *reinterpret_cast<const rs_i32x4 *>(arow + t * 256);
-                    const rs_i32x4 a_m = *reinterpret_cast<const rs_i32x4 *>(arow + ((NV - 1) * NT + t) * 256);
+                    const i32x4 a_g = *reinterpret_cast<const i32x4 *>(arow + t * 256);
+                    const i32x4 a_m = *reinterpret_cast<const i32x4 *>(arow + ((NV - 1) * NT + t) * 256);
 #pragma unroll
                     for (int u = 0; u < RS_U; ++u) {
                         acc_g[u][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_g, dose[u], acc_g[u][t], 0, 0, 0);
@@ -229,7 +213,7 @@ __global__ __launch_bounds__(RS_WAVES * 64) void rs_mm_kernel(const uint8_t *__r
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, s = lane & 15, kq = lane >> 4;
     const int o0 = (blockIdx.x * RS_WAVES + wave) * 16 * RS_U;
     const int cb = blockIdx.y;
-    rs_i32x4 acc_g[RS_U][NT], acc_m[RS_U][NT];
+    i32x4 acc_g[RS_U][NT], acc_m[RS_U][NT];
     rs_main<NT, 1>(p32, m_total * 32, rows, nrows, 0, ntiles, img + (int64_t)cb * ntiles * (8 * 16 * NT * 16), a_sh, o0, acc_g, acc_m);
     // D rows 4 kq + digit of column s: lane (s, kq) holds the four digit sums of column 4 t + kq of the pass for output o0 + 16 u + s
 #pragma unroll
@@ -260,7 +244,7 @@ __global__ __launch_bounds__(RS_WAVES * 64) void rs_tmm_kernel(const uint8_t *__
     const int cb = blockIdx.z;
     const int st0 = blockIdx.y * tiles_per_slice;
     const int st1 = (st0 + tiles_per_slice < nst) ? st0 + tiles_per_slice : nst;
-    rs_i32x4 acc_g[RS_U][NT], acc_m[RS_U][NT];
+    i32x4 acc_g[RS_U][NT], acc_m[RS_U][NT];
     rs_main<NT, 2>(t32, (int64_t)n * 32, nullptr, n, st0, st1, img + (int64_t)cb * nst * (8 * 32 * NT * 16), a_sh, o0, acc_g, acc_m);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {

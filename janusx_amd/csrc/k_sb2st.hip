@@ -19,6 +19,7 @@
 // The reflectors are kept for the back-transformation (k_sbback.hip): v2[row + s n] (entry 1 explicit), tau2[s KS + k].
 #include <stdlib.h>
 
+#include "i8_tile.h"
 #include "jx_common.h"
 
 namespace jx {
@@ -92,7 +93,6 @@ __device__ __forceinline__ void bc_house_wave(double x, int lane, int len, doubl
     v = (lane == 0) ? 1.0 : ((lane < len) ? x * sc : 0.0);
 }
 
-typedef int bc_v4i __attribute__((ext_vector_type(4)));
 constexpr int BC_NV = BC_SB * BC_LD / 2 / BC_THREADS;     // 16-byte pieces of a window per thread (16)
 constexpr int BC_AUX_SC1 = 16;                            // cache-policy bit of the raw buffer builtins: sc1
 
@@ -104,7 +104,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t bc_window_rsrc(double *ab, int
     return __builtin_amdgcn_make_buffer_rsrc(ab + (int64_t)(r < n ? r : 0) * BC_LD, 0, (int)bytes, 0x00020000);
 }
 
-__device__ __forceinline__ void bc_window_load(__amdgpu_buffer_rsrc_t rs, int t, bc_v4i (&x)[BC_NV]) {
+__device__ __forceinline__ void bc_window_load(__amdgpu_buffer_rsrc_t rs, int t, i32x4 (&x)[BC_NV]) {
 #pragma unroll
     for (int u = 0; u < BC_NV; ++u) x[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (u * BC_THREADS + t) * 16, 0, BC_AUX_SC1);
 }
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(BC_THREADS) void sb2st_chase_kernel(BcParams P) {
             if (t == 0) __hip_atomic_store(P.abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
-        bc_v4i x[BC_NV];
+        i32x4 x[BC_NV];
         bc_window_load(bc_window_rsrc(P.ab, n, r), t, x);          // window of step 0
         if (wave == 0) {
             double *col = P.ab + (int64_t)s * BC_LD;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(BC_THREADS) void sb2st_chase_kernel(BcParams P) {
                     const int q = i + d;
                     const double x0 = (i < L && q < nrow) ? E[q][i] : 0.0;
                     const double x1 = (i < L && q + 1 < nrow) ? E[q + 1][i] : 0.0;
-                    bc_v4i o;
+                    i32x4 o;
                     o[0] = __double2loint(x0);
                     o[1] = __double2hiint(x0);
                     o[2] = __double2loint(x1);
@@ -366,14 +366,14 @@ __device__ __forceinline__ unsigned long long bo_pattern(int seq) {
 }
 __device__ __forceinline__ void bo_put(__amdgpu_buffer_rsrc_t rs, int cell, double v, int seq) {
     const unsigned long long bits = (unsigned long long)__double_as_longlong(v), tag = bits ^ bo_pattern(seq);
-    bc_v4i o;
+    i32x4 o;
     o[0] = (int)(unsigned)bits;
     o[1] = (int)(unsigned)(bits >> 32);
     o[2] = (int)(unsigned)tag;
     o[3] = (int)(unsigned)(tag >> 32);
     __builtin_amdgcn_raw_buffer_store_b128(o, rs, cell * 16, 0, BC_AUX_SC1);
 }
-__device__ __forceinline__ bool bo_check(const bc_v4i &x, int seq, double &v) {
+__device__ __forceinline__ bool bo_check(const i32x4 &x, int seq, double &v) {
     const unsigned long long bits = ((unsigned long long)(unsigned)x[1] << 32) | (unsigned)x[0];
     const unsigned long long tag = ((unsigned long long)(unsigned)x[3] << 32) | (unsigned)x[2];
     v = __longlong_as_double((long long)bits);
@@ -445,7 +445,7 @@ __global__ __launch_bounds__(BC_THREADS) __attribute__((amdgpu_waves_per_eu(WPE,
             const __amdgpu_buffer_rsrc_t rr = bo_slot(P.rmsg, k, s & 1), rc = bo_slot(P.cmsg, k, (s - 1) & 1);
             // DEPTH polls in flight: memory is sampled every 1 / DEPTH of a round trip
             struct Raw {
-                bc_v4i a, b, c, d;
+                i32x4 a, b, c, d;
             };
             auto issue = [&](Raw &x) {
                 if (need_r) {

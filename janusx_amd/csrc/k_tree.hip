@@ -5,8 +5,8 @@
 // A. Pair counts (`jxg_tree_counts_p32`).  Of a biallelic site only the two homozygous codes carry a letter (00 the first, 11 the
 //    second; 10 = IUPAC het code and 01 = missing are unknown), so with U = [code is 00 or 11] and W = +1 (00) / -1 (11) / 0
 //        valid = U U^T          S = W W^T = same - differ          mismatch = valid - same = (valid - S) / 2   (exact)
-//    are two int8 Grams over the SNP axis.  The kernel is the counts form of k_king.hip (same [k = SNP][position] code image in LDS,
-//    same position order, transposed fragment reads, pad samples and rows beyond the last SNP masked to 01) with two v_perm_b32 LUTs
+//    are two int8 Grams over the SNP axis.  The kernel reads code images through `PanelReader` of i8_tile.h ([k = SNP][position] code image
+//    in LDS, transposed fragment reads, pad samples and rows beyond the last SNP masked to 01) with two v_perm_b32 LUTs
 //    per side, two v_mfma_i32_32x32x32_i8 passes per k-step and two i32 accumulator sets.  A site whose two letters are equal adds to
 //    `valid` alone, and its het calls carry that letter as well: the caller passes those rows as a second image with `same_base` = 1
 //    (one pass, N N^T with N = [code is not 01]) and `accumulate` = 1.
@@ -32,27 +32,6 @@ constexpr int TREE_WT = 32;                        // samples per wave side
 
 // byte c of a LUT = value of the 2-bit code c (0 = 00 first letter, 1 = 01 missing, 2 = 10 het, 3 = 11 second letter)
 constexpr uint32_t TR_U = 0x01000001u, TR_W = 0xff000001u, TR_CALLED = 0x01010001u;
-constexpr uint32_t TR_MISSING = 0x55555555u;       // 16 codes 01
-
-// 16 two-bit codes -> 16 code bytes: byte 4 q + b = sample 4 b + q of the dword (the order `pos_to_sample` undoes)
-__device__ __forceinline__ u32x4v tr_codes(uint32_t w) {
-    u32x4v o;
-    o.x = w & 0x03030303u;
-    o.y = (w >> 2) & 0x03030303u;
-    o.z = (w >> 4) & 0x03030303u;
-    o.w = (w >> 6) & 0x03030303u;
-    return o;
-}
-
-template <uint32_t LUT>
-__device__ __forceinline__ i32x4 tr_ind(const i32x4 c) {
-    i32x4 o;
-    o.x = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.x);
-    o.y = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.y);
-    o.z = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.z);
-    o.w = (int)__builtin_amdgcn_perm(LUT, LUT, (uint32_t)c.w);
-    return o;
-}
 
 #define TR_MFMA(a, b, c) c = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0)
 
@@ -63,64 +42,39 @@ __global__ __launch_bounds__(256, 2) void tree_counts_kernel(const uint8_t *__re
                                                              int32_t *__restrict__ out_valid, int32_t *__restrict__ out_mismatch) {
     constexpr int BK = TREE_BK, TM = TREE_TM, WT = TREE_WT;
     constexpr int NW = TM / WT;
-    constexpr int NTHREADS = 64 * NW * NW;
-    constexpr int PITCH = TM + 32;                 // bytes per SNP row of an image
-    constexpr int IMG = BK * PITCH;
-    constexpr int DW = TM / 16;                    // payload dwords per SNP row of a panel
-    constexpr int NL = BK * DW / NTHREADS;         // payload dwords per thread, step and panel
-    static_assert(NL * NTHREADS == BK * DW && NL >= 1 && BK % 32 == 0 && 128 % TM == 0 && WT == 32, "panel dwords must divide evenly");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[2 * IMG];
+    static_assert(WT == 32, "one 32 x 32 MFMA tile per wave");
+    using Reader = PanelReader<TM, BK, 64 * NW * NW, P32_ALL_MISSING>;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[Reader::SET];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int wave = threadIdx.x >> 6;
     const int wm = wave / NW, wn = wave % NW;
     const int ti = (int)blockIdx.y, tj = (int)blockIdx.x;
 
-    // decode mapping as in k_king.hip: dword idx = tid + u NTHREADS -> (SNP kk = idx / DW of the step, dword d = idx % DW of the panel
-    // row); dword ti DW + d of the sample axis lies in the 128-sample record (ti DW + d) / 8 at dword (ti DW + d) % 8
-    const int d_of = tid % DW;
-    const int kk_of = tid / DW;
-    constexpr int KSTRIDE = NTHREADS / DW;
-    const int gdA = ti * DW + d_of, gdB = tj * DW + d_of;
-    const int recA = gdA >> 3, recB = gdB >> 3;
-    // loads go to clamped (always valid) addresses; rows beyond m and records beyond the panel become all-missing words
-    const bool inA = recA < nt128, inB = recB < nt128;
-    const uint8_t *const baseA = p32 + (int64_t)(inA ? recA : nt128 - 1) * m * 32 + 4 * (gdA & 7);
-    const uint8_t *const baseB = p32 + (int64_t)(inB ? recB : nt128 - 1) * m * 32 + 4 * (gdB & 7);
-
+    const Reader rd(p32, m, nt128, ti, tj);
+    constexpr int NL = Reader::NL, PITCH = Reader::PITCH, IMG = Reader::IMG;
     uint32_t wA[NL], wB[NL];                       // payload dwords, loaded one step ahead of their use
-    auto load_payload = [&](int u, int64_t kbase) {
-        const int64_t k = kbase + kk_of + u * KSTRIDE;
-        const int64_t kc = k < m ? k : m - 1;
-        wA[u] = *reinterpret_cast<const uint32_t *>(baseA + kc * 32);
-        wB[u] = *reinterpret_cast<const uint32_t *>(baseB + kc * 32);
-    };
-    auto store_codes = [&](int u, int64_t kbase) {
-        const bool valid = kbase + kk_of + u * KSTRIDE < m;
-        const int o = (kk_of + u * KSTRIDE) * PITCH + d_of * 16;
-        *reinterpret_cast<u32x4v *>(smem + o) = tr_codes(valid && inA ? wA[u] : TR_MISSING);
-        *reinterpret_cast<u32x4v *>(smem + IMG + o) = tr_codes(valid && inB ? wB[u] : TR_MISSING);
-    };
+    auto load_payload = [&](int u, int64_t kbase) { rd.load(rd.row(u, kbase, m), wA[u], wB[u]); };
+    auto store_codes = [&](int u, int64_t kbase) { rd.store(smem, u, kbase, m, wA[u], wB[u], [](uint32_t w) { return codes16(w); }); };
 
     i32x16 cv, cs;                                 // valid, S
 #pragma unroll
     for (int r = 0; r < 16; ++r) cv[r] = 0, cs[r] = 0;
 
-    const int h = lane >> 5;
-    const int lane_off = (16 * h + ((lane & 15) >> 1)) * PITCH + 16 * ((lane >> 4) & 1) + 8 * (lane & 1);
+    const int lane_off = frag_lane_off<PITCH>(lane, h);
     auto mfma_ks = [&](int ks) {
         const i32x4 ca = tr8_frag<PITCH>(smem + lane_off + wm * WT + ks * 32 * PITCH);
         const i32x4 cb = tr8_frag<PITCH>(smem + IMG + lane_off + wn * WT + ks * 32 * PITCH);
         // equal letters: the het code of the site is that letter too (`het_iupac`, :310-313), every called sample is known
-        const i32x4 ua = tr_ind<SAME ? TR_CALLED : TR_U>(ca), ub = tr_ind<SAME ? TR_CALLED : TR_U>(cb);
+        const i32x4 ua = lut_frag<SAME ? TR_CALLED : TR_U>(ca), ub = lut_frag<SAME ? TR_CALLED : TR_U>(cb);
         TR_MFMA(ua, ub, cv);
         if constexpr (!SAME) {
-            const i32x4 wa = tr_ind<TR_W>(ca), wb = tr_ind<TR_W>(cb);
+            const i32x4 wa = lut_frag<TR_W>(ca), wb = lut_frag<TR_W>(cb);
             TR_MFMA(wa, wb, cs);
         }
     };
 
+    // single buffered, payload loaded one step ahead of its store: the other workgroup of the CU covers the stores and barriers
 #pragma unroll
     for (int u = 0; u < NL; ++u) load_payload(u, 0);
     for (int64_t kbase = 0; kbase < m; kbase += BK) {
@@ -134,11 +88,11 @@ __global__ __launch_bounds__(256, 2) void tree_counts_kernel(const uint8_t *__re
         __syncthreads();
     }
 
-    // C/D layout of the 32 x 32 shapes: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): tile POSITIONS
-    const int64_t gj = (int64_t)tj * TM + pos_to_sample(wn * WT + (lane & 31));
+    // the accumulators hold tile POSITIONS (cd_row, cd_col)
+    const int64_t gj = (int64_t)tj * TM + pos_to_sample(wn * WT + cd_col(lane));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t gi = (int64_t)ti * TM + pos_to_sample(wm * WT + (r & 3) + 8 * (r >> 2) + 4 * h);
+        const int64_t gi = (int64_t)ti * TM + pos_to_sample(cd_row(r, h, wm * WT));
         if (gi < n && gj < n) {
             const int64_t o = gi * n + gj;
             const int v = cv[r];
