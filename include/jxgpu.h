@@ -980,6 +980,35 @@ int jxg_farmcpu_fem_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq
 int jxg_farmcpu_final_stats(const double *d_qg, const double *d_qg_lo, int64_t ldq, int rank, const double *d_gy, int64_t ldg,
                             const double *d_ss, int nrows, double bg_rss, int df, double *d_out, void *stream);
 
+/* ---- Exhaustive SNP-pair screen on the int8 pipes (`jx fvlmm2 -screen`; csrc/k_pairscreen.hip; an extension).  Classes of a 2-bit
+ * code: 00 -> 0, 10 -> 1, 11 -> 2; code 01 (missing, pad) belongs to none.  The table of a pair runs over the samples called at both
+ * SNPs: N_ab = number of samples of class a at the first and b at the second SNP, R_ab = the sum of r over them as the 64-bit
+ * integer ((A1 128 + A2) 128 + A3) 128 + A4 of the digit-plane sums; the real sum is R_ab * scale.  d_planes: plane 0 of the one
+ * column r of a jxg_lmt_prepare image (plane p at d_planes + p plane_stride, plane_stride = cpad * npad; scale = d_scale[0]).
+ * n <= 2^24.
+ *   jxg_pairscreen_max_variants : 16.
+ *   jxg_pairscreen_tables_p32   : d_n (ni, nj, 3, 3) int32 and d_r (ni, nj, 3, 3) int64 of the pairs (d_rows_i[x], d_rows_j[y]),
+ *                                 records of the image, lists of any length.
+ *   jxg_pairscreen_scan_p32     : every pair i < j of the positions of d_rows (nrows records; NULL: the first nrows) against
+ *                                 every variant v < nvariants <= 16.  d_variants (nvariants, 15) f64 = C_v[a][b] (9), L1_v[a] (3),
+ *                                 L2_v[b] (3) by class; d_flip (nrows) uint8: a flipped row reads its tables at class 2 - a.  The
+ *                                 statistic T = num^2 / (sigma2 den) is the score test of the combo term given the intercept and
+ *                                 both literals in the linear model of r on the pair's complete samples (moments in f64, a major, b
+ *                                 minor; the 3 x 3 solve by fraction-free elimination, csrc/k_pairscreen.hip).  Void (never a hit):
+ *                                 fewer than 5 complete samples, a pivot of Z'Z not positive, den <= 1e-10 xc'xc.  A hit (T >= t_min)
+ *                                 takes a slot below `capacity`: d_hit_i / d_hit_j (positions, i < j), d_hit_v, d_hit_n (complete
+ *                                 samples), d_hit_stat.  d_counts (2 uint64, zeroed by the call): [0] hits, counted beyond the
+ *                                 capacity too; [1] pairs screened.  min_dist > 0: a pair with d_chrom[i] == d_chrom[j] and
+ *                                 |d_pos[i] - d_pos[j]| < min_dist is not screened (d_chrom int32, d_pos int64, per position). */
+int jxg_pairscreen_max_variants(void);
+int jxg_pairscreen_tables_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows_i, int ni, const int32_t *d_rows_j,
+                              int nj, const int8_t *d_planes, int64_t plane_stride, int32_t *d_n, int64_t *d_r, void *stream);
+int jxg_pairscreen_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const uint8_t *d_flip,
+                            const int32_t *d_chrom, const int64_t *d_pos, int64_t min_dist, const int8_t *d_planes,
+                            int64_t plane_stride, double scale, double sigma2, const double *d_variants, int nvariants, double t_min,
+                            int64_t capacity, int32_t *d_hit_i, int32_t *d_hit_j, int32_t *d_hit_v, int32_t *d_hit_n,
+                            double *d_hit_stat, uint64_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

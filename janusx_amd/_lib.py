@@ -195,6 +195,10 @@ SIGNATURES = {
     "jxg_farmcpu_max_qtn": [],
     "jxg_farmcpu_fem_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_d, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
     "jxg_farmcpu_final_stats": [c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_d, c_i, c_p, c_p],
+    "jxg_pairscreen_max_variants": [],
+    "jxg_pairscreen_tables_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_p, c_p],
+    "jxg_pairscreen_scan_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_l, c_p, c_l, c_d, c_d, c_p, c_i, c_d, c_l, c_p, c_p, c_p,
+                                c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

@@ -25,10 +25,12 @@ python/janusx/script/grm.py:18-23, 1874-1975, python/janusx/assoc/workflow_model
                                  (site / sample QC tables and LD scores; WINDOW: 100, 100kb, 0.1mb, 100000b, 10cm; bare -ldsc: 100kb)
   python -m janusx_amd tree -bfile PREFIX -nj [exact] [-maf 0.02] [-geno 0.05] [-het 0.02] [-snps-only] [-o OUT | -o DIR/ -prefix NAME]
                                  [--write-phylip] [--no-fasta]   (neighbour-joining tree: {out}.nwk, {out}.fasta, {out}.phy)
-  python -m janusx_amd fvlmm2 -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-i PAIRS.txt | -among SNPS.txt [--op '*']) [-c COV.tsv] [-k GRM.npy]
+  python -m janusx_amd fvlmm2 -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] (-i PAIRS.txt | -among SNPS.txt [--op '*'] | -screen [P]) [-c COV.tsv] [-k GRM.npy]
                                  [-maf 0.02] [-geno 0.05] [-het 1.0] [-snps-only] [--batch-size 4096] [--n-tests 0] [-pmax P]
+                                 [-screen-top 4096] [-screen-ops '*,&,|,^'] [-screen-min-dist BP] [-screen-among SNPS.txt]
                                  [-o OUT | -o DIR/ -prefix NAME]   (joint SNP-pair interaction test at the null lambda:
-                                 {out}.{trait}.fvlmm2.tsv, {out}.fvlmm2.skip)
+                                 {out}.{trait}.fvlmm2.tsv, {out}.fvlmm2.skip; -screen: exhaustive pair screen in front of it,
+                                 {out}.{trait}.fvlmm2.screen.tsv, whose p_screen ranks and does not test)
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -BLUP [-cv K] [-seed 42] [-k GRM.npy]
   python -m janusx_amd gs   -bfile PREFIX -p PHENO.tsv [-n TRAIT ...] -rrBLUP [-lambda L] [-tol 1e-4] [-max-iter 100] [-cv K]
                             [-maf 0.02] [-geno 0.05] [-o OUT]
@@ -1793,7 +1795,9 @@ def cmd_fvlmm2(args):
     interaction file the joint test of  y = covariates + SNP1 + SNP2 + combo + Zu + e  at the null model's lambda
     -> `{out}.{trait}.fvlmm2.tsv`, and `{out}.fvlmm2.skip` for the lines that did not resolve.  The pair rows are rotated with the
     trait's eigenvectors before the test (the reference's script leaves them unrotated; README, known differences).  Extensions:
-    -among SNPS.txt [--op OP] tests all pairs among the named SNPs, -pmax P writes only the rows with p_combo_joint <= P.  The
+    -among SNPS.txt [--op OP] tests all pairs among the named SNPs, -pmax P writes only the rows with p_combo_joint <= P,
+    -screen [P] scores every pair of the active rows against every combo variant first (`fvlmm2_screen_packed`, csrc/k_pairscreen.hip)
+    -> `{out}.{trait}.fvlmm2.screen.tsv`, and hands the best -screen-top hits to the joint test.  The
     reference's `.fvlmm2.log` and configuration banner are not written; non-BED input is refused."""
     from . import fvlmm2 as f2
     for flag, what in (("vcf", "-vcf"), ("hmp", "-hmp"), ("file", "-file")):
@@ -1801,7 +1805,24 @@ def cmd_fvlmm2(args):
             raise SystemExit(f"fvlmm2: {what} input is not supported on this build; give a PLINK prefix with -bfile")
     if not args.bfile:
         raise SystemExit("fvlmm2 needs -bfile PREFIX")
-    if not args.interaction and not args.among:
+    screen = getattr(args, "screen", None) is not None
+    variants = t_min = None
+    if screen:
+        if args.interaction or args.among:
+            raise SystemExit("fvlmm2: -screen finds its own pairs and cannot be combined with -i or -among (restrict its rows with "
+                             "-screen-among SNPS.txt)")
+        try:
+            t_min = f2.chi2_1_quantile(args.screen)
+            variants = f2.screen_variants(args.screen_ops)
+        except ValueError as e:
+            raise SystemExit(f"fvlmm2: {e}") from None
+        if int(args.screen_top) < 1:
+            raise SystemExit("-screen-top must be >= 1")
+        if int(args.screen_min_dist) < 0:
+            raise SystemExit("-screen-min-dist must be >= 0")
+        if args.screen_among and not os.path.isfile(args.screen_among):
+            raise SystemExit(f"fvlmm2: -screen-among file not found: {args.screen_among}")
+    elif not args.interaction and not args.among:
         raise SystemExit("fvlmm2 needs an interaction file (-i PAIRS.txt) and/or -among SNPS.txt")
     if int(args.n_tests) < 0:
         raise SystemExit("--n-tests must be >= 0")
@@ -1839,10 +1860,28 @@ def cmd_fvlmm2(args):
     if among_names is not None:
         sp2, sk2 = f2.among_specs(among_names, name_map, row_names, args.op)
         specs, skipped = specs + sp2, skipped + sk2
-    if not specs:
+    screen_rows = None
+    if screen and args.screen_among:                          # no cap on the names: the screen takes any row list
+        with open(args.screen_among, "r", encoding="utf-8", errors="replace") as fh:
+            wanted = [w[0] for w in (line.split() for line in fh) if w and not w[0].startswith("#")]
+        found = set()
+        for k, name in enumerate(wanted, start=1):
+            try:
+                found.add(f2.resolve_snp_token(name, name_map))
+            except f2.NameLookupError as e:
+                skipped.append(f2.Skipped(f"screen-among:{k}", str(name), e.reason))
+        screen_rows = np.array(sorted(found), dtype=np.int64)
+        if screen_rows.size < 2:
+            raise SystemExit("fvlmm2: -screen-among names fewer than two active variants")
+    if not specs and not screen:
         raise SystemExit(f"fvlmm2: {f2.NO_EXPRESSIONS}")
     out = _resolve_out(args, src)
-    print(f"Resolved {len(specs)} interaction rows against {len(row_names)} active filtered variants; skipped={len(skipped)}.")
+    if screen:
+        n_rows = len(row_names) if screen_rows is None else int(screen_rows.size)
+        print(f"Screening the pairs of {n_rows} of {len(row_names)} active filtered variants, {len(variants)} variants each, "
+              f"at chi2 >= {t_min:.4f} (P = {float(args.screen):g}); skipped={len(skipped)}.")
+    else:
+        print(f"Resolved {len(specs)} interaction rows against {len(row_names)} active filtered variants; skipped={len(skipped)}.")
     if skipped:
         f2.write_skip(f"{out}.fvlmm2.skip", skipped)
         print(f"Skipped interaction rows were written to {out}.fvlmm2.skip")
@@ -1886,13 +1925,42 @@ def cmd_fvlmm2(args):
         lbd = float(model.null.lbd)
         if not (math.isfinite(lbd) and lbd > 0.0):
             raise SystemExit(f"Trait {name} produced invalid null lambda: {lbd}")
+        n_tests = int(args.n_tests)
+        if screen:
+            # first stage: every pair of the active rows against every variant; the top K hits go on to the joint test
+            resid, sigma2 = f2.screen_residual(model.S, model.xcov, model.y, model.ut, lbd)
+            _names, chrom_codes = np.unique(np.asarray([str(c) for c in chrom]), return_inverse=True)
+            try:
+                hits = jxrs.fvlmm2_screen_packed(packed_t, n_fam, flip, resid, sigma2, variants, t_min, rows=screen_rows,
+                                                 chrom_id=chrom_codes.astype(np.int32), pos=np.asarray(pos_bp, dtype=np.int64),
+                                                 min_dist=int(args.screen_min_dist), sample_indices=keep_idx)
+            except RuntimeError as e:
+                raise SystemExit(f"fvlmm2: {e}") from None
+            combo = [variants[v].spelled(row_names[a], row_names[b]) for a, b, v in zip(hits["row1"], hits["row2"], hits["variant"])]
+            spath = f"{out}.{f2.trait_label(name)}.fvlmm2.screen.tsv"
+            f2.write_screen_table(spath, [row_names[a] for a in hits["row1"]], [row_names[b] for b in hits["row2"]], combo,
+                                  hits["n_complete"], hits["stat"])
+            top = min(int(args.screen_top), len(combo))
+            print(f"[{name}] screen: pairs={hits['pairs_screened']} variants={len(variants)} hits={hits['hits_total']} "
+                  f"top={top} sigma2={sigma2:.5g} -> {spath}")
+            specs = [f2.PairSpec(int(hits["row1"][k]), int(hits["row2"][k]), variants[hits["variant"][k]].op,
+                                 variants[hits["variant"][k]].neg1, variants[hits["variant"][k]].neg2, combo[k],
+                                 row_names[hits["row1"][k]], row_names[hits["row2"][k]]) for k in range(top)]
+            row1 = np.array([sp.row1 for sp in specs], dtype=np.int64)
+            row2 = np.array([sp.row2 for sp in specs], dtype=np.int64)
+            ops = [sp.op for sp in specs]
+            neg1 = np.array([sp.neg1 for sp in specs], dtype=bool)
+            neg2 = np.array([sp.neg2 for sp in specs], dtype=bool)
+            if n_tests == 0:                                  # every screened (pair, variant) was a hypothesis
+                n_tests = int(hits["pairs_screened"]) * len(variants)
+                print(f"[{name}] BH hypothesis count: {n_tests} (pairs screened x variants)")
         try:
             res = jxrs.fvlmm2_pairs_packed(packed_t, n_fam, flip, maf, row1, row2, ops, neg1, neg2, model.S, model.xcov, model.y,
                                            model.ut, math.log10(lbd), sample_indices=keep_idx, batch_size=int(args.batch_size))
         except RuntimeError as e:
             raise SystemExit(f"fvlmm2: {e}") from None
         joint = np.stack([res[c] for c in ("beta1", "se1", "p1", "beta2", "se2", "p2", "beta_combo", "se_combo", "p_combo")], axis=1)
-        fdr = f2.bh_adjust(joint[:, 8], n_tests=int(args.n_tests) if int(args.n_tests) > 0 else None)
+        fdr = f2.bh_adjust(joint[:, 8], n_tests=n_tests if n_tests > 0 else None)
         keep = None if args.pmax is None else joint[:, 8] <= float(args.pmax)
         path = f"{out}.{f2.trait_label(name)}.fvlmm2.tsv"
         wrote = f2.write_table(path, [chrom[r] for r in row1], [pos_bp[r] for r in row1], [sp.expr for sp in specs],
@@ -2148,6 +2216,21 @@ def main(argv=None):
                    help="test all unordered pairs among the SNPs named in this file, one name per line, at most 4096 (an "
                         "extension); may be combined with -i, whose rows come first")
     v.add_argument("--op", dest="op", default="*", help="operator of the -among pairs: *, &, | or ^ (default *)")
+    v.add_argument("-screen", "--screen", dest="screen", type=float, nargs="?", const=1e-5, default=None, metavar="P",
+                   help="exhaustive first stage (an extension): score every pair of the active rows against every combo variant on "
+                        "the int8 pipes, keep the hits whose chi2_1 p-value is <= P (default 1e-5) in "
+                        "{out}.{trait}.fvlmm2.screen.tsv and hand the best -screen-top of them to the joint test.  p_screen ranks, "
+                        "it does not test: it uses the samples called at both SNPs (the joint test imputes), hard calls for '*', "
+                        "and the GRAMMAR residual of the null fit with one global variance.  Not with -i or -among")
+    v.add_argument("-screen-top", "--screen-top", dest="screen_top", type=int, default=4096, metavar="K",
+                   help="hits handed to the joint test (default 4096, one device batch)")
+    v.add_argument("-screen-ops", "--screen-ops", dest="screen_ops", default="*,&,|,^", metavar="SPEC",
+                   help="comma-separated operators of the screen; '&' and '|' stand for their four negation patterns, '!&', '&!', "
+                        "'!&!' for one (default '*,&,|,^': 10 variants; at most 16)")
+    v.add_argument("-screen-min-dist", "--screen-min-dist", dest="screen_min_dist", type=int, default=0, metavar="BP",
+                   help="do not screen pairs on one chromosome closer than BP (default 0: off)")
+    v.add_argument("-screen-among", "--screen-among", dest="screen_among", default=None, metavar="SNPS.txt",
+                   help="screen only the pairs among the SNPs named in this file, one name per line, any number")
     v.add_argument("-pmax", "--pmax", dest="pmax", type=float, default=None, metavar="P",
                    help="write only the rows with p_combo_joint <= P (an extension); the FDR column is computed over every "
                         "tested row first")

@@ -1,5 +1,6 @@
 """Host side of `jx fvlmm2`: the interaction-file grammar, the code tables of a SNP pair, the Benjamini-Hochberg adjustment, the
-number formats and the table writers.  The device side is `janusx.fvlmm2_pairs_packed` (csrc/k_fvlmm2.hip).
+number formats and the table writers.  The device side is `janusx.fvlmm2_pairs_packed` (csrc/k_fvlmm2.hip); for `-screen` (the
+variants by genotype class, the chi^2 quantile, the residual, the screen table) `janusx.fvlmm2_screen_packed` (csrc/k_pairscreen.hip).
 
 The rules are those of the reference's script (python/janusx/script/fvlmm2.py), restated: the strings a user meets -- the grammar,
 the skip reasons, the error texts, the column names -- are the reference's, the code is this project's.
@@ -297,6 +298,162 @@ def write_skip(path, skipped):
         w = csv.writer(fh, delimiter="\t", lineterminator="\n", quoting=csv.QUOTE_MINIMAL)
         w.writerow(Skipped._fields)
         w.writerows(skipped)
+
+
+# ---- the pair screen (`-screen`, an extension; device side: janusx.fvlmm2_screen_packed, csrc/k_pairscreen.hip) ---------------
+
+SCREEN_DEFAULT_OPS = "*,&,|,^"
+SCREEN_DEFAULT_P = 1e-5
+SCREEN_DEFAULT_TOP = 4096           # one device batch of the joint test
+SCREEN_MAX_VARIANTS = 16
+SCREEN_COLUMNS = ("snp1", "snp2", "combo_id", "n_complete", "stat", "p_screen")
+
+
+class ScreenVariant(NamedTuple):
+    """One combo of the screen by genotype class (hom-ref 0, het 1, hom-alt 2): combo (3, 3)[a][b], lit1 (3)[a], lit2 (3)[b], f64."""
+    op: str
+    neg1: bool
+    neg2: bool
+    combo: np.ndarray
+    lit1: np.ndarray
+    lit2: np.ndarray
+
+    def spelled(self, snp1, snp2):
+        """The expression as the interaction parser reads it back."""
+        return _spelled(snp1, self.neg1) + self.op + _spelled(snp2, self.neg2)
+
+
+def variant_tables(op, neg1, neg2):
+    """The class tables of one (op, neg1, neg2) on hard calls, by the rules of `pair_tables`: a literal is the call, or 2 - call when
+    negated; '&' the smaller, '|' the larger of the literals, '^' `_XOR3`, '*' the product of the calls (no negation)."""
+    if op not in OPS:
+        raise ValueError(f"Unsupported interaction operator: {op}")
+    if op == "*" and (neg1 or neg2):
+        raise ValueError("Negated literals are not supported for multiplicative interaction '*'.")
+    call = np.arange(3, dtype=np.float64)
+    lit1, lit2 = (2.0 - call if neg1 else call), (2.0 - call if neg2 else call)
+    a, b = lit1[:, None], lit2[None, :]
+    if op == "*":
+        combo = a * b
+    elif op == "&":
+        combo = np.minimum(a, b)
+    elif op == "|":
+        combo = np.maximum(a, b)
+    else:
+        combo = _XOR3.astype(np.float64)[lit1.astype(np.intp)[:, None], lit2.astype(np.intp)[None, :]]
+    return ScreenVariant(op, bool(neg1), bool(neg2), np.ascontiguousarray(combo, dtype=np.float64), lit1, lit2)
+
+
+def screen_variants(spec=SCREEN_DEFAULT_OPS):
+    """`-screen-ops`: a comma-separated list of operators.  '&' and '|' alone stand for their four negation patterns, '!&', '&!'
+    and '!&!' (likewise '|') for one of them; '^' and '*' take no negation.  The default gives 10 variants; at most 16; an entry
+    that comes twice counts once -> list of ScreenVariant in the order of the list."""
+    out, seen = [], set()
+    tokens = [t.strip() for t in str(spec).split(",")]
+    if not any(tokens):
+        raise ValueError("-screen-ops: no operator given")
+    for tok in tokens:
+        core = tok.strip("!")
+        if core not in OPS or tok not in (core, "!" + core, core + "!", "!" + core + "!"):
+            raise ValueError(f"-screen-ops: unsupported entry '{tok}' (operators: {' '.join(OPS)}; '!' before / after '&' or '|')")
+        if tok == core:
+            patterns = [(False, False), (True, False), (False, True), (True, True)] if core in ("&", "|") else [(False, False)]
+        else:
+            if core in ("*", "^"):
+                raise ValueError(f"-screen-ops: '{core}' takes no negation")
+            patterns = [(tok.startswith("!"), tok.endswith("!"))]
+        for neg1, neg2 in patterns:
+            if (core, neg1, neg2) not in seen:
+                seen.add((core, neg1, neg2))
+                out.append(variant_tables(core, neg1, neg2))
+    if len(out) > SCREEN_MAX_VARIANTS:
+        raise ValueError(f"-screen-ops: at most {SCREEN_MAX_VARIANTS} variants, got {len(out)}")
+    return out
+
+
+def variant_array(variants):
+    """(V, 15) f64 for the device: combo (9, a major), lit1 (3), lit2 (3) of every variant; a (V, 15) array passes through."""
+    if isinstance(variants, np.ndarray):
+        return np.ascontiguousarray(variants, dtype=np.float64).reshape(-1, 15)
+    return np.array([np.concatenate([np.asarray(v.combo, dtype=np.float64).reshape(9), np.asarray(v.lit1, dtype=np.float64).reshape(3),
+                                     np.asarray(v.lit2, dtype=np.float64).reshape(3)]) for v in variants],
+                    dtype=np.float64).reshape(-1, 15)
+
+
+def permute_classes(variant, flip1, flip2):
+    """The variant as a flipped row sees it: a flipped row's class a reads the tables at 2 - a."""
+    i1 = [2, 1, 0] if flip1 else [0, 1, 2]
+    i2 = [2, 1, 0] if flip2 else [0, 1, 2]
+    return variant._replace(combo=variant.combo[np.ix_(i1, i2)], lit1=variant.lit1[i1], lit2=variant.lit2[i2])
+
+
+def chi2_1_pvalue(stat):
+    """The upper tail of chi^2_1 (`lm2.chi2_sf`, the project's own code)."""
+    from .lm2 import chi2_sf
+    return chi2_sf(float(stat), 1.0)
+
+
+def chi2_1_quantile(p):
+    """t with chi2_1_pvalue(t) = p, 0 < p < 1, by bisection on the forward p-value (monotone); the bracket ends where the erfc form
+    underflows."""
+    p = float(p)
+    if not (0.0 < p < 1.0):
+        raise ValueError("-screen P must be within (0, 1)")
+    lo, hi = 0.0, 1400.0
+    if chi2_1_pvalue(hi) >= p:
+        return hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if chi2_1_pvalue(mid) > p:
+            lo = mid
+        else:
+            hi = mid
+    return hi
+
+
+def screen_residual(s, xcov_rot, y_rot, u_t, lbd):
+    """The GRAMMAR residual of the null fit in sample space and its variance -> (r (n) f64, sigma2):
+    r = U W (y~ - X~ b^), W = 1 / (s + lambda), b^ the GLS estimate of the rotated null model; sigma2 = r'r / (n - p_cov).
+    s, xcov_rot, y_rot, u_t: host arrays or torch tensors; u_t (n, n) is U^T row-major, so r = u_t' v, taken in row blocks in f64."""
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float64)
+    s, x, y = host(s).ravel(), host(xcov_rot), host(y_rot).ravel()
+    n = y.shape[0]
+    x = x.reshape(n, -1)
+    w = 1.0 / (s + float(lbd))
+    xw = x * w[:, None]
+    beta = np.linalg.solve(xw.T @ x, xw.T @ y)
+    v = w * (y - x @ beta)
+    if tuple(u_t.shape) != (n, n):
+        raise ValueError("u_t must be (n, n) and row-major U^T")
+    r = np.zeros(n, dtype=np.float64)
+    step = 2048
+    if hasattr(u_t, "detach"):
+        import torch
+        vt = torch.from_numpy(v).to(u_t.device)
+        rt = torch.zeros(n, dtype=torch.float64, device=u_t.device)
+        for k0 in range(0, n, step):
+            rt += vt[k0:k0 + step] @ u_t[k0:k0 + step].to(torch.float64)
+        r = rt.cpu().numpy()
+    else:
+        for k0 in range(0, n, step):
+            r += v[k0:k0 + step] @ np.asarray(u_t[k0:k0 + step], dtype=np.float64)
+    dof = n - x.shape[1]
+    if dof <= 0:
+        raise ValueError("screen_residual: n must exceed the covariate count")
+    return r, float(r @ r) / float(dof)
+
+
+def write_screen_table(path, snp1, snp2, combo_id, n_complete, stat):
+    """`{out}.{trait}.fvlmm2.screen.tsv`: one line per kept hit in the order given; p_screen is the chi^2_1 tail of stat (it ranks,
+    it does not test) -> lines written."""
+    with open(path, "w", encoding="utf-8") as fh:
+        fh.write("\t".join(SCREEN_COLUMNS) + "\n")
+        for a, b, cid, nc, t in zip(snp1, snp2, combo_id, n_complete, stat):
+            fh.write("\t".join([str(a), str(b), str(cid), str(int(nc)), format_fixed4(t), format_sci4(chi2_1_pvalue(t))]) + "\n")
+    return len(stat)
 
 
 def trait_label(trait_ref):

@@ -2870,6 +2870,129 @@ def fvlmm2_pairs_packed(packed, n_samples, row_flip, row_maf, row1, row2, op, ne
 
 
 # ------------------------------------------------------------------------------------------------
+# exhaustive SNP-pair screen on the int8 pipes  (extension; csrc/k_pairscreen.hip)
+# ------------------------------------------------------------------------------------------------
+
+PAIRSCREEN_MAX_N = 1 << 24
+PAIRSCREEN_MAX_VARIANTS = 16
+
+
+def _pairscreen_planes(panel, r):
+    """The digit planes of the one column r over the samples of a panel (`pipeline._LmtOperand`, `jxg_lmt_prepare`)
+    -> (operand, plane stride in bytes, scale = S 2^-27 as a float)."""
+    import torch
+    from .pipeline import _LmtOperand
+    if panel.n > PAIRSCREEN_MAX_N:
+        raise RuntimeError(f"pair screen: at most {PAIRSCREEN_MAX_N} samples, got {panel.n}")
+    if _is_device_tensor(r):
+        col = r.to(device=panel.device, dtype=torch.float64).reshape(1, -1).contiguous()
+        finite = bool(torch.isfinite(col).all())
+    else:
+        col = _c(r, np.float64).reshape(1, -1)
+        finite = bool(np.isfinite(col).all())
+    if int(col.shape[1]) != panel.n:
+        raise RuntimeError(f"len(r) {int(col.shape[1])} != selected sample count {panel.n}")
+    if not finite:
+        raise RuntimeError("r contains non-finite values")
+    op = _LmtOperand(col, panel.n, panel.npad, panel.device)
+    return op, int(op.planes.shape[1]) * int(op.planes.shape[2]), float(op.scale[0].item())
+
+
+def _pairscreen_rows(rows, m, what):
+    rows = _c(rows, np.int64).ravel()
+    if rows.size and (rows.min() < 0 or rows.max() >= m):
+        raise RuntimeError(f"{what} out of range for {m} rows")
+    return rows
+
+
+def pair_class_tables_packed(packed, n_samples, rows_i, rows_j, r, sample_indices=None):
+    """Class tables of the SNP pairs (rows_i[x], rows_j[y]) of a packed payload over the selected samples (extension;
+    `jxg_pairscreen_tables_p32`).  Classes of a call: hom-ref 0, het 1, hom-alt 2; a missing call belongs to none, so a pair's
+    table runs over the samples called at both SNPs.  r (n) f64: a sample vector, host array or torch CUDA tensor
+    -> (N (Ri, Rj, 3, 3) int32 counts, R (Ri, Rj, 3, 3) int64 sums of r in units of `scale`, scale f64 = S 2^-27 with S the
+    smallest power of two >= max |r|).  Exact: r enters as its four signed radix-128 digits, what they leave (< S 2^-28 per
+    sample) is dropped, and an r of multiples of S 2^-27 is summed exactly."""
+    import torch
+    from .pipeline import _ptr, _stream
+    panel = _panel(packed, n_samples, sample_indices)
+    ri, rj = _pairscreen_rows(rows_i, panel.m, "rows_i"), _pairscreen_rows(rows_j, panel.m, "rows_j")
+    op, pstride, scale = _pairscreen_planes(panel, r)
+    dev = panel.device
+    out_n = torch.zeros((ri.size, rj.size, 3, 3), dtype=torch.int32, device=dev)
+    out_r = torch.zeros((ri.size, rj.size, 3, 3), dtype=torch.int64, device=dev)
+    if ri.size and rj.size:
+        ti, tj = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (ri, rj))
+        check(lib().jxg_pairscreen_tables_p32(_ptr(panel.p32), panel.m, panel.n, _ptr(ti), int(ri.size), _ptr(tj), int(rj.size),
+                                              _ptr(op.planes), pstride, _ptr(out_n), _ptr(out_r), _stream()))
+    return out_n.cpu().numpy(), out_r.cpu().numpy(), scale
+
+
+def fvlmm2_screen_packed(packed, n_samples, row_flip, r, sigma2, variants, t_min, rows=None, chrom_id=None, pos=None, min_dist=0,
+                         cap=1 << 22, sample_indices=None):
+    """Exhaustive screen of the unordered SNP pairs of a packed payload (extension; `jxg_pairscreen_scan_p32`): for every pair
+    row1 < row2 of `rows` (payload rows; None: all) and every variant the score statistic T of the combo term given the intercept
+    and both literals in the linear model of r on the pair's complete samples, error variance `sigma2` (> 0).  variants: at most 16
+    `fvlmm2.ScreenVariant` (`fvlmm2.screen_variants`), or their (V, 15) f64 array (`fvlmm2.variant_array`); row_flip: one entry per
+    payload row, a flipped row reads its tables at class 2 - a.  A pair / variant with fewer than 5 complete samples, a literal
+    that is constant or collinear with the other, or a combo inside the span of the literals is void and never a hit.
+    chrom_id / pos (one entry per payload row) with min_dist > 0: a pair on one chromosome closer than min_dist is not screened.
+    -> dict: row1, row2, variant, stat, n_complete (the hits with T >= t_min, sorted by stat descending, row1, row2, variant),
+    pairs_screened, hits_total.  More than `cap` hits raise a RuntimeError that names the count."""
+    import torch
+    from .pipeline import _ptr, _stream
+    from . import fvlmm2 as f2
+    var = f2.variant_array(variants)
+    nv = int(var.shape[0])
+    if nv < 1 or nv > PAIRSCREEN_MAX_VARIANTS:
+        raise RuntimeError(f"pair screen: between 1 and {PAIRSCREEN_MAX_VARIANTS} variants, got {nv}")
+    if not np.isfinite(var).all():
+        raise RuntimeError("pair screen: variant tables must be finite")
+    sigma2, t_min, min_dist, cap = float(sigma2), float(t_min), int(min_dist), int(cap)
+    if not (np.isfinite(sigma2) and sigma2 > 0.0):
+        raise RuntimeError("sigma2 must be finite and positive")
+    if np.isnan(t_min):
+        raise RuntimeError("t_min must not be NaN")
+    if min_dist < 0 or cap < 0:
+        raise RuntimeError("min_dist and cap must be >= 0")
+    panel = _panel(packed, n_samples, sample_indices)
+    m = panel.m
+    flip = np.asarray(row_flip).astype(bool).ravel()
+    if flip.shape[0] != m:
+        raise RuntimeError(f"row_flip length mismatch: got {flip.shape[0]}, expected packed_rows={m}")
+    lst = np.arange(m, dtype=np.int64) if rows is None else np.unique(_pairscreen_rows(rows, m, "rows"))
+    if min_dist > 0:
+        if chrom_id is None or pos is None:
+            raise RuntimeError("min_dist needs chrom_id and pos")
+        cid, bp = _c(chrom_id, np.int32).ravel(), _c(pos, np.int64).ravel()
+        if cid.shape[0] != m or bp.shape[0] != m:
+            raise RuntimeError(f"chrom_id/pos length mismatch: expected packed_rows={m}")
+    op, pstride, scale = _pairscreen_planes(panel, r)
+    dev = panel.device
+    nl = int(lst.size)
+    rows_t = None if rows is None else torch.from_numpy(lst.astype(np.int32)).to(dev)
+    flip_t = torch.from_numpy(np.ascontiguousarray(flip[lst]).astype(np.uint8)).to(dev)
+    cid_t = torch.from_numpy(np.ascontiguousarray(cid[lst])).to(dev) if min_dist > 0 else None
+    bp_t = torch.from_numpy(np.ascontiguousarray(bp[lst])).to(dev) if min_dist > 0 else None
+    var_t = torch.from_numpy(var).to(dev)
+    slots = max(1, min(cap, nl * (nl - 1) // 2 * nv))
+    hit_i, hit_j, hit_v, hit_n = (torch.empty(slots, dtype=torch.int32, device=dev) for _ in range(4))
+    hit_t = torch.empty(slots, dtype=torch.float64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    check(lib().jxg_pairscreen_scan_p32(_ptr(panel.p32), m, panel.n, _ptr(rows_t), nl, _ptr(flip_t), _ptr(cid_t), _ptr(bp_t), min_dist,
+                                        _ptr(op.planes), pstride, scale, sigma2, _ptr(var_t), nv, t_min, cap, _ptr(hit_i),
+                                        _ptr(hit_j), _ptr(hit_v), _ptr(hit_n), _ptr(hit_t), _ptr(counts), _stream()))
+    hits_total, pairs_screened = (int(v) for v in counts.cpu().numpy())
+    if hits_total > cap:
+        raise RuntimeError(f"pair screen: {hits_total} hits exceed the capacity of {cap}; raise t_min (a smaller -screen P) or cap")
+    k = hits_total
+    r1, r2 = lst[hit_i[:k].cpu().numpy()], lst[hit_j[:k].cpu().numpy()]
+    hv, hn, ht = hit_v[:k].cpu().numpy(), hit_n[:k].cpu().numpy(), hit_t[:k].cpu().numpy()
+    order = np.lexsort((hv, r2, r1, -ht))                     # stat descending, then row1, row2, variant
+    return {"row1": r1[order], "row2": r2[order], "variant": hv[order].astype(np.int32), "stat": ht[order],
+            "n_complete": hn[order].astype(np.int32), "pairs_screened": pairs_screened, "hits_total": hits_total}
+
+
+# ------------------------------------------------------------------------------------------------
 # BED -> QC -> scan -> TSV entry points (src/stats/lmm.rs:2488-2751, src/stats/fvlmm.rs:2482-2526,
 # orchestration of src/stats/lmm.rs:975-1477 `run_unified_bed_scan_to_tsv_common`)
 # ------------------------------------------------------------------------------------------------
