@@ -416,10 +416,11 @@ int jxg_fvlmm_prepare(const double *d_s, const double *d_xcov, const double *d_y
                       float *d_w, float *d_py, float *d_wx, double *h_a_chol, double *h_scalars3);
 
 /* E2. fixed-lambda scan of a rotated block -> d_out (nrows, 3 or 4) f64 = [beta, se, p(, plrt)]; with_plrt adds
- * the ML likelihood-ratio column against nullml (log_det_v from jxg_fvlmm_prepare).  src/stats/fvlmm.rs:1691-1805. */
-int jxg_fvlmm_scan(const float *d_grot, int nrows, int n, int p, const float *d_w, const float *d_py,
-                   const float *d_wx, const double *h_a_chol, double ypy, int df, int with_plrt, double nullml,
-                   double log_det_v, double *d_out, void *stream);
+ * the ML likelihood-ratio column against nullml (log_det_v from jxg_fvlmm_prepare).  src/stats/fvlmm.rs:1691-1805.
+ * The Cholesky factor is on the device: launch only (no allocation, no synchronisation). */
+int jxg_fvlmm_scan_dev(const float *d_grot, int nrows, int n, int p, const float *d_w, const float *d_py,
+                       const float *d_wx, const double *d_a_chol, double ypy, int df, int with_plrt, double nullml,
+                       double log_det_v, double *d_out, void *stream);
 
 /* LMM2 scan of a rotated block ("next" row 8f-2): per SNP a REML Brent, `final_beta_se`, then a second Brent on
  * -ml_loglike seeded with the REML optimum and the LRT against nullml.  d_out6 (nrows, 6) f64 =
@@ -566,11 +567,6 @@ int jxg_splmm_exact_scan_dev(const float *d_grot, int nrows, int n, int p, const
                              const float *d_wx, const double *d_a_chol, double ypy, int df, double *d_out,
                              void *stream);
 
-/* E2 with the Cholesky factor already on the device: launch only (no allocation, no synchronisation). */
-int jxg_fvlmm_scan_dev(const float *d_grot, int nrows, int n, int p, const float *d_w, const float *d_py,
-                       const float *d_wx, const double *d_a_chol, double ypy, int df, int with_plrt, double nullml,
-                       double log_det_v, double *d_out, void *stream);
-
 /* ------------------------------------------------------------------------------------------------
  * Host layer (reference PyO3 signatures with C arrays)
  * ---------------------------------------------------------------------------------------------- */
@@ -593,45 +589,9 @@ int jx_grm_stream_payload_f32(const uint8_t *packed, int64_t m, int n_samples, i
                               float maf_threshold, float max_missing_rate, float het_threshold,
                               float *out_k, int64_t *out_eff_m, uint8_t *out_keep);
 
-/* `rust_eigh_from_array_f64` (src/math/eigh.rs:1621-1703): a (n,n) f64 row-major (symmetrised
- * (A+A^T)/2 like eigh.rs:179) -> evals (n) ascending, evecs (n,n) row-major, columns = eigenvectors
- * (NULL = values only still computes vectors internally). */
-int jx_eigh_f64(const double *a, int n, double diag_shift, double *evals, double *evecs);
-
-/* `lmm_rotate_x_y_with_ut_f64` (src/stats/reml.rs:107-198). */
-int jx_lmm_rotate_x_y_with_ut_f64(const float *u_t, int n, const double *x, int q, const double *y,
-                                  double *out_x, double *out_y);
-
-/* `lmm_reml_null_f32` (src/stats/reml.rs:570-616) -> out3 = (lbd, ml, reml). */
-int jx_lmm_reml_null(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                     double high, int max_iter, double tol, double *out3);
-
-/* `lmm_reml_chunk_f32` (src/stats/lmm.rs:333-335; rotated input) and `lmm_reml_chunk_from_snp_f32`
- * (src/stats/lmm.rs:1479-1630; u_t != NULL -> rotate first).  has_nullml -> 4 output columns. */
-int jx_lmm_reml_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                      double high, const float *snp_chunk, int64_t m_chunk, const float *u_t, int max_iter,
-                      double tol, int has_nullml, double nullml, double *out);
-
-/* `ml_loglike_null_f32` (src/stats/reml.rs:618-646) -> *ml. */
-int jx_ml_loglike_null(const double *s, const double *xcov, const double *y_rot, int n, int p, double log10_lbd,
-                       double *ml);
-
-/* `lmm_reml_lmm2_chunk_from_snp_f32` (src/stats/lmm.rs:1632-1760; u_t == NULL -> snp_chunk is already rotated)
- * -> out (m_chunk, 6) = [beta, se, pwald, lambda_reml, ml_alt, plrt]. */
-int jx_lmm2_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p, double low, double high,
-                  const float *snp_chunk, int64_t m_chunk, const float *u_t, double nullml, int max_iter,
-                  double tol, double *out);
-
-/* Null ML of `lmm_reml_lmm2_assoc_bed_to_tsv_f32` when the caller passes no nullml (src/stats/lmm.rs:2902-2921)
- * -> out2 = (log10 lambda, ml0). */
-int jx_lmm2_null_ml(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                    double high, int max_iter, double tol, int has_init, double init, double *out2);
-
-/* `fvlmm_assoc_chunk_f32` / `fvlmm_assoc_chunk_from_snp_f32` (src/stats/fvlmm.rs:1941-1994, 2114-2262).
- * has_nullml -> 4 output columns. */
-int jx_fvlmm_assoc_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p,
-                         double log10_lbd, const float *snp_chunk, int64_t m_chunk, const float *u_t,
-                         int has_nullml, double nullml, double *out);
+/* The dense-chunk mirrors (`lmm_reml_chunk*_f32`, `fvlmm_assoc_chunk*_f32`, `lmm_reml_lmm2_chunk_from_snp_f32`, the null-model
+ * helpers, `lmm_rotate_x_y_with_ut_f64`, `rust_eigh_from_array_f64`, `lm_block_assoc_f32`) have no host-pointer entry point: they
+ * compose the jxg_* pieces above on device buffers (`pipeline.scan_dense_rows`). */
 
 /* `lm_block_assoc_packed` (src/stats/glm.rs:3550-3860): the plain LM scan `jx gwas -lmm / -fvlmm` switches to when the null
  * likelihood-ratio test (jx_gwas_lmm_lm_null_lrt_decision) finds no polygenic variance
@@ -660,12 +620,9 @@ int jxg_lm_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t 
 int jxg_lm2_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows, const float *d_lut,
                      const double *d_w, int nblk, int nblk_v, int q_rank, int k, double rss0, int df, double *d_sums,
                      double *d_out, int32_t *d_flag, int stage, void *stream);
-/* `lm_block_assoc_f32` (src/stats/glm.rs:4313-4497): the same LM formulas on an already decoded SNP-major f32 block
- * g (m, n) on the host; out (m, 4).  Row rules of that entry point (s must exceed 1e-12; a non-finite variance or standard
- * error voids the row, glm.rs:4457-4479). */
-int jx_lm_assoc_dense(const double *y, const double *x, const double *ixx, int q0, const float *g, int64_t m, int n,
-                      double *out);
-/* Device half for dense rows: d_g (nrows, ld >= n) f32 on the device, the other arguments as jxg_lm_scan_p32. */
+/* Device half of `lm_block_assoc_f32` (src/stats/glm.rs:4313-4497): the same LM formulas on an already decoded SNP-major f32
+ * block d_g (nrows, ld >= n) on the device, the other arguments as jxg_lm_scan_p32.  Row rules of that entry point (s must
+ * exceed 1e-12; a non-finite variance or standard error voids the row, glm.rs:4457-4479). */
 int jxg_lm_scan_dense(const float *d_g, int nrows, int n, int64_t ld, const double *d_xr, int q0, const double *d_ixx,
                       double yy_r, double *d_work, double *d_out, void *stream);
 

@@ -89,14 +89,10 @@ SIGNATURES = {
     "jxg_lmm_scan_tab": [c_p, c_i, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_d, c_i, c_i, c_d, c_i, c_d, c_p, c_p, c_p],
     "jxg_lmm_scan_exact": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_i, c_d, c_i, c_d, c_p, c_p, c_p],
     "jxg_fvlmm_prepare": [c_p, c_p, c_p, c_i, c_i, c_d, c_p, c_p, c_p, c_p, c_p],
-    "jxg_fvlmm_scan": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_d, c_i, c_i, c_d, c_d, c_p, c_p],
     "jxg_lmm2_scan": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_i, c_d, c_d, c_p, c_p],
     "jxg_lmm2_scan_exact": [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_i, c_d, c_d, c_p, c_p],
     "jxg_lmm2_null_ml": [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_d, c_i, c_d, c_p, c_p],
-    "jx_lmm2_chunk": [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_p, c_l, c_p, c_d, c_i, c_d, c_p],
-    "jx_lmm2_null_ml": [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_d, c_i, c_d, c_p],
     "jxg_lmm_loglike_null": [c_p, c_p, c_p, c_i, c_i, c_d, c_p, c_p],
-    "jx_ml_loglike_null": [c_p, c_p, c_p, c_i, c_i, c_d, c_p],
     "jxg_gblup_fit": [c_p, c_i, c_d, c_p, c_d, c_d, c_d, c_i, c_p, c_p, c_p],
     "jxg_packed_tdot": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "jxg_packed_tdot_f32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
@@ -123,11 +119,6 @@ SIGNATURES = {
     "jx_row_counts": [c_p, c_l, c_i, c_p, c_i, c_p],
     "jx_grm_packed": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p],
     "jx_grm_stream_payload_f32": [c_p, c_l, c_i, c_i, c_f, c_f, c_f, c_p, c_p, c_p],
-    "jx_eigh_f64": [c_p, c_i, c_d, c_p, c_p],
-    "jx_lmm_rotate_x_y_with_ut_f64": [c_p, c_i, c_p, c_i, c_p, c_p, c_p],
-    "jx_lmm_reml_null": [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_i, c_d, c_p],
-    "jx_lmm_reml_chunk": [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_p, c_l, c_p, c_i, c_d, c_i, c_d, c_p],
-    "jx_fvlmm_assoc_chunk": [c_p, c_p, c_p, c_i, c_i, c_d, c_p, c_l, c_p, c_i, c_d, c_p],
     "jx_gblup_reml_grm": [c_p, c_i, c_l, c_p, c_i, c_p, c_p, c_i, c_d, c_d, c_d, c_i, c_d, c_i, c_p, c_p, c_p],
     "jx_spgrm_packed_to_jxgrm": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_i, c_d, c_i, c_i, C.c_char_p, c_p, c_p],
     "jx_spgrm_set_part": [c_i, c_i],
@@ -164,7 +155,6 @@ SIGNATURES = {
     "jxg_splmm_grammar_scan_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_p],
     "jxg_splmm_gamma_sums": [c_p, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
     "jx_lm_residualize": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
-    "jx_lm_assoc_dense": [c_p, c_p, c_p, c_i, c_p, c_l, c_i, c_p],
     "jxg_lm_scan_dense": [c_p, c_i, c_i, c_l, c_p, c_i, c_p, c_d, c_p, c_p, c_p],
     "jxg_decode_rows_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_l, c_p],
     "jxg_rot_miss_max": [c_i, c_d],

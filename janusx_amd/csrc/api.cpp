@@ -91,9 +91,6 @@ void async_pool_keep() {
     pool_set = true;
 }
 
-int launch_symmetrize(double *d_a, int n, hipStream_t st);
-int launch_transpose_f64(const double *src, double *dst, int n, hipStream_t st);
-
 // ---- value LUTs (host) ---------------------------------------------------------------------------
 
 // GRM design LUT indexed by the 2-bit code [00, 01(missing), 10, 11]
@@ -721,231 +718,9 @@ extern "C" int jx_grm_stream_payload_f32(const uint8_t *packed, int64_t m, int n
 }
 
 // ---------------------------------------------------------------------------------------------------
-// rust_eigh_from_array_f64 (src/math/eigh.rs:1621-1703)
-// ---------------------------------------------------------------------------------------------------
-extern "C" int jx_eigh_f64(const double *a, int n, double diag_shift, double *evals, double *evecs) {
-    if (n <= 0) return fail("matrix must be non-empty");
-    DevBuf da, dw, dt;
-    const size_t nn = (size_t)n * (size_t)n;
-    if (da.alloc(sizeof(double) * nn)) return 1;
-    if (dw.alloc(sizeof(double) * (size_t)n)) return 1;
-    JX_HIP(hipMemcpy(da.p, a, sizeof(double) * nn, hipMemcpyHostToDevice));
-    if (launch_symmetrize(da.as<double>(), n, nullptr)) return 1;  // eigh.rs:179
-    if (jxg_eigh_f64(da.as<double>(), n, diag_shift, dw.as<double>(), nullptr)) return 1;
-    JX_HIP(hipMemcpy(evals, dw.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    if (evecs) {
-        if (dt.alloc(sizeof(double) * nn)) return 1;
-        if (launch_transpose_f64(da.as<double>(), dt.as<double>(), n, nullptr)) return 1;  // U^T -> U (columns = vectors)
-        JX_HIP(hipMemcpy(evecs, dt.p, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-extern "C" int jx_lmm_rotate_x_y_with_ut_f64(const float *u_t, int n, const double *x, int q, const double *y,
-                                             double *out_x, double *out_y) {
-    if (n <= 0) return fail("y must not be empty");
-    if (q < 0 || q > 15) return fail("x must have between 0 and 15 columns");
-    const int qq = q + 1;
-    std::vector<double> xy((size_t)n * qq);
-    for (int i = 0; i < n; ++i) {
-        for (int c = 0; c < q; ++c) xy[(size_t)i * qq + c] = x[(size_t)i * q + c];
-        xy[(size_t)i * qq + q] = y[i];
-    }
-    DevBuf dut, dxy, dout;
-    if (dut.alloc(sizeof(float) * (size_t)n * n)) return 1;
-    if (dxy.alloc(sizeof(double) * xy.size())) return 1;
-    if (dout.alloc(sizeof(double) * xy.size())) return 1;
-    JX_HIP(hipMemcpy(dut.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-    JX_HIP(hipMemcpy(dxy.p, xy.data(), sizeof(double) * xy.size(), hipMemcpyHostToDevice));
-    if (jxg_rotate_xy(dut.as<float>(), n, dxy.as<double>(), qq, dout.as<double>(), nullptr)) return 1;
-    JX_HIP(hipMemcpy(xy.data(), dout.p, sizeof(double) * xy.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) {
-        for (int c = 0; c < q; ++c) out_x[(size_t)i * q + c] = xy[(size_t)i * qq + c];
-        out_y[i] = xy[(size_t)i * qq + q];
-    }
-    return 0;
-}
-
-namespace {
-struct NullDev {
-    DevBuf s, x, y;
-    int upload(const double *hs, const double *hx, const double *hy, int n, int p) {
-        if (s.alloc(sizeof(double) * (size_t)n) || x.alloc(sizeof(double) * (size_t)n * p) ||
-            y.alloc(sizeof(double) * (size_t)n))
-            return 1;
-        JX_HIP(hipMemcpy(s.p, hs, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-        JX_HIP(hipMemcpy(x.p, hx, sizeof(double) * (size_t)n * p, hipMemcpyHostToDevice));
-        JX_HIP(hipMemcpy(y.p, hy, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-        return 0;
-    }
-};
-}  // namespace
-
-extern "C" int jx_lmm_reml_null(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                                double high, int max_iter, double tol, double *out3) {
-    if (low >= high) return fail("low must be < high");
-    NullDev nd;
-    DevBuf o;
-    if (nd.upload(s, xcov, y_rot, n, p) || o.alloc(3 * sizeof(double))) return 1;
-    if (jxg_lmm_reml_null(nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), n, p, low, high, max_iter, tol,
-                          o.as<double>(), nullptr))
-        return 1;
-    JX_HIP(hipMemcpy(out3, o.p, 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-extern "C" int jx_ml_loglike_null(const double *s, const double *xcov, const double *y_rot, int n, int p,
-                                  double log10_lbd, double *ml) {
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    DevBuf o;
-    if (o.alloc(2 * sizeof(double))) return 1;
-    if (jxg_lmm_loglike_null(nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), n, p, log10_lbd, o.as<double>(),
-                             nullptr))
-        return 1;
-    double h[2];
-    JX_HIP(hipMemcpy(h, o.p, sizeof(h), hipMemcpyDeviceToHost));
-    *ml = h[0];
-    return 0;
-}
-
-static const int64_t kBlockRows = 4096;  // rotate/scan block (rows x n f32 kept in HBM)
-
-extern "C" int jx_lmm_reml_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                                 double high, const float *snp_chunk, int64_t m_chunk, const float *u_t, int max_iter,
-                                 double tol, int has_nullml, double nullml, double *out) {
-    if (low >= high) return fail("low must be < high");
-    if (m_chunk <= 0) return 0;
-    const int cols = has_nullml ? 4 : 3;
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    DevBuf dut, dg, drot, dout;
-    if (u_t) {
-        if (dut.alloc(sizeof(float) * (size_t)n * n)) return 1;
-        JX_HIP(hipMemcpy(dut.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-        if (drot.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    }
-    if (dg.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    if (dout.alloc(sizeof(double) * (size_t)kBlockRows * cols)) return 1;
-    for (int64_t r0 = 0; r0 < m_chunk; r0 += kBlockRows) {
-        const int rows = (int)std::min<int64_t>(kBlockRows, m_chunk - r0);
-        JX_HIP(hipMemcpy(dg.p, snp_chunk + (size_t)r0 * n, sizeof(float) * (size_t)rows * n, hipMemcpyHostToDevice));
-        const float *grot = dg.as<float>();
-        if (u_t) {
-            if (jxg_rotate_dense_f32(dg.as<float>(), rows, n, dut.as<float>(), drot.as<float>(), nullptr)) return 1;
-            grot = drot.as<float>();
-        }
-        if (jxg_lmm_scan(grot, rows, n, nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), p, low, high, tol,
-                         max_iter, 0, 0.0, has_nullml, nullml, dout.as<double>(), nullptr, nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)r0 * cols, dout.p, sizeof(double) * (size_t)rows * cols, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-extern "C" int jx_lmm2_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                             double high, const float *snp_chunk, int64_t m_chunk, const float *u_t, double nullml,
-                             int max_iter, double tol, double *out) {
-    if (low >= high) return fail("low must be < high");
-    if (!std::isfinite(nullml)) return fail("nullml must be finite");
-    if (m_chunk <= 0) return 0;
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    DevBuf dut, dg, drot, dout;
-    if (u_t) {
-        if (dut.alloc(sizeof(float) * (size_t)n * n)) return 1;
-        JX_HIP(hipMemcpy(dut.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-        if (drot.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    }
-    if (dg.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    if (dout.alloc(sizeof(double) * (size_t)kBlockRows * 6)) return 1;
-    for (int64_t r0 = 0; r0 < m_chunk; r0 += kBlockRows) {
-        const int rows = (int)std::min<int64_t>(kBlockRows, m_chunk - r0);
-        JX_HIP(hipMemcpy(dg.p, snp_chunk + (size_t)r0 * n, sizeof(float) * (size_t)rows * n, hipMemcpyHostToDevice));
-        const float *grot = dg.as<float>();
-        if (u_t) {
-            if (jxg_rotate_dense_f32(dg.as<float>(), rows, n, dut.as<float>(), drot.as<float>(), nullptr)) return 1;
-            grot = drot.as<float>();
-        }
-        if (jxg_lmm2_scan(grot, rows, n, nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), p, low, high, tol,
-                          max_iter, 0, 0.0, nullml, dout.as<double>(), nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)r0 * 6, dout.p, sizeof(double) * (size_t)rows * 6, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-extern "C" int jx_lmm2_null_ml(const double *s, const double *xcov, const double *y_rot, int n, int p, double low,
-                               double high, int max_iter, double tol, int has_init, double init, double *out2) {
-    if (low >= high) return fail("low must be < high");
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    DevBuf o;
-    if (o.alloc(2 * sizeof(double))) return 1;
-    if (jxg_lmm2_null_ml(nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), n, p, low, high, max_iter, tol,
-                         has_init, init, o.as<double>(), nullptr))
-        return 1;
-    JX_HIP(hipMemcpy(out2, o.p, 2 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-namespace {
-struct FvDev {
-    DevBuf w, py, wx;
-    std::vector<double> a_chol;
-    double sc[3];
-    int prepare(const NullDev &nd, int n, int p, double lbd) {
-        if (w.alloc(sizeof(float) * (size_t)n) || py.alloc(sizeof(float) * (size_t)n) ||
-            wx.alloc(sizeof(float) * (size_t)n * p))
-            return 1;
-        a_chol.assign((size_t)p * p, 0.0);
-        return jxg_fvlmm_prepare(nd.s.as<double>(), nd.x.as<double>(), nd.y.as<double>(), n, p, lbd, w.as<float>(),
-                                 py.as<float>(), wx.as<float>(), a_chol.data(), sc);
-    }
-};
-}  // namespace
-
-extern "C" int jx_fvlmm_assoc_chunk(const double *s, const double *xcov, const double *y_rot, int n, int p,
-                                    double log10_lbd, const float *snp_chunk, int64_t m_chunk, const float *u_t,
-                                    int has_nullml, double nullml, double *out) {
-    if (m_chunk <= 0) return 0;
-    const int cols = has_nullml ? 4 : 3;
-    NullDev nd;
-    if (nd.upload(s, xcov, y_rot, n, p)) return 1;
-    FvDev fv;
-    if (fv.prepare(nd, n, p, pow(10.0, log10_lbd))) return 1;
-    DevBuf dut, dg, drot, dout;
-    if (u_t) {
-        if (dut.alloc(sizeof(float) * (size_t)n * n)) return 1;
-        JX_HIP(hipMemcpy(dut.p, u_t, sizeof(float) * (size_t)n * n, hipMemcpyHostToDevice));
-        if (drot.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    }
-    if (dg.alloc(sizeof(float) * (size_t)kBlockRows * n)) return 1;
-    if (dout.alloc(sizeof(double) * (size_t)kBlockRows * cols)) return 1;
-    for (int64_t r0 = 0; r0 < m_chunk; r0 += kBlockRows) {
-        const int rows = (int)std::min<int64_t>(kBlockRows, m_chunk - r0);
-        JX_HIP(hipMemcpy(dg.p, snp_chunk + (size_t)r0 * n, sizeof(float) * (size_t)rows * n, hipMemcpyHostToDevice));
-        const float *grot = dg.as<float>();
-        if (u_t) {
-            if (jxg_rotate_dense_f32(dg.as<float>(), rows, n, dut.as<float>(), drot.as<float>(), nullptr)) return 1;
-            grot = drot.as<float>();
-        }
-        if (jxg_fvlmm_scan(grot, rows, n, p, fv.w.as<float>(), fv.py.as<float>(), fv.wx.as<float>(), fv.a_chol.data(),
-                           fv.sc[0], (int)fv.sc[2], has_nullml, nullml, fv.sc[1], dout.as<double>(), nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)r0 * cols, dout.p, sizeof(double) * (size_t)rows * cols, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
 // lm_block_assoc_packed (src/stats/glm.rs:3550-3860): the plain LM scan the mixed-model routes fall back to
 // ---------------------------------------------------------------------------------------------------
-extern "C" int jxg_lm_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const int32_t *d_rows, int nrows,
-                               const float *d_lut, const double *d_xr, int q0, const double *d_ixx, double yy_r,
-                               double *d_work, double *d_out, void *stream);
-
-// Host half shared with the resident-panel route (janusx_amd/pipeline.py): r_y = y - X (C X'y), y'M_X y, and [X | r_y]
+// Host half of the packed and the dense LM scan (janusx_amd/pipeline.py): r_y = y - X (C X'y), y'M_X y, and [X | r_y]
 // rounded through f32 (glm.rs:3635-3672).  xr_out (n, q0 + 1).
 extern "C" int jx_lm_residualize(const double *y, const double *x, const double *ixx, int n, int q0, double *xr_out,
                                  double *yy_r_out) {
@@ -970,32 +745,6 @@ extern "C" int jx_lm_residualize(const double *y, const double *x, const double 
         xr_out[(size_t)i * ld + q0] = (double)(float)resid;
     }
     *yy_r_out = yy;
-    return 0;
-}
-
-// `lm_block_assoc_f32` (src/stats/glm.rs:4313-4497): dense SNP-major f32 rows on the host, blocks staged to the device.
-extern "C" int jx_lm_assoc_dense(const double *y, const double *x, const double *ixx, int q0, const float *g, int64_t m, int n,
-                                 double *out) {
-    if (m <= 0) return 0;
-    std::vector<double> xr((size_t)n * (q0 + 1));
-    double yy_r = 0.0;
-    if (jx_lm_residualize(y, x, ixx, n, q0, xr.data(), &yy_r)) return 1;
-    DevBuf dxr, dixx, dwork, dout, dg;
-    if (dxr.alloc(xr.size() * sizeof(double)) || dixx.alloc(sizeof(double) * (size_t)std::max(q0 * q0, 1))) return 1;
-    JX_HIP(hipMemcpy(dxr.p, xr.data(), xr.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (q0 > 0) JX_HIP(hipMemcpy(dixx.p, ixx, sizeof(double) * (size_t)q0 * q0, hipMemcpyHostToDevice));
-    const int64_t brows = std::max<int64_t>(1, std::min<int64_t>(m, ((int64_t)1 << 30) / ((int64_t)n * 4)));   // <= 1 GiB of rows
-    if (dg.alloc(sizeof(float) * (size_t)brows * n) || dwork.alloc(sizeof(double) * (size_t)brows * (q0 + 2)) ||
-        dout.alloc(sizeof(double) * (size_t)brows * 4))
-        return 1;
-    for (int64_t r0 = 0; r0 < m; r0 += brows) {
-        const int rows = (int)std::min<int64_t>(brows, m - r0);
-        JX_HIP(hipMemcpy(dg.p, g + (size_t)r0 * n, sizeof(float) * (size_t)rows * n, hipMemcpyHostToDevice));
-        if (jxg_lm_scan_dense(dg.as<float>(), rows, n, n, dxr.as<double>(), q0, dixx.as<double>(), yy_r, dwork.as<double>(),
-                              dout.as<double>(), nullptr))
-            return 1;
-        JX_HIP(hipMemcpy(out + (size_t)r0 * 4, dout.p, sizeof(double) * (size_t)rows * 4, hipMemcpyDeviceToHost));
-    }
     return 0;
 }
 

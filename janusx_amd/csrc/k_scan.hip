@@ -942,32 +942,13 @@ extern "C" int jxg_fvlmm_scan_dev(const float *d_grot, int nrows, int n, int p, 
                                   const float *d_wx, const double *d_a_chol, double ypy, int df, int with_plrt,
                                   double nullml, double log_det_v, double *d_out, void *stream) {
     if (nrows <= 0) return 0;
-    if (p < 1 || p > JXG_MAX_COV) return fail("jxg_fvlmm_scan: p out of range");
+    if (p < 1 || p > JXG_MAX_COV) return fail("jxg_fvlmm_scan_dev: p out of range");
     int grid = (nrows + SCAN_WAVES - 1) / SCAN_WAVES;
     if (grid > 65536 * 8) grid = 65536 * 8;
     JX_DISPATCH_DIM(p, hipLaunchKernelGGL(fvlmm_scan_kernel<MAXD>, dim3(grid), dim3(SCAN_THREADS), 0,
                                           (hipStream_t)stream, d_grot, nrows, n, p, d_w, d_py, d_wx, d_a_chol, ypy, df,
                                           with_plrt, nullml, log_det_v, d_out, 0));
     JX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int jxg_fvlmm_scan(const float *d_grot, int nrows, int n, int p, const float *d_w, const float *d_py,
-                              const float *d_wx, const double *h_a_chol, double ypy, int df, int with_plrt,
-                              double nullml, double log_det_v, double *d_out, void *stream) {
-    if (nrows <= 0) return 0;
-    if (p < 1 || p > JXG_MAX_COV) return fail("jxg_fvlmm_scan: p out of range");
-    hipStream_t st = (hipStream_t)stream;
-    DevBuf a;
-    if (a.alloc(sizeof(double) * p * p)) return 1;
-    JX_HIP(hipMemcpyAsync(a.p, h_a_chol, sizeof(double) * p * p, hipMemcpyHostToDevice, st));
-    int grid = (nrows + SCAN_WAVES - 1) / SCAN_WAVES;
-    if (grid > 65536 * 8) grid = 65536 * 8;
-    JX_DISPATCH_DIM(p, hipLaunchKernelGGL(fvlmm_scan_kernel<MAXD>, dim3(grid), dim3(SCAN_THREADS), 0, st, d_grot,
-                                          nrows, n, p, d_w, d_py, d_wx, a.as<double>(), ypy, df, with_plrt, nullml,
-                                          log_det_v, d_out, 0));
-    JX_LAUNCH_CHECK();
-    JX_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -2191,11 +2191,20 @@ def rust_eigh_from_array_f64(a, threads=0, driver=None, jobz="V", require_lapack
     if a.ndim != 2 or a.shape[0] != a.shape[1]:
         raise RuntimeError("matrix must be square")
     n = int(a.shape[0])
+    if n == 0:
+        raise RuntimeError("matrix must be non-empty")
+    import torch
     t0 = time.perf_counter()
-    evals = np.empty(n, dtype=np.float64)
-    want = str(jobz).upper() != "N"
-    evecs = np.empty((n, n), dtype=np.float64) if want else None
-    check(lib().jx_eigh_f64(_p(a), n, float(diag_shift), _p(evals), _p(evecs)))
+    stream = torch.cuda.current_stream().cuda_stream
+    d_a = torch.tensor(a, device=torch.device("cuda", torch.cuda.current_device()))       # a copy: overwritten with U^T
+    d_w = torch.empty(n, dtype=torch.float64, device=d_a.device)
+    check(lib().jxg_symmetrize_f64(d_a.data_ptr(), n, stream))                             # eigh.rs:179
+    check(lib().jxg_eigh_f64(d_a.data_ptr(), n, float(diag_shift), d_w.data_ptr(), stream))
+    evals, evecs = d_w.cpu().numpy(), None
+    if str(jobz).upper() != "N":
+        d_u = torch.empty_like(d_a)
+        check(lib().jxg_transpose_f64(d_a.data_ptr(), d_u.data_ptr(), n, stream))          # U^T -> U (columns = vectors)
+        evecs = d_u.cpu().numpy()
     # which solver ran (csrc/eigh.cpp): rocSOLVER below n = 256 or on request, else the own one- or two-stage reduction
     # + own divide and conquer (jxg_last_kernel_ms(10) = 1 after a two-stage decomposition)
     if n < 256 or os.environ.get("JXGPU_EIGH", "") == "rocsolver":
@@ -2341,10 +2350,16 @@ def lmm_rotate_x_y_with_ut_f64(u_t, x, y, threads=0):
         raise RuntimeError(f"x rows must equal len(y): rows={x.shape[0]}, len(y)={n}")
     u_t = _assoc_u_t(u_t, n, "u_t must be shape (n, n) and row-major U^T")
     q = int(x.shape[1])
-    ox = np.empty((n, q), dtype=np.float64)
-    oy = np.empty((n, 1), dtype=np.float64)
-    check(lib().jx_lmm_rotate_x_y_with_ut_f64(_p(u_t), n, _p(x), q, _p(y), _p(ox), _p(oy)))
-    return ox, oy
+    if q > 15:
+        raise RuntimeError("x must have between 0 and 15 columns")
+    import torch
+    d_ut = torch.tensor(u_t, device=torch.device("cuda", torch.cuda.current_device()))
+    d_xy = torch.from_numpy(np.concatenate([x, y[:, None]], axis=1)).to(d_ut.device)     # [X | y] side by side
+    d_out = torch.empty_like(d_xy)
+    check(lib().jxg_rotate_xy(d_ut.data_ptr(), n, d_xy.data_ptr(), q + 1, d_out.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream))
+    out = d_out.cpu().numpy()
+    return np.ascontiguousarray(out[:, :q]), np.ascontiguousarray(out[:, q:])
 
 
 def lmm_rotate_y_with_ut_f64(u_t, y, threads=0):
@@ -2358,11 +2373,7 @@ def lmm_rotate_y_with_ut_f64(u_t, y, threads=0):
     if u_t.ndim != 2:
         raise RuntimeError("u_t must be 2D (n, n)")
     u_t = _assoc_u_t(u_t, n, "u_t must be shape (n, n) and row-major U^T")
-    x = np.zeros((n, 1), dtype=np.float64)
-    ox = np.empty((n, 1), dtype=np.float64)
-    oy = np.empty((n, 1), dtype=np.float64)
-    check(lib().jx_lmm_rotate_x_y_with_ut_f64(_p(u_t), n, _p(x), 1, _p(y), _p(ox), _p(oy)))
-    return oy.ravel()
+    return lmm_rotate_x_y_with_ut_f64(u_t, np.zeros((n, 1), dtype=np.float64), y)[1].ravel()      # beside one zero column
 
 
 def _null_args(s, xcov, y_rot):
@@ -2379,33 +2390,38 @@ def _null_args(s, xcov, y_rot):
 
 def lmm_reml_null_f32(s, xcov, y_rot, low, high, max_iter=50, tol=1e-2):
     """src/stats/reml.rs:570-616 -> (lbd, ml, reml)."""
-    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
+    s, xcov, y, _n, _p_cov = _null_args(s, xcov, y_rot)
     _assoc_check_bounds(low, high)
-    out = np.zeros(3, dtype=np.float64)
-    check(lib().jx_lmm_reml_null(_p(s), _p(xcov), _p(y), n, p, float(low), float(high), int(max_iter), float(tol),
-                                 _p(out)))
-    return float(out[0]), float(out[1]), float(out[2])
+    return _dense_model(s, xcov, y).reml_null(low, high, max_iter, tol)
 
 
 def ml_loglike_null_f32(s, xcov, y_rot, log10_lbd):
     """src/stats/reml.rs:618-646 -> ML profile log-likelihood of the null model at log10 lambda (-1e8 on failure)."""
-    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    out = np.zeros(1, dtype=np.float64)
-    check(lib().jx_ml_loglike_null(_p(s), _p(xcov), _p(y), n, p, float(log10_lbd), _p(out)))
-    return float(out[0])
+    return _loglike_null(s, xcov, y_rot, log10_lbd)[0]
 
 
 def _loglike_null(s, xcov, y_rot, log10_lbd):
     """(ml, reml) of the null model at log10 lambda, one device launch (jxg_lmm_loglike_null)."""
+    s, xcov, y, _n, _p_cov = _null_args(s, xcov, y_rot)
+    return _dense_model(s, xcov, y).loglike_null(log10_lbd)
+
+
+def _dense_model(s, xcov, y, u_t=None):
+    """The caller's rotated null model (checked host arrays) on the current device: `pipeline.SpectralModel.rotated`; torch is
+    imported here, behind every argument check."""
     import torch
-    s, xcov, y, n, p = _null_args(s, xcov, y_rot)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    ds, dx, dy = (torch.from_numpy(a).to(dev) for a in (s, xcov, y))
-    o = torch.empty(2, dtype=torch.float64, device=dev)
-    check(lib().jxg_lmm_loglike_null(ds.data_ptr(), dx.data_ptr(), dy.data_ptr(), n, p, float(log10_lbd),
-                                     o.data_ptr(), torch.cuda.current_stream().cuda_stream))
-    h = o.cpu().numpy()
-    return float(h[0]), float(h[1])
+    from . import pipeline as pl
+    return pl.SpectralModel.rotated(s, u_t, xcov, y, torch.device("cuda", torch.cuda.current_device()))
+
+
+def _scan_dense_chunk(g, s, xcov, y, u_t, mode, cols, **opts):
+    """The dense-chunk scans of the mirror: `pipeline.scan_dense_rows` over the checked chunk `g` (m, n) f32 with the caller's
+    rotated null model (u_t None: rows rotated already), in blocks of 4096 rows -> f64 (m, cols).  An empty chunk returns before
+    the device is touched."""
+    if g.shape[0] == 0:
+        return np.zeros((0, cols), dtype=np.float64)
+    from . import pipeline as pl
+    return pl.scan_dense_rows(g, _dense_model(s, xcov, y, u_t), mode, **opts).cpu().numpy()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2415,13 +2431,8 @@ def _loglike_null(s, xcov, y_rot, log10_lbd):
 def _chunk(s, xcov, y_rot, low, high, chunk, u_t, max_iter, tol, nullml, what):
     s, xcov, y, n, p, g, u_t = _assoc_chunk_args(s, xcov, y_rot, chunk, u_t, what)
     _assoc_check_bounds(low, high)
-    m = int(g.shape[0])
-    cols = 4 if nullml is not None else 3
-    out = np.zeros((m, cols), dtype=np.float64)
-    check(lib().jx_lmm_reml_chunk(_p(s), _p(xcov), _p(y), n, p, float(low), float(high), _p(g), m, _p(u_t),
-                                  int(max_iter), float(tol), 1 if nullml is not None else 0,
-                                  float(nullml if nullml is not None else 0.0), _p(out)))
-    return out
+    return _scan_dense_chunk(g, s, xcov, y, u_t, "lmm", 4 if nullml is not None else 3, low=low, high=high, max_iter=max_iter,
+                             tol=tol, nullml=nullml)
 
 
 def lmm_reml_chunk_f32(s, xcov, y_rot, low, high, g_rot_chunk, max_iter=50, tol=1e-2, threads=0, nullml=None):
@@ -2545,12 +2556,8 @@ def lmm_reml_assoc_packed_f32(packed, n_samples, row_flip, row_maf, s, xcov, y_r
 
 def _fv_chunk(s, xcov, y_rot, log10_lbd, chunk, u_t, nullml, what):
     s, xcov, y, n, p, g, u_t = _assoc_chunk_args(s, xcov, y_rot, chunk, u_t, what)
-    m = int(g.shape[0])
-    out = np.zeros((m, 4 if nullml is not None else 3), dtype=np.float64)
-    check(lib().jx_fvlmm_assoc_chunk(_p(s), _p(xcov), _p(y), n, p, float(log10_lbd), _p(g), m, _p(u_t),
-                                     1 if nullml is not None else 0, float(nullml if nullml is not None else 0.0),
-                                     _p(out)))
-    return out
+    return _scan_dense_chunk(g, s, xcov, y, u_t, "fvlmm", 4 if nullml is not None else 3, log10_lbd=float(log10_lbd),
+                             nullml=nullml)
 
 
 def fvlmm_assoc_chunk_f32(s, xcov, y_rot, log10_lbd, g_rot_chunk, threads=0, nullml=None):
@@ -3089,11 +3096,7 @@ def lmm_reml_lmm2_chunk_from_snp_f32(s, xcov, y_rot, low, high, snp_chunk, u_t, 
     _assoc_check_bounds(low, high)
     if not np.isfinite(nullml):
         raise RuntimeError("nullml must be finite")
-    m = int(g.shape[0])
-    out = np.zeros((m, 6), dtype=np.float64)
-    check(lib().jx_lmm2_chunk(_p(s), _p(xcov), _p(y), n, p, float(low), float(high), _p(g), m, _p(u_t), float(nullml),
-                              int(max_iter), float(tol), _p(out)))
-    return out
+    return _scan_dense_chunk(g, s, xcov, y, u_t, "lmm2", 6, low=low, high=high, max_iter=max_iter, tol=tol, nullml=nullml)
 
 
 def lmm_reml_lmm2_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr,
@@ -3113,14 +3116,9 @@ def lmm_reml_lmm2_assoc_bed_to_tsv_f32(bed_prefix, out_tsv, s, xcov, y_rot, u_t,
             raise RuntimeError("nullml must be finite when provided")
         nullml_val = float(nullml)
     else:
-        s_, xcov_, y_, n, p = _null_args(s, xcov, y_rot)
+        s_, xcov_, y_, _n, _p_cov = _null_args(s, xcov, y_rot)
         init = init_log10_lbd_ml if init_log10_lbd_ml is not None else init_log10_lbd_reml
-        o2 = np.zeros(2, dtype=np.float64)
-        check(lib().jx_lmm2_null_ml(_p(s_), _p(xcov_), _p(y_), n, p, float(low), float(high), int(max_iter), float(tol),
-                                    1 if init is not None else 0, float(init if init is not None else 0.0), _p(o2)))
-        nullml_val = float(o2[1])
-        if not np.isfinite(nullml_val):
-            raise RuntimeError("failed to optimize null ML for LMM2 unified scan")
+        nullml_val = _dense_model(s_, xcov_, y_).null_ml(max_iter, tol, (low, high), init)[1]
     init_scan = init_log10_lbd_reml if init_log10_lbd_reml is not None else init_log10_lbd_ml
     return _bed_scan_to_tsv(bed_prefix, out_tsv, s, xcov, y_rot, u_t, maf_thr, miss_thr, het_thr, genetic_model,
                             snps_only, sample_ids, row_indices, row_flip, row_missing, row_maf, "lmm2", nullml_val,
@@ -3413,10 +3411,10 @@ def lm_block_assoc_f32(y, x, ixx, g, chunk_size=10000, threads=0):
     g = _assoc_dense_chunk(g, n, "g must be shape (m, n)")
     if n <= q0 + 1:
         raise RuntimeError(f"n too small: require n > q0+1, got n={n}, q0={q0}")
-    m = int(g.shape[0])
-    out = np.zeros((m, 4), dtype=np.float64)
-    check(lib().jx_lm_assoc_dense(_p(y), _p(x), _p(ixx), q0, _p(g), m, n, _p(out)))
-    return out
+    if g.shape[0] == 0:
+        return np.zeros((0, 4), dtype=np.float64)
+    from . import pipeline as pl
+    return pl.scan_rows_lm_dense(g, x, y, ixx).cpu().numpy()
 
 
 def lm_block_assoc_packed_to_tsv(y, x, ixx, packed, n_samples, row_flip, row_maf, row_missing, chrom, pos, snp, allele0,

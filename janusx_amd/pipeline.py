@@ -15,6 +15,7 @@ import copy
 import math
 import os
 import time
+import warnings
 from collections import namedtuple
 from dataclasses import dataclass, field
 
@@ -385,17 +386,16 @@ class SpectralModel:
         if not fit_null:      # spectrum of a sparse (possibly indefinite) K: lambda comes from the sparse REML search
             self.null = None
             return
-        out3 = torch.empty(3, dtype=torch.float64, device=dev)
-        check(lib().jxg_lmm_reml_null(_ptr(self.S), _ptr(self.xcov), _ptr(self.y), n, p, -5.0, 5.0, 50, 1e-3,
-                                      _ptr(out3), _stream()))
-        lbd, ml0, reml0 = [float(v) for v in out3.cpu().numpy()]
-        self.null = self._profile(lbd, ml0, reml0)
+        self.null = self._profile(*self.reml_null())
 
     @classmethod
     def rotated(cls, s, u_t, xcov, y, device):
-        """A model from what a caller has rotated already (the mirror's packed entry points): s (n) f64, u_t (n, n) f32 row-major
-        U^T kept as given, X~ (n, p) and y~ (n) f64, host arrays or torch tensors.  No rotation and no null fit (null = None)."""
+        """A model from what a caller has rotated already (the mirror's packed and dense-chunk entry points): s (n) f64, u_t (n, n)
+        f32 row-major U^T kept as given (None: the rows to scan are rotated already), X~ (n, p) and y~ (n) f64, host arrays or torch
+        tensors.  No rotation and no null fit (null = None)."""
         def dev(a, dtype):
+            if a is None:
+                return None
             if torch.is_tensor(a):           # parts that are on a device already
                 return a.to(device=device, dtype=torch.float64 if dtype == np.float64 else torch.float32).contiguous()
             a = np.ascontiguousarray(a, dtype=dtype)
@@ -438,13 +438,23 @@ class SpectralModel:
         for ti in range(nt):
             mdl = base if ti == 0 else copy.copy(base)
             mdl.y = base.y_rot[ti]
-            out3 = torch.empty(3, dtype=torch.float64, device=dev)
-            check(lib().jxg_lmm_reml_null(_ptr(mdl.S), _ptr(mdl.xcov), _ptr(mdl.y), n, p, -5.0, 5.0, 50, 1e-3, _ptr(out3),
-                                          _stream()))
-            lbd, ml0, reml0 = [float(v) for v in out3.cpu().numpy()]
-            mdl.null = mdl._profile(lbd, ml0, reml0)
+            mdl.null = mdl._profile(*mdl.reml_null())
             models.append(mdl)
         return models
+
+    def reml_null(self, low=-5.0, high=5.0, max_iter=50, tol=1e-3):
+        """-> (lambda0, ml0, reml0): Brent on -reml_loglike of the null model (`lmm_reml_null_f32`, src/stats/reml.rs:570-616)."""
+        out3 = torch.empty(3, dtype=torch.float64, device=self.S.device)
+        check(lib().jxg_lmm_reml_null(_ptr(self.S), _ptr(self.xcov), _ptr(self.y), self.n, self.p, float(low), float(high),
+                                      int(max_iter), float(tol), _ptr(out3), _stream()))
+        return tuple(float(v) for v in out3.cpu().numpy())
+
+    def loglike_null(self, log10_lbd):
+        """-> (ml, reml) of the null model at log10 lambda, -1e8 on failure (src/stats/reml.rs:255-470)."""
+        out2 = torch.empty(2, dtype=torch.float64, device=self.S.device)
+        check(lib().jxg_lmm_loglike_null(_ptr(self.S), _ptr(self.xcov), _ptr(self.y), self.n, self.p, float(log10_lbd),
+                                         _ptr(out2), _stream()))
+        return tuple(float(v) for v in out2.cpu().numpy())
 
     def _profile(self, lbd, ml0, reml0) -> NullFit:
         # assoc.py:907-951 `_lmm_profile_exact_vc` + :1845-1876 (host, O(n p^2))
@@ -518,11 +528,14 @@ class SpectralModel:
         lo_b, hi_b = self.null.bounds
         return min(max(math.log10(self.null.lbd), lo_b), hi_b) if self.null.lbd > 0 else None
 
-    def null_ml(self, max_iter, tol):
+    def null_ml(self, max_iter, tol, bounds=None, init=None):
         """-> (seed, null ML of the lmm2 scan): Brent on -ml_loglike, seeded with the REML optimum (src/stats/lmm.rs:2902-2921; the
-        workflow passes bounds, max_iter = 30, tol = 1e-2, init_log10_lbd_reml = log10 lambda0: workflow_model_stream.py:1499-1590)."""
+        workflow passes bounds, max_iter = 30, tol = 1e-2, init_log10_lbd_reml = log10 lambda0: workflow_model_stream.py:1499-1590).
+        bounds (low, high) and init: the caller's own (a model without a null fit); default: those of the null fit."""
         o2 = torch.empty(2, dtype=torch.float64, device=self.S.device)
-        (lo_b, hi_b), init = self.null.bounds, self.warm_seed()
+        if bounds is None:
+            bounds, init = self.null.bounds, self.warm_seed()
+        lo_b, hi_b = float(bounds[0]), float(bounds[1])
         check(lib().jxg_lmm2_null_ml(_ptr(self.S), _ptr(self.xcov), _ptr(self.y), self.n, self.p, lo_b, hi_b, int(max_iter),
                                      float(tol), 1 if init is not None else 0, float(init or 0.0), o2.data_ptr(), _stream()))
         ml0 = float(o2.cpu().numpy()[1])
@@ -581,6 +594,7 @@ class _Fp16Rotation:
     """What the two rotation stages share: rows and LUT records of a call on the device, and the fp16 hi / lo launches over the
     `parts` (offset, nb, hi, lo, panel) of an eigenbasis -- one part for a dense basis, the diagonal blocks otherwise."""
     int8 = False
+    fused_ok = True        # `fused_sums` exists: `_fixed_lambda_scan` may take the sums instead of G~
 
     def _upload(self, rows, lut, dev):
         self.rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
@@ -624,6 +638,7 @@ class DenseRotation(_Fp16Rotation):
         if fixed_lambda and os.environ.get("JXGPU_FVLMM_FUSED", "1").strip() == "2" and _fused_fixed_lambda(model.p):
             use_q = False
         self.int8, self.qpl = use_q, (model.qplanes() if use_q else None)
+        self.fused_ok = not use_q
         # fp16 hi/lo LUT records (range-checked; rows without missing calls as integer LUT + offset, see jxg_lut_split_rows)
         self.rowoff = torch.empty(mk, dtype=torch.float32, device=dev)
         # rows with a few missing calls keep the exact (int8) rotation and get their missing-call term added behind it
@@ -714,6 +729,41 @@ class BlockDiagRotation(_Fp16Rotation):
         check(lib().jxg_lut_split(_ptr(lut_t), len(rows), _ptr(self.lut16), _stream()))
 
 
+class DenseRowsRotation:
+    """Rotation stage of DENSE SNP-major f32 rows `g` (m, n) on the host (the mirror's dense-chunk entry points): a block of
+    rows is copied to the device and rotated with the exact f32 kernel (`jxg_rotate_dense_f32`) by the `parts` (offset, nb, U^T f32
+    (nb, nb) on the device, sample positions of the part or None) of the eigenbasis -- one part for a dense basis, the diagonal
+    blocks otherwise; no parts: the rows are rotated already.  The staging buffers are allocated here, once."""
+    fused_ok = False       # G~ is always written
+    tiles = 0
+
+    def __init__(self, g: np.ndarray, parts, n: int, block_rows: int, dev):
+        self.n, self.parts = int(n), list(parts)
+        with warnings.catch_warnings():      # a read-only array is only ever read through this tensor
+            warnings.simplefilter("ignore", UserWarning)
+            self.g = torch.from_numpy(g)
+        br = int(block_rows)
+        self.whole = len(self.parts) == 1 and self.parts[0][3] is None and self.parts[0][1] == self.n
+        self.gb = torch.empty((br, self.n), dtype=torch.float32, device=dev) if self.parts else None
+        # (rows of the part's samples, their rotation) per part of a split basis
+        self.sub = [] if self.whole else [tuple(torch.empty((br, nb), dtype=torch.float32, device=dev) for _ in range(2))
+                                          for _off, nb, _ut, _cols in self.parts]
+
+    def rotate(self, grot, r0, nr):
+        """G~ of the rows [r0, r0 + nr) -> grot (>= nr, n) f32."""
+        (self.gb if self.parts else grot)[:nr].copy_(self.g[r0:r0 + nr])
+        if self.whole:
+            check(lib().jxg_rotate_dense_f32(_ptr(self.gb), nr, self.n, _ptr(self.parts[0][2]), _ptr(grot), _stream()))
+            return
+        for (off, nb, ut32, cols), (sub, rb) in zip(self.parts, self.sub):
+            if cols is None:
+                sub[:nr].copy_(self.gb[:nr, off:off + nb])
+            else:
+                torch.index_select(self.gb[:nr], 1, cols, out=sub[:nr])
+            check(lib().jxg_rotate_dense_f32(_ptr(sub), nr, nb, _ptr(ut32), _ptr(rb), _stream()))
+            grot[:nr, off:off + nb] = rb[:nr]
+
+
 # What `_run_blocks` drives: a rotation stage, scan(buf, r0, nr) writing the rows [r0, r0 + nr) of the table from their block
 # buffer, whole_table (`on_block` gets the table once at the end) and fused = (w, py, wx, p) where that buffer holds the sums, not G~.
 _Scanner = namedtuple("_Scanner", "stage scan whole_table fused", defaults=(False, None))
@@ -786,12 +836,13 @@ def _lmm2_scan(stage, model, out, brent, max_iter, tol, nullml):
 
 
 def _fixed_lambda_scan(stage, p, out, w, py, wx, a_chol, ypy, df, score, with_plrt=0, nullml=0.0, log_det_v=0.0):
-    """'fvlmm' / 'splmm' over a rotation stage of either basis.  Where the stage runs the fp16 kernel and `_fused_fixed_lambda`
-    allows it `jxg_fvlmm_finish_dev` finishes the fused sums; else `jxg_fvlmm_scan_dev` / `jxg_splmm_exact_scan_dev` read G~.
+    """'fvlmm' / 'splmm' over any rotation stage.  Where the stage has the fused form (`fused_ok`: the fp16 kernel) and
+    `_fused_fixed_lambda` allows it `jxg_fvlmm_finish_dev` finishes the fused sums; else `jxg_fvlmm_scan_dev` /
+    `jxg_splmm_exact_scan_dev` read G~.
     score: the SparseLMM exact scan -- score-form test with the null sigma2 = yPy / (n - p) (src/stats/splmm.rs:2567-2880)."""
     n = stage.n
     a_dev = torch.from_numpy(np.ascontiguousarray(a_chol, dtype=np.float64)).to(out.device)
-    if _fused_fixed_lambda(p) and not stage.int8:
+    if _fused_fixed_lambda(p) and stage.fused_ok:
         def finish(sums, r0, nr):
             check(lib().jxg_fvlmm_finish_dev(_ptr(sums), stage.tiles, p + 2, nr, n, p, _ptr(a_dev), ypy, df, with_plrt, nullml,
                                              log_det_v, 1 if score else 0, out[r0:].data_ptr(), _stream()))
@@ -815,9 +866,10 @@ def _splmm_scan(stage, p, out, fv_state):
 
 
 def _run_blocks(scanner, out, br, nbuf=1, times: StageTimes = None, on_block=None, progress=None, progress_every=0):
-    """The block loop of the packed scans: rotate block b into one of `nbuf` buffers, scan it; stage times from events,
-    `on_block` on a copy stream one block behind, `progress`.  Only launches, no allocation and no host sync per block (the
-    chain forms upload the offsets of the chains that touch a block or super-block: `_chain_segments`)."""
+    """The block loop of the packed and the dense-row scans: rotate block b into one of `nbuf` buffers, scan it; stage times from
+    events, `on_block` on a copy stream one block behind, `progress`.  Only launches, no allocation and no host sync per block (the
+    chain forms upload the offsets of the chains that touch a block or super-block: `_chain_segments`; the dense-row stage uploads
+    the block's rows)."""
     stage, scan, whole_table, fused = scanner
     mk = int(out.shape[0])
     rotate = stage.rotate if fused is None else (lambda buf, r0, nr: stage.fused_sums(buf, r0, nr, *fused))
@@ -1034,31 +1086,42 @@ def scan_rows_splmm_blocks(rot: BlockRotation, p: int, rows: np.ndarray, lut: np
     return out
 
 
+_Dims = namedtuple("_Dims", "n p")     # what the 'splmm' scan reads of a model: its null state arrives as `fv_state`
+
+
+def scan_dense_rows(g: np.ndarray, model, mode, parts=None, low=None, high=None, max_iter=30, tol=1e-2, log10_lbd=None,
+                    nullml=None, fv_state=None, dev=None, block_rows=4096):
+    """`scan_rows` for DENSE SNP-major f32 rows `g` (m, n) on the host (the mirror's dense-chunk entry points): the same scanners
+    and block loop over a `DenseRowsRotation`.  mode: 'lmm' (exact per-SNP REML on [low, high], no chains, no warm start), 'lmm2'
+    (needs `nullml`), 'fvlmm' (fixed lambda at `log10_lbd`) or 'splmm' (`fv_state` as `scan_rows`).  parts: see `DenseRowsRotation`;
+    None = `model.ut` as one part, or no rotation where the model has none.  -> (m, 3 | 4 with nullml | 6 for 'lmm2') f64 on the
+    device."""
+    dev = model.S.device if dev is None else dev
+    m, n, p = int(g.shape[0]), model.n, model.p
+    if parts is None:
+        parts = [] if model.ut is None else [(0, n, model.ut, None)]
+    with_plrt, nullml_v = (1, float(nullml)) if nullml is not None else (0, 0.0)
+    out = torch.empty((m, 6 if mode == "lmm2" else 3 + with_plrt), dtype=torch.float64, device=dev)
+    br = int(max(1, min(block_rows, m)))
+    stage = DenseRowsRotation(g, parts, n, br, dev)
+    if mode == "lmm":
+        scanner = _exact_scan(stage, model, out, None, br, (float(low), float(high), 0, 0.0), max_iter, tol, nullml, None)
+    elif mode == "lmm2":
+        scanner = _lmm2_scan(stage, model, out, (float(low), float(high), 0, 0.0), max_iter, tol, nullml)
+    elif mode == "splmm":
+        scanner = _splmm_scan(stage, p, out, fv_state)
+    else:
+        _lbd, w, py, wx, a_chol, ypy, log_det_v, df = model.fv_cache(log10_lbd)
+        scanner = _fixed_lambda_scan(stage, p, out, w, py, wx, a_chol, ypy, df, False, with_plrt, nullml_v, log_det_v)
+    _run_blocks(scanner, out, br)
+    return out
+
+
 def scan_rows_splmm_dense(g: np.ndarray, parts, n: int, p: int, fv_state, dev, block_rows=8192):
     """SparseLMM exact scan of DENSE f32 rows `g` (m, n) on the host (`splmm_assoc_pcg_dense_f32`, src/stats/splmm.rs:5464-5650):
-    blocks of rows are staged to the device, rotated by the eigenbasis (`parts`: (offset, nb, U' (nb, nb) f32, sample positions of
-    the block or None for the identity) -- one part for a dense decomposition, the diagonal blocks otherwise) with the f32
-    rotation kernel and scanned (`jxg_splmm_exact_scan_dev`).  -> (m, 3) f64 on the device."""
-    m = int(g.shape[0])
-    out = torch.empty((m, 3), dtype=torch.float64, device=dev)
-    w, py, wx, a_chol, ypy = fv_state
-    a_dev = torch.from_numpy(np.ascontiguousarray(a_chol, dtype=np.float64)).to(dev)
-    br = int(max(1, min(block_rows, m)))
-    grot = torch.empty((br, n), dtype=torch.float32, device=dev)
-    for r0 in range(0, m, br):
-        nr = min(br, m - r0)
-        gb = torch.from_numpy(g[r0:r0 + nr]).to(dev)
-        for off, nb, ut32, cols in parts:
-            if cols is None and nb == n:
-                check(lib().jxg_rotate_dense_f32(_ptr(gb), nr, n, _ptr(ut32), _ptr(grot), _stream()))
-            else:
-                sub = gb[:, cols].contiguous()
-                rb = torch.empty((nr, nb), dtype=torch.float32, device=dev)
-                check(lib().jxg_rotate_dense_f32(_ptr(sub), nr, nb, _ptr(ut32), _ptr(rb), _stream()))
-                grot[:nr, off:off + nb] = rb
-        check(lib().jxg_splmm_exact_scan_dev(_ptr(grot), nr, n, p, _ptr(w), _ptr(py), _ptr(wx), _ptr(a_dev), ypy, n - p,
-                                             out[r0:].data_ptr(), _stream()))
-    return out
+    `scan_dense_rows` with the eigenbasis of the sparse K as `parts` -- one part for a dense decomposition, the diagonal blocks
+    otherwise -- and `jxg_splmm_exact_scan_dev` behind it.  -> (m, 3) f64 on the device."""
+    return scan_dense_rows(g, _Dims(n, p), "splmm", parts, fv_state=fv_state, dev=dev, block_rows=block_rows)
 
 
 def scan_rows_splmm_factor(rows_f32, m: int, n: int, p: int, csr, diag: np.ndarray, lam: float, vinv_x: np.ndarray,
@@ -1145,6 +1208,36 @@ def scan_rows_grammar(panel: Panel, rows: np.ndarray, lut: np.ndarray, x: np.nda
     return out
 
 
+def _lm_residualized(x, y, ixx, dev):
+    """Host half of the LM scans (`jx_lm_residualize`; `ixx` None: (X'X)^-1 from `x`) -> ([X | r_y] rounded through f32
+    (n, q0 + 1) f64 and (X'X)^-1 on the device, y'M_X y)."""
+    from .janusx import lm_precompute_ixx_qr
+    n, q0 = x.shape
+    ixx = lm_precompute_ixx_qr(x) if ixx is None else np.ascontiguousarray(ixx, dtype=np.float64)
+    xr = np.empty((n, q0 + 1), dtype=np.float64)
+    yy = np.zeros(1, dtype=np.float64)
+    check(lib().jx_lm_residualize(y.ctypes.data, x.ctypes.data, ixx.ctypes.data, n, q0, xr.ctypes.data, yy.ctypes.data))
+    return torch.from_numpy(xr).to(dev), torch.from_numpy(ixx).to(dev), float(yy[0])
+
+
+def scan_rows_lm_dense(g: np.ndarray, x: np.ndarray, y: np.ndarray, ixx=None, dev=None, block_rows=None):
+    """`scan_rows_lm` for DENSE SNP-major f32 rows `g` (m, n) on the host (`lm_block_assoc_f32`, src/stats/glm.rs:4313-4497): per
+    block of rows an upload and `jxg_lm_scan_dense`, in the block loop of the other scans.  x (n, q0) with the intercept and
+    y (n): contiguous f64.  block_rows: None = at most 1 GiB of rows.  -> (m, 4) f64 device tensor [beta, se, pwald, plrt]."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    (m, n), q0 = g.shape, int(x.shape[1])
+    br = max(1, min(m, 2 ** 30 // (4 * n))) if block_rows is None else max(1, min(m, int(block_rows)))
+    xr_t, ixx_t, yy = _lm_residualized(x, y, ixx, dev)
+    out = torch.empty((m, 4), dtype=torch.float64, device=dev)
+    work = torch.empty(br * (q0 + 2), dtype=torch.float64, device=dev)
+
+    def scan(gb, r0, nr):
+        check(lib().jxg_lm_scan_dense(_ptr(gb), nr, n, n, _ptr(xr_t), q0, _ptr(ixx_t), yy, _ptr(work), out[r0:].data_ptr(),
+                                      _stream()))
+    _run_blocks(_Scanner(DenseRowsRotation(g, [], n, br, dev), scan), out, br)       # no parts: the stage only uploads
+    return out
+
+
 def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, y: np.ndarray, on_block=None, flip=None,
                  ixx=None, progress=None, progress_every=0):
     """Plain LM scan of the given SNP rows of a resident panel (`lm_block_assoc_packed`, src/stats/glm.rs:3550-3860; the `LM`
@@ -1152,7 +1245,6 @@ def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, 
     ([0, mean, 1, 2], or [2, mean, 1, 0] where `flip`), `x` includes the intercept, `ixx` = (X'X)^-1 (default: from `x`).
     One launch per LM_BLOCK_ROWS rows; `progress(done, total)` as in `scan_rows`.  Returns a (len(rows), 4) f64 device tensor
     [beta, se, pwald (Student t), plrt]."""
-    from .janusx import lm_precompute_ixx_qr
     dev = panel.device
     n = panel.n
     y = np.ascontiguousarray(y, dtype=np.float64).ravel()
@@ -1164,25 +1256,20 @@ def scan_rows_lm(panel: Panel, rows: np.ndarray, af: np.ndarray, x: np.ndarray, 
     out = torch.empty((mk, 4), dtype=torch.float64, device=dev)
     if mk == 0:
         return out
-    ixx = lm_precompute_ixx_qr(x) if ixx is None else np.ascontiguousarray(ixx, dtype=np.float64)
-    xr = np.empty((n, q0 + 1), dtype=np.float64)
-    yy = np.zeros(1, dtype=np.float64)
-    check(lib().jx_lm_residualize(y.ctypes.data, x.ctypes.data, ixx.ctypes.data, n, q0, xr.ctypes.data, yy.ctypes.data))
+    xr_t, ixx_t, yy = _lm_residualized(x, y, ixx, dev)
     mean_g = np.clip(np.float32(2.0) * np.asarray(af, dtype=np.float32), np.float32(0.0), np.float32(2.0))
     fl = np.zeros(mk, dtype=bool) if flip is None else np.asarray(flip, dtype=bool)
     lut = np.zeros((mk, 4), dtype=np.float32)
     lut[:, 0], lut[:, 1], lut[:, 2], lut[:, 3] = np.where(fl, 2.0, 0.0), mean_g, 1.0, np.where(fl, 0.0, 2.0)
     rows_t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
     lut_t = torch.from_numpy(lut).to(dev)
-    xr_t = torch.from_numpy(xr).to(dev)
-    ixx_t = torch.from_numpy(ixx).to(dev)
     br = min(LM_BLOCK_ROWS, mk)
     step, last_tick = (int(progress_every) if progress_every and int(progress_every) > 0 else br), 0
     work = torch.empty(br * (q0 + 2), dtype=torch.float64, device=dev)
     for r0 in range(0, mk, br):
         nr = min(br, mk - r0)
         check(lib().jxg_lm_scan_p32(_ptr(panel.p32), panel.m, n, rows_t[r0:].data_ptr(), nr, lut_t[r0:].data_ptr(), _ptr(xr_t),
-                                    q0, _ptr(ixx_t), float(yy[0]), _ptr(work), out[r0:].data_ptr(), _stream()))
+                                    q0, _ptr(ixx_t), yy, _ptr(work), out[r0:].data_ptr(), _stream()))
         if progress is not None and (r0 + nr >= mk or r0 + nr >= last_tick + step):
             last_tick = r0 + nr
             progress(r0 + nr, mk)

@@ -390,6 +390,10 @@ TABLE = [
     (lm2(sample_ids=[7] + IDS[1:]), E, "sample id not found in FAM: 7"),
     (lm2(sample_ids=IDS + IDS[:1]), E, "sample_ids length mismatch: selected n=11 but len(y)=10"),
     (lm2(packed=PACKED, packed_n_samples=11), E, "packed_n_samples 11 != 10 samples of <prefix>.fam"),
+
+    # rows added later stand at the end: a row's number is part of its test id
+    (rot_xy(x=np.ones((N, 16))), E, "x must have between 0 and 15 columns"),
+    (rot_xy(x=np.ones((N, 16)), u_t=UT9), E, UT_SHAPE_MSG),
 ]
 
 
@@ -417,6 +421,10 @@ def test_an_empty_payload_returns_before_the_device():
         assert out.shape == (0, cols) and out.dtype == np.float64
     out = jx.lm_block_assoc_packed(YR, X2, IXX, none, N, FLIP[:0], MAF[:0])
     assert out.shape == (0, 4) and out.dtype == np.float64
+    for out, shape in ((jx.lmm_reml_chunk_f32(S, X2, YR, -5.0, 5.0, G[:0]), (0, 3)),
+                       (jx.fvlmm_assoc_chunk_f32(S, X2, YR, 0.0, G[:0]), (0, 3)),
+                       (jx.lm_block_assoc_f32(YR, X2, IXX, G[:0]), (0, 4))):
+        assert out.shape == shape and out.dtype == np.float64
     assert jx.fvlmm_assoc_chunk_from_snp_to_tsv_f32(S, X2, YR, 0.0, G[:0], UT9, [], [], [], [], [], [], []) == ([], 0)
 
 
