@@ -966,6 +966,24 @@ int jxg_pairscreen_scan_p32(const uint8_t *d_p32, int64_t m_total, int n, const 
                             int64_t capacity, int32_t *d_hit_i, int32_t *d_hit_j, int32_t *d_hit_v, int32_t *d_hit_n,
                             double *d_hit_stat, uint64_t *d_counts, void *stream);
 
+/* ---- Dense f64 Cholesky and the reductions of multi-kernel AI-REML (`jx reml`; csrc/k_potrf.hip).  Column-major device matrices; only
+ * the lower triangle of a symmetric matrix or a factor is read or written.
+ *   jxg_potrf_block      : the diagonal block size NB (64).
+ *   jxg_dpotrf_lower_f64 : A = L L' in place.  h_info[0] = 0, or the 1-based index of the first pivot that is not positive and finite
+ *                          (LAPACK's dpotrf rule); the call then still returns 0 and the lower triangle holds no usable factor.
+ *   jxg_dpotrs_lower_f64 : B (n x nrhs) <- (L L')^-1 B, any nrhs >= 0.
+ *   jxg_reml_combine_f64 : lower triangle of V (ld n) = theta[q] I + sum_j theta[j] K_j, d_kstack (q, n, n) of symmetric matrices,
+ *                          h_theta q + 1 host doubles; q <= 16, n <= 65535.
+ *   jxg_sym_dot_f64      : d_out[0] = sum_ij a_ij b_ij over the full symmetric matrices, read from the two lower triangles; sums in a
+ *                          fixed order (reproducible run to run).
+ *   jxg_potrf_logdet_f64 : h_out[0] = 2 sum_i ln L_ii. */
+int jxg_potrf_block(void);
+int jxg_dpotrf_lower_f64(double *d_a, int n, int64_t lda, int *h_info, void *stream);
+int jxg_dpotrs_lower_f64(const double *d_l, int n, int64_t ldl, double *d_b, int nrhs, int64_t ldb, void *stream);
+int jxg_reml_combine_f64(const double *d_kstack, int q, int n, const double *h_theta, double *d_v, void *stream);
+int jxg_sym_dot_f64(const double *d_a, const double *d_b, int n, int64_t lda, int64_t ldb, double *d_out, void *stream);
+int jxg_potrf_logdet_f64(const double *d_l, int n, int64_t ldl, double *h_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

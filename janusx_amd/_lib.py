@@ -189,6 +189,12 @@ SIGNATURES = {
     "jxg_pairscreen_tables_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_i, c_p, c_l, c_p, c_p, c_p],
     "jxg_pairscreen_scan_p32": [c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_l, c_p, c_l, c_d, c_d, c_p, c_i, c_d, c_l, c_p, c_p, c_p,
                                 c_p, c_p, c_p, c_p],
+    "jxg_potrf_block": [],
+    "jxg_dpotrf_lower_f64": [c_p, c_i, c_l, c_p, c_p],
+    "jxg_dpotrs_lower_f64": [c_p, c_i, c_l, c_p, c_i, c_l, c_p],
+    "jxg_reml_combine_f64": [c_p, c_i, c_i, c_p, c_p, c_p],
+    "jxg_sym_dot_f64": [c_p, c_p, c_i, c_l, c_l, c_p, c_p],
+    "jxg_potrf_logdet_f64": [c_p, c_i, c_l, c_p, c_p],
 }
 _RESTYPES = {"jx_last_error": C.c_char_p, "jxg_last_kernel_ms": C.c_float, "jxg_lmm_tables_bytes": C.c_int64,
              "jxg_t32_bytes": C.c_int64, "jxg_eigh_dist_staging_doubles": C.c_int64, "jxg_eigh_band_staging_doubles": C.c_int64,

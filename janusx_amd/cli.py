@@ -1971,6 +1971,181 @@ def cmd_fvlmm2(args):
     return 0
 
 
+_REML_MISSING = {"", "na", "nan", "null", "none", "."}
+
+
+def _read_table_text(path):
+    """Header + rows of a tab/space/comma delimited table as text: (ids, column names, list of string rows)."""
+    with open(path) as fh:
+        header = fh.readline().rstrip("\n").replace(",", "\t").split()
+        ids, rows = [], []
+        for line in fh:
+            parts = line.rstrip("\n").replace(",", "\t").split()
+            if parts:
+                ids.append(parts[0])
+                rows.append(parts[1:])
+    names = header[1:]
+    for r in rows:
+        r.extend([""] * (len(names) - len(r)))
+    return ids, names, rows
+
+
+def _reml_columns(spec_list):
+    """The comma lists of -c / -rc as tokens; `A:B` interaction terms are not built."""
+    out = []
+    for spec in spec_list or []:
+        for tok in str(spec).split(","):
+            tok = tok.strip()
+            if not tok:
+                continue
+            if ":" in tok:
+                raise SystemExit(f"reml: the interaction term '{tok}' (A:B) is not built on this build; give single columns")
+            out.append(tok)
+    return out
+
+
+def _reml_refusals(args):
+    """Everything `jx reml` refuses is refused here, before any file is opened."""
+    for flag, what in (("gxe", "-gxe"), ("gxc", "-gxc"), ("spk", "-spk"), ("spk_mode", "--spk-mode")):
+        if getattr(args, flag, None):
+            raise SystemExit(f"reml: {what} is not built on this build (dense multi-kernel REML over -k and -rc terms only)")
+    cov, rc = _reml_columns(args.cov), _reml_columns(args.rcov)
+    if not args.ncol:
+        raise SystemExit("reml needs -n TRAIT")
+    if not args.grm and not rc:
+        raise SystemExit("reml needs at least one random term: -k GRM.npy or -rc COLUMN")
+    if not args.out:
+        raise SystemExit("reml needs -o OUT")
+    return cov, rc
+
+
+def _reml_col_index(tok, names, what):
+    if tok in names:
+        return names.index(tok)
+    if tok.isdigit() and int(tok) < len(names):
+        return int(tok)
+    raise SystemExit(f"reml: unknown {what} column '{tok}'")
+
+
+def cmd_reml(args):
+    """`jx reml -p PHENO -n TRAIT [-k GRM.npy]... [-c COLS] [-rc COLS] -o OUT`: y = fixed + one random term per -k + one per -rc + e
+    by multi-kernel AI-REML on the device (`blup.BLUP`; python/janusx/pyBLUP/blup.py:610-1004 is the class behind the reference's
+    `jx reml`).  Samples: the ids present in every -k id list with the trait, every -c and every -rc column non-missing, in
+    phenotype order; each id once.  -> `{out}.reml.vc.tsv` (trait, n, term, theta, var, pve, reml, ml, iters, route; one line per
+    term, residual last) and `{out}.reml.blup.tsv` (id, trait, fixed, one column per random term, residual).  These tables are this
+    build's own: the reference's `.reml.summary.tsv`, `.blue.txt`, `.blup.txt` belong to its line x environment workflow, which is
+    refused (a repeated id), as are -gxe, -gxc, -spk, --spk-mode, A:B terms and non-numeric -c columns.  -exact-trace is an
+    extension: the exact trace of V^-1 K_j at every n (the reference uses Hutchinson probes above n = 768)."""
+    cov_tok, rc_tok = _reml_refusals(args)
+    rank, _world = _dist_setup()
+    if rank != 0:                                             # one GPU does the work
+        return 0
+    ids, names, rows = _read_table_text(args.pheno)
+    seen = set()
+    for s in ids:
+        if s in seen:
+            raise SystemExit(f"reml: sample id '{s}' occurs more than once in {args.pheno}; repeated records per line are the "
+                             "reference's line x environment workflow, which is not built on this build")
+        seen.add(s)
+    traits = _select_traits(names, args.ncol)
+    cov_idx = [_reml_col_index(t, names, "-c") for t in cov_tok]
+    rc_idx = [_reml_col_index(t, names, "-rc") for t in rc_tok]
+
+    def missing(v):
+        return v.strip().lower() in _REML_MISSING
+
+    def number(v, col):
+        try:
+            return float(v)
+        except ValueError:
+            raise SystemExit(f"reml: -c column '{names[col]}' is not numeric ('{v}'); categorical fixed effects are not built "
+                             "on this build, give the column to -rc") from None
+
+    cov_val = np.full((len(ids), len(cov_idx)), np.nan)
+    for j, c in enumerate(cov_idx):
+        for i, r in enumerate(rows):
+            if not missing(r[c]):
+                cov_val[i, j] = number(r[c], c)
+    grm_ids = []
+    for path in args.grm or []:
+        id_path = path + ".id"
+        if os.path.exists(id_path):
+            with open(id_path) as fh:
+                grm_ids.append([ln.split()[0] for ln in fh if ln.strip()])
+        else:
+            grm_ids.append(list(ids))                          # no id file: the matrix is in phenotype order (_load_grm checks its shape)
+    grm_sets = [set(g) for g in grm_ids]
+    in_all = [all(s in g for g in grm_sets) for s in ids]
+    # every matrix is loaded once, over the records present in all of them (phenotype order); a trait takes its rows from that
+    common = [i for i in range(len(ids)) if in_all[i]]
+    common_pos = {i: k for k, i in enumerate(common)}
+    grm_common = []
+    for path in args.grm or []:
+        if os.path.exists(path + ".id"):
+            grm_common.append(np.asarray(_load_grm(path, [ids[i] for i in common]), dtype=np.float64))
+        else:
+            grm_common.append(np.asarray(_load_grm(path, ids), dtype=np.float64)[np.ix_(common, common)])
+    from . import blup
+    out = args.out
+    parent = os.path.dirname(out)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    vc_lines, blup_lines = [], []
+    terms = [f"rc:{names[c]}" for c in rc_idx] + [f"k:{os.path.basename(p)}" for p in args.grm or []]
+    for t in traits:
+        keep = []
+        for i, r in enumerate(rows):
+            if not in_all[i] or missing(r[t]) or any(missing(r[c]) for c in rc_idx) or not np.all(np.isfinite(cov_val[i])):
+                continue
+            try:
+                float(r[t])
+            except ValueError:
+                continue
+            keep.append(i)
+        if len(keep) < 3:
+            raise SystemExit(f"reml: trait '{names[t]}' has {len(keep)} usable samples")
+        sel_ids = [ids[i] for i in keep]
+        y = np.array([float(rows[i][t]) for i in keep])
+        x = cov_val[keep] if cov_idx else None
+        z_list = []
+        for c in rc_idx:
+            levels = sorted({rows[i][c] for i in keep})
+            pos = {v: k for k, v in enumerate(levels)}
+            z = np.zeros((len(keep), len(levels)))
+            z[np.arange(len(keep)), [pos[rows[i][c]] for i in keep]] = 1.0
+            z_list.append(z)
+        sub = [common_pos[i] for i in keep]
+        g_list = [np.ascontiguousarray(g[np.ix_(sub, sub)]) for g in grm_common]
+        t0 = time.perf_counter()
+        try:
+            fit = blup.BLUP(y, X=x, Z=z_list or None, G=g_list or None, maxiter=args.maxiter, progress=False,
+                            exact_trace=bool(args.exact_trace))
+        except (RuntimeError, ValueError, np.linalg.LinAlgError) as e:
+            raise SystemExit(f"reml: {e}") from None
+        total = float(np.sum(fit.var))
+        for term, th, v in zip(terms + ["residual"], fit.theta, fit.var):
+            vc_lines.append(f"{names[t]}\t{len(keep)}\t{term}\t{th:.10g}\t{v:.10g}\t{v / total:.10g}\t{fit.reml:.10g}\t{fit.ml:.10g}\t"
+                            f"{int(getattr(fit.result, 'nit', 0))}\t{fit.route}")
+        fixed = fit.X @ fit.beta
+        parts, start = [], 0
+        for z, w in zip(z_list, fit.z_cols):
+            parts.append(z @ fit.u[start:start + w])
+            start += w
+        parts += list(fit.g_by_G)
+        for k, s in enumerate(sel_ids):
+            cells = "\t".join(f"{float(pt[k, 0]):.10g}" for pt in parts)
+            blup_lines.append(f"{s}\t{names[t]}\t{float(fixed[k, 0]):.10g}\t{cells}\t{float(fit.residuals[k, 0]):.10g}")
+        print(f"reml: trait {names[t]}: n={len(keep)}, route {fit.route}, {int(getattr(fit.result, 'nit', 0))} iterations, "
+              f"reml={fit.reml:.6f}, pve " + ", ".join(f"{tm}={v / total:.4f}" for tm, v in zip(terms, fit.var))
+              + f" ({time.perf_counter() - t0:.2f} s)")
+    with open(out + ".reml.vc.tsv", "w") as fh:
+        fh.write("trait\tn\tterm\ttheta\tvar\tpve\treml\tml\titers\troute\n" + "".join(ln + "\n" for ln in vc_lines))
+    with open(out + ".reml.blup.tsv", "w") as fh:
+        fh.write("id\ttrait\tfixed\t" + "\t".join(terms) + "\tresidual\n" + "".join(ln + "\n" for ln in blup_lines))
+    print(f"  {out}.reml.vc.tsv\n  {out}.reml.blup.tsv")
+    return 0
+
+
 def _add_admixture_parser(sub, name):
     a = sub.add_parser(name)
     a.add_argument("-bfile", "--bfile", default=None)
@@ -2250,6 +2425,25 @@ def main(argv=None):
     for flag in ("vcf", "hmp", "file"):
         v.add_argument(f"-{flag}", f"--{flag}", dest=flag, default=None, help=argparse.SUPPRESS)
     v.set_defaults(func=cmd_fvlmm2)
+    m = sub.add_parser("reml")
+    m.add_argument("-p", "--pheno", required=True)
+    m.add_argument("-n", "--n", dest="ncol", action="append", default=None)
+    m.add_argument("-k", "--grm", dest="grm", action="append", default=None,
+                   help="dense GRM (.npy with a sibling .id); may be repeated: one variance component each")
+    m.add_argument("-c", "--cov", dest="cov", action="append", default=None,
+                   help="numeric fixed-effect columns of the phenotype table, by name or 0-based index, comma lists")
+    m.add_argument("-rc", "--rcov", dest="rcov", action="append", default=None,
+                   help="random-effect columns of the phenotype table: the distinct values of a column are its levels")
+    m.add_argument("-maxiter", "--maxiter", dest="maxiter", type=int, default=100)
+    m.add_argument("-exact-trace", "--exact-trace", dest="exact_trace", action="store_true", default=False,
+                   help="exact trace of V^-1 K at every n (an extension; the reference uses Hutchinson probes above n = 768)")
+    m.add_argument("-o", "--out", default=None)
+    m.add_argument("-t", "--thread", "--threads", dest="thread", type=int, default=0, help="accepted for compatibility; unused")
+    m.add_argument("-gxe", "--gxe", dest="gxe", nargs="?", const=True, default=None, help=argparse.SUPPRESS)
+    m.add_argument("-gxc", "--gxc", dest="gxc", nargs="?", const=True, default=None, help=argparse.SUPPRESS)
+    m.add_argument("-spk", "--spk", dest="spk", nargs="?", const=True, default=None, help=argparse.SUPPRESS)
+    m.add_argument("--spk-mode", dest="spk_mode", default=None, help=argparse.SUPPRESS)
+    m.set_defaults(func=cmd_reml)
     args = ap.parse_args(argv)
     return args.func(args)
 

@@ -6863,3 +6863,99 @@ def farmcpu_packed_to_tsv(y, x_cov, packed, n_samples, row_flip, row_maf, row_mi
         qtn_rows = fc.write_qtn_tsv(pseudo_tsv, res.qtn, chrom, pos, snp, a0, a1, maf, res.miss, res.stats, rows)
     _done(progress_callback, m)
     return written, len(res.qtn), qtn_rows, res.stage1_secs, res.stage2_secs + (time.perf_counter() - t0)
+
+
+# ---- multi-kernel AI-REML (src/stats/reml.rs:703-1049) ------------------------------------------------------------------------
+
+def _reml_probe_signs(n, probes, seed):
+    """The +-1 Hutchinson probes of reml.rs:798-806 -> (probes, n) f64, probe-major then sample.  Entry k of probe i is -1 when
+    `rng.random::<f64>() < 0.5`; with rand 0.9's `(next_u64 >> 11) 2^-53` that is bit 63 of the u64 clear: the top bit of the
+    SECOND u32 word of the pair.  The words come from `_stdrng_words`, so this inherits the "parity unpinned" status of the StdRng
+    restatement (README, "Known differences"): it pins this build's stream, not the crate's."""
+    n, probes = int(n), int(probes)
+    w = _stdrng_words(seed, 2 * n * probes)
+    hi = w[1::2]
+    return np.where((hi >> np.uint32(31)) == 0, -1.0, 1.0).reshape(probes, n)
+
+
+def ai_reml_multi_f64(k_stack, xcov, y, max_iter=100, tol=1e-6, min_var=1e-12, trace_probes=8, trace_seed=42, _fitter=None):
+    """`ai_reml_multi_f64` (src/stats/reml.rs:703-1049): average-information REML over q n x n kernels plus the residual
+    -> (theta ndarray (q + 1), ml, reml, used_iter, converged).  Literal to the source: the argument checks and their messages
+    (RuntimeError, before any device call), the start value var(y) / (q + 1), the `max(min_var)` clamp, the 24-step halving with
+    acceptance `reml_cand >= reml_curr - 1e-12`, the stop on the largest relative change < tol, and every early `break`, which
+    returns the last values with converged = False.  `use_exact_trace = trace_probes == 0 or n <= 768`; otherwise the probes of
+    `_reml_probe_signs` (parity with the crate's StdRng stream is unpinned, see there).  Every likelihood evaluation is
+    `pipeline.MultiKernelReml.profile`, every step `ai_step`: V is formed, factored and solved on the device.
+    `k_stack` may be a CUDA f64 tensor (an extension: kernels already in HBM are not staged through the host); `_fitter`, a
+    `MultiKernelReml` built from the same arguments, is reused instead of building one (`blup.BLUP`)."""
+    if not hasattr(k_stack, "shape"):
+        k_stack = np.asarray(k_stack, dtype=np.float64)
+    kshape = tuple(k_stack.shape)
+    if len(kshape) != 3:
+        raise RuntimeError("k_stack must be 3D (q, n, n)")
+    q, n = int(kshape[0]), int(kshape[1])
+    if int(kshape[2]) != n:
+        raise RuntimeError("k_stack must be (q, n, n)")
+    if q == 0:
+        raise RuntimeError("k_stack requires at least one kernel")
+    y = _c(y, np.float64).reshape(-1)
+    if y.shape[0] != n:
+        raise RuntimeError("len(y) must equal n in k_stack")
+    x = _c(xcov, np.float64)
+    if x.ndim != 2:
+        raise RuntimeError("xcov must be 2D (n, p)")
+    if x.shape[0] != n:
+        raise RuntimeError("xcov.n_rows must equal n in k_stack")
+    p = int(x.shape[1])
+    if p == 0:
+        raise RuntimeError("xcov must have at least one column")
+    if n <= p:
+        raise RuntimeError("n must be > p in xcov")
+    min_var = float(min_var) if np.isfinite(min_var) and min_var > 0.0 else 1e-12
+    tol = float(tol) if np.isfinite(tol) and tol > 0.0 else 1e-6
+    trace_probes = int(trace_probes)
+    use_exact_trace = trace_probes == 0 or n <= 768
+    probes = None if use_exact_trace else _reml_probe_signs(n, max(trace_probes, 1), int(trace_seed))
+    if _fitter is None:
+        from . import pipeline
+        _fitter = pipeline.MultiKernelReml(k_stack, x, y)
+    fit = _fitter
+
+    mean = float(np.sum(y)) / float(n)
+    var_y = float(np.sum((y - mean) ** 2)) / float(max(n, 2) - 1)
+    if not np.isfinite(var_y) or var_y <= 0.0:
+        var_y = 1.0
+    m = q + 1
+    theta = np.full(m, max(var_y / float(m), min_var))
+    converged, used_iter = False, 0
+    last_ml = last_reml = float("nan")
+    for it in range(int(max_iter)):
+        used_iter = it + 1
+        prof = fit.profile(theta)
+        if prof is None:
+            break
+        reml_curr, ml_curr = prof[0], prof[1]
+        last_reml, last_ml = reml_curr, ml_curr
+        step_out = fit.ai_step(theta, probes)
+        if step_out is None:
+            break
+        delta = step_out[2]
+        accepted, step = False, 1.0
+        theta_next, reml_next, ml_next = theta.copy(), reml_curr, ml_curr
+        for _ in range(24):
+            cand = np.maximum(theta + step * delta, min_var)
+            pc = fit.profile(cand)
+            if pc is not None and np.isfinite(pc[0]) and pc[0] >= reml_curr - 1e-12:
+                accepted, theta_next, reml_next, ml_next = True, cand, pc[0], pc[1]
+                break
+            step *= 0.5
+            if step < 1e-8:
+                break
+        if not accepted:
+            break
+        rel_max = float(np.max(np.abs(theta_next - theta) / np.maximum(theta, min_var)))
+        theta, last_reml, last_ml = theta_next, reml_next, ml_next
+        if rel_max < tol:
+            converged = True
+            break
+    return np.asarray(theta, dtype=np.float64), float(last_ml), float(last_reml), int(used_iter), bool(converged)

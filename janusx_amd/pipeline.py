@@ -1858,3 +1858,182 @@ def run_gwas(packed: torch.Tensor, n_samples: int, y: np.ndarray, covar: np.ndar
     tm.add("scan_total", t5 - t4)
     tm.add("total", t5 - t0)
     return GwasResult(keep, af_k, miss_k, res, model.null, geff, tm.t)
+
+
+class MultiKernelReml:
+    """Device-resident evaluation of the multi-kernel REML of `ai_reml_multi_f64` (src/stats/reml.rs:703-1049):
+    V = sum_j theta_j K_j + theta_e I is formed, factored and solved in HBM (csrc/k_potrf.hip: `jxg_reml_combine_f64`,
+    `jxg_dpotrf_lower_f64`, `jxg_dpotrs_lower_f64`); the p x p and m x m algebra is host f64 numpy.
+
+    `k_stack` (q, n, n) numpy or CUDA f64 tensor, symmetrised as the reference does ((K + K') / 2, reml.rs:776) and kept in HBM;
+    `x` (n, p) fixed-effect design, `y` (n,).  The factor and the pieces of the last `profile` are kept: asking for the same theta
+    again (the accepted line-search candidate becomes the next iteration's theta) costs nothing and changes no number."""
+
+    def __init__(self, k_stack, x, y):
+        ks = k_stack if torch.is_tensor(k_stack) else torch.from_numpy(np.ascontiguousarray(k_stack, dtype=np.float64))
+        if ks.dim() != 3 or ks.shape[1] != ks.shape[2] or ks.shape[0] < 1:
+            raise RuntimeError("k_stack must be (q, n, n)")
+        ks = ks.to(device="cuda", dtype=torch.float64)
+        self.ks = ((ks + ks.transpose(1, 2)) * 0.5).contiguous()
+        del ks
+        self.q, self.n = int(self.ks.shape[0]), int(self.ks.shape[1])
+        self.x = np.ascontiguousarray(x, dtype=np.float64).reshape(self.n, -1)
+        self.y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        self.p = int(self.x.shape[1])
+        self.v = torch.empty((self.n, self.n), dtype=torch.float64, device="cuda")
+        self.logdet = float("nan")
+        self._fac_key = None
+        self._prof_key, self._prof = None, None
+        self.n_factor = 0                       # factorisations done (the timing script and the tests read it)
+
+    # ---- device pieces --------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _key(theta):
+        return np.ascontiguousarray(theta, dtype=np.float64).reshape(-1).tobytes()
+
+    def _factor(self, theta):
+        """The Cholesky factor of V(theta) in the lower triangle of self.v; False when a pivot fails (the reference's
+        `v.cholesky()` returning None)."""
+        th = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+        if th.shape[0] != self.q + 1:
+            raise RuntimeError(f"theta must have q + 1 = {self.q + 1} entries")
+        key = th.tobytes()
+        if key == self._fac_key:
+            return True
+        self._fac_key = None
+        import ctypes as C
+        info = C.c_int(0)
+        ld = C.c_double(0.0)
+        check(lib().jxg_reml_combine_f64(self.ks.data_ptr(), self.q, self.n, th.ctypes.data, self.v.data_ptr(), _stream()))
+        check(lib().jxg_dpotrf_lower_f64(self.v.data_ptr(), self.n, self.n, C.addressof(info), _stream()))
+        self.n_factor += 1
+        if info.value != 0:
+            return False
+        check(lib().jxg_potrf_logdet_f64(self.v.data_ptr(), self.n, self.n, C.addressof(ld), _stream()))
+        self.logdet = float(ld.value)
+        self._fac_key = key
+        return True
+
+    def solve(self, cols):
+        """V^-1 applied to the columns `cols` (n, c) numpy -> (n, c) numpy, with the current factor."""
+        b = torch.from_numpy(np.ascontiguousarray(np.asarray(cols, dtype=np.float64).reshape(self.n, -1).T)).cuda()
+        check(lib().jxg_dpotrs_lower_f64(self.v.data_ptr(), self.n, self.n, b.data_ptr(), int(b.shape[0]), self.n, _stream()))
+        return np.ascontiguousarray(b.cpu().numpy().T)
+
+    def _kernel_products(self, cols):
+        """K_j cols for every kernel: one dgemm each -> list of q (n, c) numpy arrays."""
+        r = torch.from_numpy(np.ascontiguousarray(np.asarray(cols, dtype=np.float64).T)).cuda()      # (c, n): column-major n x c
+        c = int(r.shape[0])
+        out = torch.empty_like(r)
+        res = []
+        for j in range(self.q):
+            check(lib().jxg_dgemm_f64(0, 0, self.n, c, self.n, 1.0, self.ks[j].data_ptr(), self.n, r.data_ptr(), self.n, 0.0,
+                                      out.data_ptr(), self.n, 0, _stream()))
+            res.append(np.ascontiguousarray(out.cpu().numpy().T))
+        return res
+
+    def _traces_exact(self):
+        """tr(V^-1 K_j), j < q, and tr(V^-1): V^-1 by n solves on the identity, the traces by `jxg_sym_dot_f64`."""
+        vinv = torch.eye(self.n, dtype=torch.float64, device="cuda")
+        check(lib().jxg_dpotrs_lower_f64(self.v.data_ptr(), self.n, self.n, vinv.data_ptr(), self.n, self.n, _stream()))
+        out = torch.empty(self.q, dtype=torch.float64, device="cuda")
+        for j in range(self.q):
+            check(lib().jxg_sym_dot_f64(vinv.data_ptr(), self.ks[j].data_ptr(), self.n, self.n, self.n, out[j:].data_ptr(), _stream()))
+        tr = list(out.cpu().numpy())
+        tr.append(float(np.sum(vinv.diagonal().cpu().numpy())))
+        return np.asarray(tr, dtype=np.float64)
+
+    # ---- the two blocks of the iteration ----------------------------------------------------------------------------------------
+    def profile(self, theta):
+        """reml.rs:833-884 (and 966-1012 for a candidate): -> (reml, ml, pieces), or None where the reference breaks or halves the
+        step: a failed Cholesky of V or of X'V^-1X, r'V^-1r not positive and finite, a value that is not finite.  One rule serves
+        both uses, so a candidate whose ml alone is not finite is rejected too, where reml.rs:1013 tests only reml_cand; with
+        r'V^-1r positive and finite the two differ by finite terms, so the case does not arise."""
+        key = self._key(theta)
+        if key == self._prof_key:
+            return self._prof
+        self._prof_key, self._prof = None, None
+        if not self._factor(theta):
+            return None
+        n, p, x, y = self.n, self.p, self.x, self.y
+        sol = self.solve(np.concatenate([x, y[:, None]], axis=1))
+        vinv_x, vinv_y = sol[:, :p], sol[:, p]
+        xt_vinv_x = x.T @ vinv_x
+        try:
+            lx = np.linalg.cholesky(xt_vinv_x)
+        except np.linalg.LinAlgError:
+            return None
+        eye_p = np.eye(p)
+        c_inv = np.linalg.solve(lx.T, np.linalg.solve(lx, eye_p))
+        beta = np.linalg.solve(lx.T, np.linalg.solve(lx, x.T @ vinv_y))
+        r = y - x @ beta
+        vinv_r = self.solve(r[:, None])[:, 0]
+        alpha = vinv_r - vinv_x @ (c_inv @ (x.T @ vinv_r))
+        qval = float(r @ vinv_r)
+        if not np.isfinite(qval) or qval <= 0.0:
+            return None
+        log_det_v = self.logdet
+        log_det_xt = float(2.0 * np.sum(np.log(np.diag(lx))))
+        nf, pf = float(n), float(p)
+        reml_c = (nf - pf) * (math.log(nf - pf) - 1.0 - math.log(2.0 * math.pi)) / 2.0
+        reml = reml_c - 0.5 * ((nf - pf) * math.log(qval) + log_det_v + log_det_xt)
+        ml_c = nf * (math.log(nf) - 1.0 - math.log(2.0 * math.pi)) / 2.0
+        ml = ml_c - 0.5 * (nf * math.log(qval) + log_det_v)
+        if not np.isfinite(reml) or not np.isfinite(ml):
+            return None
+        pieces = {"vinv_x": vinv_x, "c_inv": c_inv, "beta": beta, "r": r, "vinv_r": vinv_r, "alpha": alpha, "qval": qval,
+                  "log_det_v": log_det_v, "log_det_xt": log_det_xt}
+        self._prof_key, self._prof = key, (float(reml), float(ml), pieces)
+        return self._prof
+
+    def ai_step(self, theta, probes=None):
+        """reml.rs:886-952: -> (score, ai, delta) at theta, or None where the reference breaks (no factor, a singular AI matrix, a
+        step that is not finite).  probes None: the exact trace through V^-1; otherwise `probes` (n_probes, n) of +-1 and the
+        Hutchinson estimate with the cached V^-1 z."""
+        prof = self.profile(theta)
+        if prof is None:
+            return None
+        if not self._factor(theta):             # the factor of this theta (a failed candidate in between replaces it)
+            return None
+        pc = prof[2]
+        n, p, q, m = self.n, self.p, self.q, self.q + 1
+        alpha, vinv_x, c_inv = pc["alpha"], pc["vinv_x"], pc["c_inv"]
+        cols = [alpha[:, None], vinv_x]
+        if probes is not None:
+            z = np.ascontiguousarray(probes, dtype=np.float64).reshape(-1, n)
+            vinv_z = self.solve(z.T)
+            cols.append(z.T)
+            tr1 = np.zeros(m)
+        else:
+            tr1 = self._traces_exact()
+        rmat = np.concatenate(cols, axis=1)
+        prods = self._kernel_products(rmat) + [rmat]            # the residual's kernel is the identity
+        score = np.zeros(m)
+        ka = np.empty((n, m))
+        for j in range(m):
+            kr = prods[j]
+            ka[:, j] = kr[:, 0]
+            quad = float(alpha @ kr[:, 0])
+            if probes is not None:
+                kz = kr[:, 1 + p:]
+                s = 0.0
+                for i in range(z.shape[0]):
+                    s += float(vinv_z[:, i] @ kz[:, i])
+                tr1[j] = s / float(z.shape[0])
+            bt_kb = vinv_x.T @ kr[:, 1:1 + p]
+            tr2 = float(np.sum(c_inv * bt_kb.T))
+            score[j] = -0.5 * ((tr1[j] - tr2) - quad)
+        vinv_ka = self.solve(ka)
+        pka = vinv_ka - vinv_x @ (c_inv @ (vinv_x.T @ ka))
+        ai = np.zeros((m, m))
+        for a in range(m):
+            for b in range(a + 1):
+                ai[a, b] = ai[b, a] = 0.5 * float(ka[:, a] @ pka[:, b])
+        ai[np.diag_indices(m)] += 1e-10
+        try:
+            delta = np.linalg.solve(ai, score)
+        except np.linalg.LinAlgError:
+            return None
+        if not np.all(np.isfinite(delta)):
+            return None
+        return score, ai, delta
